@@ -11,8 +11,14 @@ estimation draws are independent, so `certify` runs them in the same classifier 
 every image -- into 255-sample classifier batches that are not aligned to image boundaries and sums all histograms of the group
 with one all-reduce (same sample indices, counts, labels and radii as K separate `certify` calls; tested).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--cpu-budget-s S] [--cpu-baseline-headline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--cpu-budget-s S] [--cpu-baseline-headline]]
     (extra, NON-headline data points: --workload encode_img | rgf | minigpt4, --img-size 448, --n 1000 / --n0 K)
+    A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, roofline from the timed region's own
+    HIP events; at N > 1 the `ranks` report).  Everything measured outside the timed steps runs only under --full: the CPU baseline +
+    parity legs, the reference-shaped single-image time, the image-sharded pass (N > 1), the MFMA-only device rate and the MiniGPT-4
+    phase breakdown.  --dump-outputs DIR writes what a caller of the timed path received in the last timed step as DIR/<name>.npy
+    (certify: label.npy, radius.npy; rgf: label.npy, history.npy of vote shares, x_adv.npy), for output-for-output
+    comparison of two builds: with the same arguments, weights, images and noise draws are the same from run to run.
     environment: CGPT_BENCH_FORCE_NCCL=1 with --gpus 1 = the whole multi-rank code path over RCCL with a world of ONE rank (first contact
     with the collective on a one-GPU box); CGPT_BENCH_ONLY_TIMED=1 = profiling runs (tools/pmc_summary.py): nothing but the timed region's
     batches reaches the GPU, one stream synchronisation per classifier batch.
@@ -184,6 +190,21 @@ def cpu_baseline_and_parity(clf, x, process_group=None):
     return baseline, parity
 
 
+def dump_outputs(out_dir, result, last_attack):
+    """--dump-outputs: what a caller of the timed path received in the last timed step, as .npy files (float64; the image float32).
+    certify returns (label, radius); RGFAttack.attack returns (x_adv, label, history) and the step keeps x_adv and history aside."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    label, second = result
+    if last_attack:
+        arrays = {"label": np.float64([label]), "history": np.float64(last_attack["history"]),
+                  "x_adv": last_attack["x_adv"].float().cpu().numpy()}
+    else:
+        arrays = {"label": np.float64([label]), "radius": np.float64([second])}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_ranks(n, argv):
     """Parent of a self-contained N-rank run: start the ranks as a child process and relay its exit code.  Nothing in this
     process has touched the GPU (torch.cuda.device_count() does not initialise it)."""
@@ -210,8 +231,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None)
+    # everything outside the timed steps (CPU / parity legs, single-image call, image-sharded pass, MFMA-only rate, MiniGPT-4 phases)
+    ap.add_argument("--full", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    # the CPU leg on the headline config itself (n0 = n = 100, sigma = 0.5: ~100 s of host time) beside the default configs[0] leg
+    # --full: the CPU leg on the headline config itself (n0 = n = 100, sigma = 0.5: ~100 s of host time) beside the default configs[0] leg
     ap.add_argument("--cpu-baseline-headline", action="store_true")
     # ... which also runs by default at --gpus 1 when its projected time (10 x the configs[0] leg) fits this many seconds; 0 = never
     ap.add_argument("--cpu-budget-s", type=float, default=300.0)
@@ -223,6 +247,10 @@ def main():
     ap.add_argument("--decode", choices=["graph", "hf"], default="graph")   # --workload minigpt4: greedy decode as one hipGraph | HF generate
     ap.add_argument("--prefill-linear", choices=["cgpt", "torch"], default="cgpt")   # graph decode: the prefill's linears through this library's GEMM
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.cpu_baseline_headline and not args.full:
+        ap.error("--cpu-baseline-headline is a leg of --full")
     headline = args.workload == "vit_head" and args.img_size == 224 and args.n == N and args.n0 == N0
     n_est, n_sel = args.n, args.n0
     rgf = args.workload == "rgf"                     # BASELINE configs[4]: 8-step RGF x smoothed predict(N) on ViT-G + head
@@ -337,10 +365,12 @@ def main():
                 dist.barrier()
 
     attack = cg.RGFAttack(smooth, steps=8, num_dirs=1, delta=0.5, lr=0.05, eps=0.25, dir_seed=1234) if rgf else None
+    last_attack = {}                                 # rgf: the adversarial image and vote-share history of the latest step (--dump-outputs)
 
     def step(img):
         if rgf:                                      # attack towards class 1, then the smoothed prediction of the result
-            _, label, hist = attack.attack(img, 1, n_est, ALPHA, per_gpu, targeted=True)
+            x_adv, label, hist = attack.attack(img, 1, n_est, ALPHA, per_gpu, targeted=True)
+            last_attack.update(x_adv=x_adv, history=hist)
             return label, hist[-1]
         return smooth.certify(img, n_sel, n_est, ALPHA, per_gpu)
 
@@ -367,6 +397,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     clf.profile(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, results[-1], last_attack)
     ranks_report = None
     if collective:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
@@ -496,7 +528,7 @@ def main():
     # (smoothing.py:29-56), i.e. no grouping of images; every rank takes part (its shard + the all-reduce).
     single_ms = None
     only_timed = os.environ.get("CGPT_BENCH_ONLY_TIMED", "") not in ("", "0")   # profiling runs (tools/pmc_summary.py): nothing but the
-    if not rgf and not only_timed:                                              # timed region's full batches reaches the GPU
+    if args.full and not rgf and not only_timed:                                # timed region's full batches reaches the GPU
         reps = 3
         smooth.certify(images[0], n_sel, n_est, ALPHA, n_sel + n_est)
         torch.cuda.synchronize()
@@ -512,7 +544,7 @@ def main():
     # certifies whole images with all their draws, no vote all-reduce; 16 bytes per image come back).  Same sample indices as the
     # timed region, so the (label, radius) list must be the same list.  Outside the timed region; reported beside the headline.
     image_sharded = None
-    if collective and not rgf and not gen:
+    if args.full and collective and not rgf and not gen:
         sm2 = cg.Smooth(base, NUM_CLASSES, SIGMA, seed=42, force_collective=forced)
         sm2.certify_images(images[:min(world, len(images))], n_sel, n_est, ALPHA, per_gpu)      # untimed: first use of this path
         sm2.reset(args.warmup * (n_sel + n_est))                                             # the cursor of the timed region
@@ -536,7 +568,7 @@ def main():
     # The yardstick beside the data-sheet peak: the dense fp16 MFMA rate THIS device sustains on random operands with nothing else
     # running (cgpt_mfma_sustained: MFMA-only loop, ~2 s, clock settled first), measured after everything else, rank 0 of a 1-GPU run only.
     sustained = None
-    if world == 1 and rank == 0 and headline and not os.environ.get("CGPT_BENCH_NO_SUSTAINED") and not only_timed:
+    if args.full and world == 1 and rank == 0 and headline and not os.environ.get("CGPT_BENCH_NO_SUSTAINED") and not only_timed:
         import ctypes as C
         tf, ghz = C.c_double(), C.c_double()
         if cg.lib().cgpt_mfma_sustained(2.0, C.byref(tf), C.byref(ghz)) == 0:
@@ -546,7 +578,7 @@ def main():
                                  "measured in this run, after the timed region (profiles/r04/mfma_sustained.txt)"}
 
     gen_report = None
-    if gen:
+    if gen and args.full:
         # where a certified image's time goes (one 200-row batch, HIP events), and what the graph decode changes against HF generate
         def timed(fn, reps=3):
             fn()
@@ -637,10 +669,11 @@ def main():
                          "vit_gemms": by_kind,
                          "pmc": pmc_fc1, "device_sustained": sustained},
             "results_sample": [[int(l), float(r)] for l, r in results[-3:]],
-            "single_image_certify_ms": single_ms,
-            "single_image_certify_note": "one reference-shaped Smooth.certify(x, n0, n, alpha, batch_size=n0+n) per image, no grouping "
-                                         "of images (the headline value sends groups of images through Smooth.certify_many)",
         }
+        if args.full:
+            line["single_image_certify_ms"] = single_ms
+            line["single_image_certify_note"] = ("one reference-shaped Smooth.certify(x, n0, n, alpha, batch_size=n0+n) per image, no grouping "
+                                                 "of images (the headline value sends groups of images through Smooth.certify_many)")
         if sustained:
             sustained["frac_of_sustained"] = fc1_tflops / sustained["mfma_only_tflops"]
             sustained["all_gemms_frac_of_sustained"] = all_tflops / sustained["mfma_only_tflops"]
@@ -658,7 +691,8 @@ def main():
                          "answers (BASELINE configs[2])" % (("prefill + 19 steps replayed from one hipGraph" + (", the prefill's linears through "
                                                              "libcgpt's GEMM" if args.prefill_linear == "cgpt" else "")) if args.decode == "graph" else
                                                             "HF generate", per_gpu, len(base.label_map.answers)))
-                line["minigpt4_phases"] = gen_report
+                if args.full:
+                    line["minigpt4_phases"] = gen_report
             line["config"]["workload"] = (f"NON-HEADLINE data point: mode={mode}, image {args.img_size}x{args.img_size} (T={T}), "
                                           f"random-init weights, {what}")
             line["config"].update({"n0": n_sel, "n": n_est})
@@ -672,7 +706,7 @@ def main():
             line.pop("vit_tflops_end_to_end", None)
             line["roofline"]["traffic"] = None
             line["roofline"]["flop_per_launch"] = fc1_flops / max(fc1_n, 1)
-        if not args.no_cpu_baseline and headline:
+        if args.full and not args.no_cpu_baseline and headline:
             try:
                 cb, line["parity"] = cpu_baseline_and_parity(clf, images[0], process_group=cg.LOCAL_ONLY if world > 1 else None)
                 line["cpu_baseline"] = cb

@@ -200,7 +200,7 @@ def test_nccl_product_path_runs_on_one_gpu():
 
 
 def test_bench_ranks_block_over_nccl_on_one_gpu():
-    """`CGPT_BENCH_FORCE_NCCL=1 python bench.py --gpus 1`: bench.py's whole multi-rank code path (process group "nccl", barrier with
+    """`CGPT_BENCH_FORCE_NCCL=1 python bench.py --gpus 1 --full`: bench.py's whole multi-rank code path (process group "nccl", barrier with
     device_ids, MAX over ranks, per-rank timing gather, SUM of ones, image-sharded pass) on a world of one rank."""
     import json
     import subprocess
@@ -209,7 +209,7 @@ def test_bench_ranks_block_over_nccl_on_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0",
-                        "--cpu-budget-s", "0"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--cpu-budget-s", "0"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["collective_backend"] == "nccl" and line["rccl_ranks"] == 1
@@ -244,8 +244,8 @@ def test_bench_self_launches_its_ranks():
     root = os.path.dirname(HERE)
     env = dict(os.environ, CGPT_BENCH_ONE_GPU_REHEARSAL="1")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "0"],
-                       env=env, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "0",
+                        "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["collective_backend"] == "gloo" and line["rccl_ranks"] == 0
@@ -293,7 +293,7 @@ def test_bench_four_rank_rehearsal_runs_the_planned_batches():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "8", "--warmup", "0",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     rk = line["ranks"]
@@ -305,6 +305,35 @@ def test_bench_four_rank_rehearsal_runs_the_planned_batches():
     si = rk["scaling_inputs"]
     assert si["classifier_ms_per_image"] > 0 and si["host_statistics_ms_per_image"] > 0 and si["ms_per_step"] > 0
     assert line["image_sharded"]["equals_sample_sharded"] is True
+
+
+def test_bench_plain_run_times_the_steps_only_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py --gpus 1` line carries the headline figures of its timed steps and none of the legs --full adds after them;
+    --dump-outputs writes the (label, radius) the last timed step returned, and two runs with the same arguments write the same."""
+    import json
+    import subprocess
+    import numpy as np
+    root = os.path.dirname(HERE)
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "CGPT_BENCH_FORCE_NCCL", "CGPT_BENCH_ONE_GPU_REHEARSAL"):
+        env.pop(k, None)
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["unit"] == "certified images/s" and line["higher_is_better"] is True and line["dtype"] == "f16"
+        assert not {"cpu_baseline", "parity", "single_image_certify_ms", "image_sharded"} & set(line)
+        assert line["roofline"]["device_sustained"] is None and line["roofline"]["launches"] > 0
+        assert sorted(os.listdir(out)) == ["label.npy", "radius.npy"]
+        got = {n: np.load(out / (n + ".npy")) for n in ("label", "radius")}
+        assert all(a.dtype == np.float64 and a.shape == (1,) for a in got.values())
+        assert [int(got["label"][0]), float(got["radius"][0])] == line["results_sample"][-1]
+        dumps.append(got)
+    assert all(np.array_equal(dumps[0][n], dumps[1][n]) for n in ("label", "radius"))
 
 
 def test_c_level_allreduce_counts_single_rank_communicator():
