@@ -257,6 +257,42 @@ def test_layernorm_matches_torch(rows, D):
     assert float(y16[:, D:].abs().max()) == 0.0 if ld16 > D else True
 
 
+@pytest.mark.parametrize("D", [176, 768, 1408, 4096])
+def test_layernorm_hard_rows_match_float64(D):
+    """Rows a trained model produces and N(0, 1) rows do not: mean = 1e3 sigma (a one-pass E[x^2] - mean^2 variance loses
+    ~6e-2 of the output here), constant rows (sigma = 0: y = beta up to eps), and rows with four channels x 1e3.  176 runs
+    the float2 kernel, 768 / 4096 the 16-byte one, 1408 layernorm4_vitg_kernel.  Reference: float64 layer_norm of the same
+    fp32 input."""
+    L = cg.lib()
+    g = torch.Generator(device="cpu").manual_seed(7 * D)
+    z = torch.randn(12, D, generator=g, dtype=torch.float64)
+    sig = torch.tensor([1.0, 1e-2, 3e-1, 1e-3], dtype=torch.float64)[:, None]
+    offset = 1e3 * sig * torch.tensor([1.0, -1.0, 1.0, -1.0], dtype=torch.float64)[:, None]
+    far = offset + sig * z[:4]                                             # mean = +-1e3 sigma
+    const = torch.tensor([0.5, -3.0, 0.1, 7.25], dtype=torch.float64)[:, None].expand(4, D).clone()
+    outl = z[8:].clone()
+    outl[:, [1, D // 3, D // 2 + 5, D - 2]] *= 1e3                         # four channels x 1e3
+    x64 = torch.cat([far, const, outl]).float().double()                    # the kernel's input, exactly
+    x = x64.float()
+    rows = x.shape[0]
+    w = 1.0 + 0.1 * torch.randn(D, generator=g)
+    b = 0.1 * torch.randn(D, generator=g)
+    ld16 = ru(D, 64)
+    xd, wd, bd = x.to(DEV), w.to(DEV), b.to(DEV)
+    y16 = torch.zeros(rows, ld16, dtype=torch.float16, device=DEV)
+    y32 = torch.zeros(rows, D, device=DEV)
+    for eps in (1e-6, 1e-5):
+        _lib.check(L.cgpt_layernorm(P(xd), D, P(wd), P(bd), eps, P(y16), ld16, P(y32), D, rows, D, stream()))
+        ref = torch.nn.functional.layer_norm(x64, (D,), w.double(), b.double(), eps)
+        got = y32.cpu().double()
+        errs = [float((got[i:i + 4] - ref[i:i + 4]).abs().max()) for i in (0, 4, 8)]
+        print(f"layernorm D={D} eps={eps}: max abs err far-mean {errs[0]:.2e} constant {errs[1]:.2e} outlier {errs[2]:.2e}")
+        report(f"layernorm mean=1e3 sigma D={D}", got[:4], ref[:4], 2e-3)
+        report(f"layernorm constant rows D={D}", got[4:8], ref[4:8], 2e-3)
+        report(f"layernorm outlier rows D={D}", got[8:], ref[8:], 1e-3 * float(ref[8:].abs().max()))
+        report(f"layernorm f16 out D={D}", y16.cpu().double()[:, :D], got, 2e-3 * max(1.0, float(ref.abs().max())))
+
+
 def test_noise_stream_matches_oracle_and_is_shard_independent():
     x = torch.randn(3, 56, 56)
     xd = x.to(DEV)
