@@ -12,6 +12,7 @@ ERR_NAMES = {1: "CGPT_ERR_INVALID", 2: "CGPT_ERR_NO_DEVICE", 3: "CGPT_ERR_HIP", 
 MODE_VIT_HEAD = 0
 MODE_ENCODE_IMG = 1
 ABSTAIN = -1
+NOISE_LAWS = {"gaussian": 0, "uniform": 1}   # CGPT_NOISE_GAUSSIAN, CGPT_NOISE_UNIFORM
 
 
 class CgptError(RuntimeError):
@@ -44,6 +45,7 @@ SIGNATURES = {
     "cgpt_weight_numel": (_I64, [_P, C.c_char_p]),
     "cgpt_weight_name": (C.c_char_p, [_P, _I32]),
     "cgpt_init_synthetic_weights": (_I32, [_P, _U64, _P]),
+    "cgpt_set_noise_law": (_I32, [_P, _I32]),
     "cgpt_sample_counts": (_I32, [_P, _P, _I64, _I64, _I64, _F, _U64, _P, _P]),
     "cgpt_sample_counts2": (_I32, [_P, _P, _I64, _I64, _P, _I64, _I64, _P, _I64, _F, _U64, _P]),
     "cgpt_sample_counts_images": (_I32, [_P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _F, _U64, _P]),
@@ -53,14 +55,17 @@ SIGNATURES = {
     "cgpt_encode_img_noisy": (_I32, [_P, _P, _I64, _I64, _F, _U64, _P, _P]),
     "cgpt_get_activation": (_I32, [_P, C.c_char_p, _P, _I64, _P]),
     "cgpt_noise_batch": (_I32, [_P, _I64, _I64, _I64, _F, _U64, _P, _P]),
+    "cgpt_noise_batch_law": (_I32, [_P, _I64, _I64, _I64, _F, _I32, _U64, _P, _P]),
     "cgpt_rgf_step": (_I32, [_P, _P, _I64, _I64, _I32, _P, _F, _F, _U64, _P, _P]),
     "cgpt_vote": (_I32, [_P, _I64, _I32, _P, _P]),
     "cgpt_allreduce_counts": (_I32, [_P, _P, _I64, _P]),
     "cgpt_allreduce_counts_fn": (_I32, [_P, _P, _P, _I64, _P]),
     "cgpt_certify_from_counts": (_I32, [_P, _P, _I32, _I64, _D, _D, C.POINTER(_I32), C.POINTER(_D)]),
     "cgpt_certify_many_from_counts": (_I32, [_P, _I64, _I32, _I64, _D, _D, _P, _P]),
+    "cgpt_certify_many_from_counts_law": (_I32, [_P, _I64, _I32, _I64, _D, _D, _I32, _P, _P]),
     "cgpt_predict_from_counts": (_I32, [_P, _I32, _D, C.POINTER(_I32)]),
     "cgpt_certify_device": (_I32, [_P, _P, _I32, _I64, _D, _D, _P, _P]),
+    "cgpt_certify_device_law": (_I32, [_P, _P, _I32, _I64, _D, _D, _I32, _P, _P]),
     "cgpt_predict_device": (_I32, [_P, _I32, _D, _P, _P]),
     "cgpt_lower_confidence_bound": (_D, [_I64, _I64, _D]),
     "cgpt_binom_test": (_D, [_I64, _I64, _D]),
@@ -96,6 +101,13 @@ def lib():
             fn.argtypes = args
         _lib = L
     return _lib
+
+
+def noise_law(law):
+    """"gaussian" | "uniform" -> CGPT_NOISE_* (ValueError for anything else)."""
+    if law not in NOISE_LAWS:
+        raise ValueError(f"unknown noise law {law!r}: expected one of {sorted(NOISE_LAWS)}")
+    return NOISE_LAWS[law]
 
 
 def check(status):

@@ -7,7 +7,7 @@ are build-side.  Per (image, label): smoothed prediction of the clean image, RGF
 (adversarial prediction == target), the flip rate and the throughput.
 
     run: {agent: image_text_attack_eval, output_dir: ..., seed: 0,
-          smoothing: {sigma: 0.5, n: 100, alpha: 0.001, batch_size: 100, num_classes: 1000},
+          smoothing: {sigma: 0.5, n: 100, alpha: 0.001, batch_size: 100, num_classes: 1000, noise: gaussian},
           attack: {steps: 8, num_dirs: 1, delta: 0.5, lr: 0.05, eps: 0.25, seed: 1234, targeted: true}}
 """
 import json
@@ -36,7 +36,7 @@ class MiniGPT4AttackEvalAgent(BaseAgent):
         clf = self.classifier or build_classifier(cfg.get("model", {}), sm["num_classes"], sm["batch_size"], local)
         self._model, self._device = clf, getattr(clf, "device", None)
         K = sm["num_classes"]
-        smooth = Smooth(clf, K, sm["sigma"], seed=int(cfg["run"].get("seed", 0)))
+        smooth = Smooth(clf, K, sm["sigma"], seed=int(cfg["run"].get("seed", 0)), noise=sm.get("noise", "gaussian"))
         attack = RGFAttack(smooth, steps=int(at.get("steps", 8)), num_dirs=int(at.get("num_dirs", 1)), delta=float(at.get("delta", 0.5)),
                            lr=float(at.get("lr", 0.05)), eps=float(at.get("eps", 0.25)), dir_seed=int(at.get("seed", 1234)))
         targeted = bool(at.get("targeted", True))

@@ -7,6 +7,7 @@ log one line per sample (idx, label, predict, radius, correct, time -- the forma
 Config (a plain dict or any mapping; the reference's YAMLs define no smoothing keys, so these are build-side):
     run:   {agent: image_text_certify, output_dir: ..., seed: 0,
             smoothing: {sigma: 0.5, n0: 100, n: 100, alpha: 0.001, batch_size: 100, num_classes: 1000, radii: [0.25, 0.5, 1.0],
+                        noise: gaussian,          # uniform: x + sigma * U[0,1) (sigma = noise_level), L1 radii
                         images_per_pass: 1,       # > 1: Smooth.certify_many (multi-GPU throughput mode)
                         shard: samples}}          # images: Smooth.certify_images / predict_images -- every rank takes whole images
             #                                       (all their draws) of each group of images_per_pass x world; no vote all-reduce
@@ -236,7 +237,7 @@ class MiniGPT4CertifyAgent(BaseAgent, CertifyLoop):
         # a generating classifier's "other" bucket (answers outside the vocabulary) is not a class of the certificate
         label_map = getattr(clf, "label_map", None)
         smooth = Smooth(clf, sm["num_classes"], sm["sigma"], seed=int(cfg["run"].get("seed", 0)),
-                        non_certifiable=(label_map.other_id,) if label_map is not None else ())
+                        non_certifiable=(label_map.other_id,) if label_map is not None else (), noise=sm.get("noise", "gaussian"))
         data = self.dataset
         if data is None:
             d = cfg.get("data", {})
@@ -249,6 +250,8 @@ class MiniGPT4CertifyAgent(BaseAgent, CertifyLoop):
             log = os.path.join(out_dir, f"{self.mode}.tsv")
         self.certify_dataset(sm, data, smooth, log, mode=self.mode)
         self.result = self.summary(tuple(sm.get("radii", (0.0, 0.25, 0.5, 1.0))))
+        if smooth.norm != "l2":                            # the radii (and certified_acc@r) are L1 radii
+            self.result["norm"] = smooth.norm
         if log:
             with open(os.path.join(out_dir, f"{self.mode}_summary.json"), "w") as f:
                 json.dump(self.result, f)

@@ -23,7 +23,10 @@ def _stream_ptr():
 
 class HipClassifier:
     """mode: "vit_head" (EVA-ViT-G + ln_vision(CLS) + Linear head; BASELINE config 2) or
-    "encode_img" (ViT + ln_vision + Q-Former + llama_proj + head on the mean query token)."""
+    "encode_img" (ViT + ln_vision + Q-Former + llama_proj + head on the mean query token).
+    Every noisy method takes `law="gaussian"` (x + sigma * N(0,1)) or `law="uniform"` (x + sigma * U[0,1), sigma = the noise level)."""
+
+    noise_laws = ("gaussian", "uniform")
 
     def __init__(self, mode="vit_head", num_classes=1000, max_batch=100, device=0, vit_ln_eps=1e-6,
                  ln_vision_eps=1e-5, qf_ln_eps=1e-12, **dims):
@@ -102,6 +105,10 @@ class HipClassifier:
         return self
 
     # ---- forward
+    def _law(self, law):
+        """Set the handle's noise law for the ABI call that follows (a handle may be shared by Smooth objects of both laws)."""
+        _lib.check(self._L.cgpt_set_noise_law(self._h, _lib.noise_law(law)))
+
     def _check_x(self, x, batched):
         if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32):
             raise TypeError("expected a float32 CUDA(HIP) tensor")
@@ -121,32 +128,34 @@ class HipClassifier:
                                              C.c_void_p(out[lo:hi].data_ptr()), _stream_ptr()))
         return out
 
-    def sample_counts(self, x, first_sample, num, batch_size, sigma, seed, counts=None):
+    def sample_counts(self, x, first_sample, num, batch_size, sigma, seed, counts=None, law="gaussian"):
         """The `_sample_noise` engine (smoothing.py:81-99) for samples first_sample..first_sample+num-1.
         Returns (and accumulates into) an int64 device tensor [num_classes]; no host sync."""
         x = self._check_x(x, False)
         if counts is None:
             counts = torch.zeros(self.num_classes, dtype=torch.int64, device=x.device)
         if num > 0:
+            self._law(law)
             _lib.check(self._L.cgpt_sample_counts(self._h, C.c_void_p(x.data_ptr()), first_sample, num,
                                                   min(batch_size, self.max_batch), sigma, seed,
                                                   C.c_void_p(counts.data_ptr()), _stream_ptr()))
         return counts
 
-    def sample_counts_pair(self, x, first_a, num_a, first_b, num_b, batch_size, sigma, seed):
+    def sample_counts_pair(self, x, first_a, num_a, first_b, num_b, batch_size, sigma, seed, law="gaussian"):
         """Selection + estimation draws of one `certify` in a single device pass (cgpt_sample_counts2).
         Returns an int64 device tensor [2, num_classes]: row 0 = votes of samples [first_a, first_a+num_a),
         row 1 = votes of [first_b, first_b+num_b).  Identical to two sample_counts calls."""
         x = self._check_x(x, False)
         counts = torch.zeros((2, self.num_classes), dtype=torch.int64, device=x.device)
         if num_a + num_b > 0:
+            self._law(law)
             _lib.check(self._L.cgpt_sample_counts2(self._h, C.c_void_p(x.data_ptr()), first_a, num_a,
                                                    C.c_void_p(counts[0].data_ptr()), first_b, num_b,
                                                    C.c_void_p(counts[1].data_ptr()), min(batch_size, self.max_batch), sigma,
                                                    seed, _stream_ptr()))
         return counts
 
-    def sample_counts_images(self, xs, first_a, num_a, first_b, num_b, image_stride, sigma, seed):
+    def sample_counts_images(self, xs, first_a, num_a, first_b, num_b, image_stride, sigma, seed, law="gaussian"):
         """The pair pass for several images at once (cgpt_sample_counts_images): image i draws samples
         first_a + i*image_stride + [0,num_a) and first_b + i*image_stride + [0,num_b).  Returns int64 [G, 2, num_classes];
         identical to G sample_counts_pair calls, but the rows of all images are cut into classifier batches of max_batch rows
@@ -156,6 +165,7 @@ class HipClassifier:
         counts = torch.zeros((G, 2, self.num_classes), dtype=torch.int64, device=xs.device)
         if num_a + num_b <= 0 or G == 0:
             return counts
+        self._law(law)
         _lib.check(self._L.cgpt_sample_counts_images(self._h, C.c_void_p(xs.data_ptr()), G, first_a, num_a, first_b, num_b,
                                                      image_stride, C.c_void_p(counts.data_ptr()), sigma, seed, _stream_ptr()))
         return counts
@@ -169,19 +179,21 @@ class HipClassifier:
         _lib.check(self._L.cgpt_encode_img(self._h, C.c_void_p(images.data_ptr()), B, C.c_void_p(out.data_ptr()), _stream_ptr()))
         return out, torch.ones(out.shape[:-1], dtype=torch.long, device=images.device)
 
-    def encode_img_noisy(self, x, first_sample, num, sigma, seed):
+    def encode_img_noisy(self, x, first_sample, num, sigma, seed, law="gaussian"):
         """encode_img(x + sigma * eps_s) for the samples s = first_sample .. first_sample+num-1 of the noise stream, the noise
         fused into the patch-embed operand (cgpt_encode_img_noisy) -> inputs_llama [num, queries, proj_dim] float32."""
         x = self._check_x(x, False)
         out = torch.empty((num, self.cfg["qf_queries"], self.cfg["proj_dim"]), dtype=torch.float32, device=x.device)
         if num > 0:
+            self._law(law)
             _lib.check(self._L.cgpt_encode_img_noisy(self._h, C.c_void_p(x.data_ptr()), first_sample, num, sigma, seed,
                                                      C.c_void_p(out.data_ptr()), _stream_ptr()))
         return out
 
-    def forward_logits(self, x, first_sample, num, sigma, seed):
+    def forward_logits(self, x, first_sample, num, sigma, seed, law="gaussian"):
         x = self._check_x(x, False)
         out = torch.empty((num, self.num_classes), dtype=torch.float32, device=x.device)
+        self._law(law)
         _lib.check(self._L.cgpt_forward_logits(self._h, C.c_void_p(x.data_ptr()), first_sample, num, sigma, seed,
                                                C.c_void_p(out.data_ptr()), _stream_ptr()))
         return out
@@ -237,13 +249,15 @@ def interpolate_pos_embed(pos_embed, num_patches):
     return torch.cat((pe[:, :extra], tok), dim=1).numpy()
 
 
-def noise_batch(x, first_sample, num, sigma, seed):
-    """x[3,H,W] -> [num,3,H,W] noisy copies (smoothing.py:95-96) from the counter-based stream."""
+def noise_batch(x, first_sample, num, sigma, seed, law="gaussian"):
+    """x[3,H,W] -> [num,3,H,W] noisy copies (smoothing.py:95-96) from the counter-based stream: x + sigma * N(0,1), or
+    x + sigma * U[0,1) with law="uniform" (the fine-tuning noise, sigma = noise_level)."""
     L = _lib.lib()
+    code = _lib.noise_law(law)
     x = x.contiguous()
     out = torch.empty((num,) + tuple(x.shape), dtype=torch.float32, device=x.device)
-    _lib.check(L.cgpt_noise_batch(C.c_void_p(x.data_ptr()), x.numel(), first_sample, num, sigma, seed,
-                                  C.c_void_p(out.data_ptr()), _stream_ptr()))
+    _lib.check(L.cgpt_noise_batch_law(C.c_void_p(x.data_ptr()), x.numel(), first_sample, num, sigma, code, seed,
+                                      C.c_void_p(out.data_ptr()), _stream_ptr()))
     return out
 
 

@@ -1,4 +1,4 @@
-// elementwise.hip -- the HBM-bound kernels of the hot path: Gaussian perturbation fused with the patch-embed
+// elementwise.hip -- the HBM-bound kernels of the hot path: Gaussian / uniform perturbation fused with the patch-embed
 // im2col, LayerNorm, CLS/pos rows, query-token broadcast, mean pool, argmax + vote histogram, weight fills/casts.
 //
 // Reference ops replaced: smoothing.py:95-98,101-105 (repeat + randn*sigma; argmax(1); _count_arr),
@@ -194,11 +194,13 @@ __global__ __launch_bounds__(256) void add_delta_kernel(float* __restrict__ x, i
 // patch row of A (3*ps*ps contiguous halfs = 1176 B at ps = 14) then leaves in 8-byte vector stores, one row after the other
 // (the direct form wrote 2-byte stores scattered over img/ps rows per pixel group).  The noise of pixel group `grp` depends
 // only on (seed, sample, grp), so the values are the ones the direct form produced.
-template <bool NOISE>
+// LAW: NOISE_NONE (plain im2col), NOISE_GAUSSIAN (x + sigma * z) or NOISE_UNIFORM (x + sigma * u, u in [0,1); philox.h).
+template <int LAW>
 __global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ src, int img, int ps,
                                                      int64_t first_sample, int na, int64_t first_b, int nb, float sigma,
                                                      uint64_t seed, half_t* __restrict__ A, int64_t lda, int per,
                                                      int64_t img_stride, int64_t row0) {
+    constexpr bool NOISE = LAW != NOISE_NONE;
     extern __shared__ __attribute__((aligned(16))) half_t patch_lds[];   // [pw][kp]
     const int pw = img / ps, kp = 3 * ps * ps;
     const int b = blockIdx.x / pw, py = blockIdx.x - b * pw;
@@ -213,8 +215,8 @@ __global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ s
         const int iy = r / xg_per_row, x0 = (r - iy * xg_per_row) << 2;
         const int e = (c * img + py * ps + iy) * img + x0;                // element index in the image; e/4 = noise group
         float4 px = *reinterpret_cast<const float4*>(image + e);
-        if (NOISE) {
-            const float4 z = normal4(seed, (uint64_t)sample, (uint32_t)(e >> 2), 0u);
+        if constexpr (NOISE) {
+            const float4 z = noise4<LAW>(seed, (uint64_t)sample, (uint32_t)(e >> 2), 0u);
             // explicit fma: the fused path and cgpt_noise_batch must round identically (bit-identical votes)
             px.x = __fmaf_rn(sigma, z.x, px.x); px.y = __fmaf_rn(sigma, z.y, px.y);
             px.z = __fmaf_rn(sigma, z.z, px.z); px.w = __fmaf_rn(sigma, z.w, px.w);
@@ -248,6 +250,8 @@ __global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ s
     }
 }
 
+// out[b] = x + sigma * draw under LAW (NOISE_GAUSSIAN or NOISE_UNIFORM), with the fused path's single fma rounding.
+template <int LAW>
 __global__ __launch_bounds__(256) void noise_batch_kernel(const float* __restrict__ x, int64_t chw,
                                                           int64_t first_sample, int64_t num, float sigma,
                                                           uint64_t seed, float* __restrict__ out) {
@@ -255,7 +259,7 @@ __global__ __launch_bounds__(256) void noise_batch_kernel(const float* __restric
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= groups * num) return;
     const int64_t b = gid / groups, grp = gid - b * groups;
-    const float4 z = normal4(seed, (uint64_t)(first_sample + b), (uint32_t)grp, 0u);
+    const float4 z = noise4<LAW>(seed, (uint64_t)(first_sample + b), (uint32_t)grp, 0u);
     const float zz[4] = {z.x, z.y, z.z, z.w};
     const int64_t e = grp * 4;
     if (e + 3 < chw && (chw & 3) == 0) {
@@ -366,11 +370,11 @@ __global__ __launch_bounds__(256) void vote_kernel(const float* __restrict__ log
 // ------------------------------------------------------------------- device-side finalisation of certify / predict
 // One wave.  Smooth.certify lines 46-56 (smoothing.py): cAHat = first maximal index of the selection histogram
 // (64 lanes scan K/64 classes each, then a 6-step xor-shuffle butterfly keeps (larger count, then smaller index)),
-// nA = estimation[cAHat], Clopper-Pearson lower bound and sigma * Phi^-1 in float64 by lane 0 (stats.h, the same
-// code the host path runs).  Smooth.predict lines 73-79: top-2 counts by two butterflies, two-sided binomial test.
+// nA = estimation[cAHat], Clopper-Pearson lower bound and the radius of the noise law (stats.h radius(): sigma * Phi^-1 or
+// sigma * (p - 1/2)) in float64 by lane 0 (the same code the host path runs).  Smooth.predict lines 73-79: top-2 counts by two butterflies, two-sided binomial test.
 // out[0] = label (as double), out[1] = radius (certify) or p-value (predict).
 __global__ __launch_bounds__(64) void finalize_kernel(const long long* __restrict__ csel, const long long* __restrict__ cest,
-                                                      int K, long long n, double alpha, double sigma, int predict,
+                                                      int K, long long n, double alpha, double sigma, int law, int predict,
                                                       double* __restrict__ out) {
     const int lane = threadIdx.x;
     auto wave_argmax = [&](const long long* c, int skip) {
@@ -395,7 +399,7 @@ __global__ __launch_bounds__(64) void finalize_kernel(const long long* __restric
             const long long nA = cest[cAHat];
             const double pABar = cgpt_stats::cp_lower_bound(nA, n, alpha);
             if (pABar < 0.5) { out[0] = -1.0; out[1] = 0.0; }
-            else { out[0] = (double)cAHat; out[1] = sigma * cgpt_stats::norm_ppf(pABar); }
+            else { out[0] = (double)cAHat; out[1] = cgpt_stats::radius(law, pABar, sigma); }
         }
     } else {
         const int i1 = wave_argmax(cest, -1);
@@ -493,12 +497,13 @@ generic:
 
 hipError_t launch_noise_im2col(const float* x, int img, int ps, int64_t first_sample, int na, int64_t first_b, int nb,
                                float sigma, uint64_t seed, half_t* A, int64_t lda, hipStream_t stream, int per,
-                               int64_t img_stride, int64_t row0) {
+                               int64_t img_stride, int64_t row0, int law) {
     if (nb <= 0) return hipSuccess;
-    if ((img & 3) || (img % ps)) return hipErrorInvalidValue;
+    if ((img & 3) || (img % ps) || (law != NOISE_GAUSSIAN && law != NOISE_UNIFORM)) return hipErrorInvalidValue;
     const int pw = img / ps;
-    hipLaunchKernelGGL(im2col_kernel<true>, dim3((unsigned)(nb * pw)), dim3(256), (size_t)pw * 3 * ps * ps * sizeof(half_t), stream, x,
-                       img, ps, first_sample, na, first_b, nb, sigma, seed, A, lda, per, img_stride, row0);
+    hipLaunchKernelGGL(law == NOISE_UNIFORM ? im2col_kernel<NOISE_UNIFORM> : im2col_kernel<NOISE_GAUSSIAN>, dim3((unsigned)(nb * pw)),
+                       dim3(256), (size_t)pw * 3 * ps * ps * sizeof(half_t), stream, x, img, ps, first_sample, na, first_b, nb, sigma,
+                       seed, A, lda, per, img_stride, row0);
     return hipGetLastError();
 }
 
@@ -506,17 +511,18 @@ hipError_t launch_im2col(const float* images, int img, int ps, int nb, half_t* A
     if (nb <= 0) return hipSuccess;
     if ((img & 3) || (img % ps)) return hipErrorInvalidValue;
     const int pw = img / ps;
-    hipLaunchKernelGGL(im2col_kernel<false>, dim3((unsigned)(nb * pw)), dim3(256), (size_t)pw * 3 * ps * ps * sizeof(half_t), stream,
+    hipLaunchKernelGGL(im2col_kernel<NOISE_NONE>, dim3((unsigned)(nb * pw)), dim3(256), (size_t)pw * 3 * ps * ps * sizeof(half_t), stream,
                        images, img, ps, (int64_t)0, nb, (int64_t)0, nb, 0.0f, (uint64_t)0, A, lda, 0, (int64_t)0, (int64_t)0);
     return hipGetLastError();
 }
 
 hipError_t launch_noise_batch(const float* x, int64_t chw, int64_t first_sample, int64_t num, float sigma,
-                              uint64_t seed, float* out, hipStream_t stream) {
+                              uint64_t seed, float* out, hipStream_t stream, int law) {
+    if (law != NOISE_GAUSSIAN && law != NOISE_UNIFORM) return hipErrorInvalidValue;
     if (num <= 0) return hipSuccess;
     const int64_t n = ((chw + 3) / 4) * num;
-    hipLaunchKernelGGL(noise_batch_kernel, dim3(blocks_for(n)), dim3(256), 0, stream, x, chw, first_sample, num, sigma,
-                       seed, out);
+    hipLaunchKernelGGL(law == NOISE_UNIFORM ? noise_batch_kernel<NOISE_UNIFORM> : noise_batch_kernel<NOISE_GAUSSIAN>, dim3(blocks_for(n)),
+                       dim3(256), 0, stream, x, chw, first_sample, num, sigma, seed, out);
     return hipGetLastError();
 }
 
@@ -560,9 +566,9 @@ hipError_t launch_vote(const float* logits, int64_t ld, int64_t num, int K, int6
 }
 
 hipError_t launch_finalize(const int64_t* csel, const int64_t* cest, int K, int64_t n, double alpha, double sigma, int predict,
-                           double* out, hipStream_t stream) {
+                           double* out, hipStream_t stream, int law) {
     hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(64), 0, stream, reinterpret_cast<const long long*>(csel),
-                       reinterpret_cast<const long long*>(cest), K, (long long)n, alpha, sigma, predict, out);
+                       reinterpret_cast<const long long*>(cest), K, (long long)n, alpha, sigma, law, predict, out);
     return hipGetLastError();
 }
 

@@ -77,14 +77,16 @@ hipError_t launch_add_delta(float* x, int64_t ldx, const half_t* delta, int64_t 
 // Batch row b carries sample first_sample + b for b < na and first_b + (b - na) otherwise (two index ranges per batch).
 // per > 0: several clean images x[i] in one batch, image-major, `per` rows each (na of the first range, per - na of the
 // second), both ranges shifted by i * img_stride sample indices for image i.
+// law: NOISE_GAUSSIAN (eps ~ N(0,1)) or NOISE_UNIFORM (eps ~ U[0,1), philox.h); anything else is hipErrorInvalidValue.
 hipError_t launch_noise_im2col(const float* x, int img, int ps, int64_t first_sample, int na, int64_t first_b, int nb,
                                float sigma, uint64_t seed, half_t* A, int64_t lda, hipStream_t stream, int per = 0,
-                               int64_t img_stride = 0, int64_t row0 = 0);   // row0: sequence row of batch row 0 (per > 0)
+                               int64_t img_stride = 0, int64_t row0 = 0,    // row0: sequence row of batch row 0 (per > 0)
+                               int law = 0);
 // Same im2col for caller-supplied images [nb,3,img,img] (no noise).
 hipError_t launch_im2col(const float* images, int img, int ps, int nb, half_t* A, int64_t lda, hipStream_t stream);
-// out[b, :] = x + sigma * eps_{first_sample + b}   (fp32 images; handle-free C-ABI cgpt_noise_batch)
+// out[b, :] = x + sigma * eps_{first_sample + b}   (fp32 images; handle-free C-ABI cgpt_noise_batch_law; law as above)
 hipError_t launch_noise_batch(const float* x, int64_t chw, int64_t first_sample, int64_t num, float sigma,
-                              uint64_t seed, float* out, hipStream_t stream);
+                              uint64_t seed, float* out, hipStream_t stream, int law = 0);
 // RGF attack step (build-side rule, see elementwise.hip): out = clamp(x_adv + lr*sign(sum_i coeffs[i]*u_{first_dir+i}), x_clean +- eps);
 // coeffs is a HOST array of q <= CGPT_RGF_MAX_DIRS floats.
 #define CGPT_RGF_MAX_DIRS 32
@@ -105,9 +107,9 @@ hipError_t launch_mean_rows(const float* src, int64_t lds, int rows, int D, int 
 hipError_t launch_vote(const float* logits, int64_t ld, int64_t num, int K, int64_t* counts, int64_t na, int64_t* counts_b,
                        hipStream_t stream, int per = 0, int64_t row0 = 0);
 // Smooth.certify lines 46-56 (predict = 0) or Smooth.predict lines 73-79 (predict = 1) on device histograms; one wave.
-// out[0] = label, out[1] = radius | p-value (float64).
+// out[0] = label, out[1] = radius | p-value (float64); the radius is stats.h radius(law, pABar, sigma).
 hipError_t launch_finalize(const int64_t* csel, const int64_t* cest, int K, int64_t n, double alpha, double sigma, int predict,
-                           double* out, hipStream_t stream);
+                           double* out, hipStream_t stream, int law = 0);
 // Fill a tensor from the counter-based normal stream: dst = mean + std * z (fp16 or fp32 destination, 2-D with ld).
 hipError_t launch_fill_normal(void* dst, int is_f16, int64_t rows, int64_t cols, int64_t ld, float mean, float std,
                               uint64_t seed, uint64_t tensor_id, hipStream_t stream);

@@ -94,6 +94,7 @@ struct cgpt_model {
     std::vector<hipEvent_t> event_pool;      // timing-only events (hipEventDisableSystemFence), reused across profile_read(0) drains
     unsigned long long* clk_dev = nullptr;   // [8][2]: per GEMM kind, shader cycles and 100-MHz ticks summed over workgroups (cgpt_profile_clock)
     std::vector<int32_t> batch_log;          // samples of every classifier forward while profiling is on (cgpt_profile_batches)
+    int32_t noise_law = CGPT_NOISE_GAUSSIAN; // law of every later noisy forward (cgpt_set_noise_law), read at enqueue time
 };
 
 namespace {
@@ -342,7 +343,8 @@ cgpt_status forward(cgpt_model* m, const float* src, bool noise, int64_t first_s
     m->pending_delta = false;
     if (m->profile && m->batch_log.size() < (1u << 20)) m->batch_log.push_back(nb);
     // K1 + im2col: smoothing.py:95-96 fused into the patch-embed operand (eva_vit.py:202,209)
-    if (noise) HIPCHK(launch_noise_im2col(src, c.img_size, c.patch_size, first_sample, na, first_b, nb, sigma, seed, m->Apatch, m->Kpatch_p, st, per, img_stride, row0));
+    if (noise) HIPCHK(launch_noise_im2col(src, c.img_size, c.patch_size, first_sample, na, first_b, nb, sigma, seed, m->Apatch, m->Kpatch_p, st, per, img_stride, row0,
+                                          m->noise_law));
     else HIPCHK(launch_im2col(src, c.img_size, c.patch_size, nb, m->Apatch, m->Kpatch_p, st));
     // patch-embed GEMM + bias + pos_embed, scattered to token rows 1..P; CLS row = cls + pos[0]  (eva_vit.py:333-340)
     CGCHK(gemm(m, EPI_PATCH, m->Apatch, m->Kpatch_p, m->Wpatch, m->Kpatch_p, m->bpatch, m->resid, D, m->pos, D, nb * P, D,
@@ -712,10 +714,25 @@ cgpt_status cgpt_get_activation(cgpt_handle h, const char* what, float* out_dev,
     return CGPT_OK;
 }
 
+static bool valid_law(int32_t law) { return law == CGPT_NOISE_GAUSSIAN || law == CGPT_NOISE_UNIFORM; }
+
+cgpt_status cgpt_set_noise_law(cgpt_handle h, int32_t law) {
+    if (!valid_law(law)) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_set_noise_law: law must be CGPT_NOISE_GAUSSIAN or CGPT_NOISE_UNIFORM");
+    if (!h) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_set_noise_law: null handle");
+    h->noise_law = law;
+    return CGPT_OK;
+}
+
 cgpt_status cgpt_noise_batch(const float* x_dev, int64_t chw, int64_t first_sample, int64_t num, float sigma,
                              uint64_t noise_seed, float* out_dev, void* stream) {
+    return cgpt_noise_batch_law(x_dev, chw, first_sample, num, sigma, CGPT_NOISE_GAUSSIAN, noise_seed, out_dev, stream);
+}
+
+cgpt_status cgpt_noise_batch_law(const float* x_dev, int64_t chw, int64_t first_sample, int64_t num, float scale, int32_t law,
+                                 uint64_t noise_seed, float* out_dev, void* stream) {
+    if (!valid_law(law)) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_noise_batch_law: law must be CGPT_NOISE_GAUSSIAN or CGPT_NOISE_UNIFORM");
     if (!x_dev || !out_dev || chw < 1 || num < 0) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_noise_batch: bad argument");
-    HIPCHK(launch_noise_batch(x_dev, chw, first_sample, num, sigma, noise_seed, out_dev, (hipStream_t)stream));
+    HIPCHK(launch_noise_batch(x_dev, chw, first_sample, num, scale, noise_seed, out_dev, (hipStream_t)stream, law));
     return CGPT_OK;
 }
 
@@ -785,9 +802,16 @@ cgpt_status cgpt_allreduce_counts(void* rccl_comm, int64_t* counts_dev, int64_t 
 
 cgpt_status cgpt_certify_device(const int64_t* counts_selection_dev, const int64_t* counts_estimation_dev, int32_t num_classes,
                                 int64_t n, double alpha, double sigma, double* out2_dev, void* stream) {
+    return cgpt_certify_device_law(counts_selection_dev, counts_estimation_dev, num_classes, n, alpha, sigma, CGPT_NOISE_GAUSSIAN,
+                                   out2_dev, stream);
+}
+
+cgpt_status cgpt_certify_device_law(const int64_t* counts_selection_dev, const int64_t* counts_estimation_dev, int32_t num_classes,
+                                    int64_t n, double alpha, double scale, int32_t law, double* out2_dev, void* stream) {
+    if (!valid_law(law)) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_certify_device_law: law must be CGPT_NOISE_GAUSSIAN or CGPT_NOISE_UNIFORM");
     if (!counts_selection_dev || !counts_estimation_dev || !out2_dev || num_classes < 1 || n < 1 || !(alpha > 0.0 && alpha < 1.0))
         return cgpt_fail(CGPT_ERR_INVALID, "cgpt_certify_device: bad argument");
-    HIPCHK(launch_finalize(counts_selection_dev, counts_estimation_dev, num_classes, n, alpha, sigma, 0, out2_dev, (hipStream_t)stream));
+    HIPCHK(launch_finalize(counts_selection_dev, counts_estimation_dev, num_classes, n, alpha, scale, 0, out2_dev, (hipStream_t)stream, law));
     return CGPT_OK;
 }
 

@@ -41,4 +41,24 @@ __device__ inline float4 normal4(uint64_t seed, uint64_t stream, uint32_t g, uin
     return make_float4(ra * ca, ra * sa, rb * cb, rb * sb);
 }
 
+// 4 uniforms in [0, 1) from the same Philox block: element e takes word e % 4, u = (word >> 8) * 2^-24 (24 bits, exact in
+// fp32).  The uniform law of the reference's fine-tuning noise, `image + torch.rand_like(image) * noise_level`
+// (agents/minigpt4_finetune_agent.py:142-147), is x + level * u.
+__device__ inline float4 uniform4(uint64_t seed, uint64_t stream, uint32_t g, uint32_t hi_word) {
+    const u32x4 r = philox4x32_10(g, hi_word, (uint32_t)stream, (uint32_t)(stream >> 32),
+                                  (uint32_t)seed, (uint32_t)(seed >> 32));
+    const float k = 5.9604644775390625e-08f;  // 2^-24
+    return make_float4((float)(r.x >> 8) * k, (float)(r.y >> 8) * k, (float)(r.z >> 8) * k, (float)(r.w >> 8) * k);
+}
+
+// Noise law of a noisy kernel instantiation; GAUSSIAN and UNIFORM carry the values of CGPT_NOISE_* (include/cgpt.h).
+enum NoiseLaw { NOISE_NONE = -1, NOISE_GAUSSIAN = 0, NOISE_UNIFORM = 1 };
+
+// The 4 unit draws of element group g under LAW (GAUSSIAN or UNIFORM); the caller adds scale * draw.
+template <int LAW>
+__device__ inline float4 noise4(uint64_t seed, uint64_t stream, uint32_t g, uint32_t hi_word) {
+    if constexpr (LAW == NOISE_UNIFORM) return uniform4(seed, stream, g, hi_word);
+    else return normal4(seed, stream, g, hi_word);
+}
+
 }  // namespace cgpt

@@ -169,16 +169,24 @@ CGPT_HD inline double norm_ppf(double p) {
     return upper ? -x : x;
 }
 
+// Certified radius of a smoothed classifier whose top class has probability >= pABar >= 1/2, by noise law (CGPT_NOISE_*):
+//   0 Gaussian, scale = sigma:     L2 radius sigma * Phi^-1(pABar)                      (smoothing.py:55)
+//   1 uniform on [x, x + scale)^d: L1 radius scale * (pABar - 1/2)   (TV(mu_x, mu_{x+delta}) <= |delta|_1 / scale)
+CGPT_HD inline double radius(int law, double pABar, double scale) {
+    if (law == 1) return scale * (pABar - 0.5);
+    return scale * norm_ppf(pABar);
+}
+
 // Smooth.certify, smoothing.py:46-56, given the two histograms.
 CGPT_HD inline void certify_from_counts(const int64_t* csel, const int64_t* cest, int K, int64_t n, double alpha,
-                                        double sigma, int* label, double* radius) {
+                                        double sigma, int* label, double* radius_out, int law = 0) {
     int cAHat = 0;                                    // ndarray.argmax(): first maximal index
     for (int i = 1; i < K; ++i) if (csel[i] > csel[cAHat]) cAHat = i;
     const int64_t nA = cest[cAHat];
     const double pABar = cp_lower_bound(nA, n, alpha);
-    if (pABar < 0.5) { *label = -1; *radius = 0.0; return; }
+    if (pABar < 0.5) { *label = -1; *radius_out = 0.0; return; }
     *label = cAHat;
-    *radius = sigma * norm_ppf(pABar);
+    *radius_out = radius(law, pABar, sigma);
 }
 
 // Smooth.predict, smoothing.py:73-79, given the histogram.  Ties cannot change the outcome: a first-place

@@ -190,6 +190,8 @@ class MiniGPT4Classifier:
        :param label_map: `AnswerLabelMap` -- frozen when torch.distributed is initialised (see label_adapter.py)
     """
 
+    noise_laws = ("gaussian", "uniform")       # passed through to encoder.encode_img_noisy
+
     def __init__(self, encoder, llama_model, llama_tokenizer, prompt, label_map, max_new_tokens=20, max_batch=None,
                  generate_kwargs=None, decode="hf", prefill_linear="torch"):
         self.encoder = encoder
@@ -482,19 +484,19 @@ class MiniGPT4Classifier:
             out.append(self._logits(self.generate(images[lo:lo + self.max_batch], self.prompt), images.device))
         return torch.cat(out)
 
-    def sample_counts_pair(self, x, first_a, num_a, first_b, num_b, batch_size, sigma, seed):
+    def sample_counts_pair(self, x, first_a, num_a, first_b, num_b, batch_size, sigma, seed, law="gaussian"):
         """Selection + estimation draws of one `certify` (smoothing.py:44,48) in the same classifier batches: [2, num_classes] int64,
         identical to two `sample_counts` calls (a row's answer does not depend on its batch: tested)."""
         counts = torch.zeros((2, self.num_classes), dtype=torch.int64, device=x.device)
         if first_b != first_a + num_a:                                 # not one contiguous index range: two passes
-            self.sample_counts(x, first_a, num_a, batch_size, sigma, seed, counts[0])
-            self.sample_counts(x, first_b, num_b, batch_size, sigma, seed, counts[1])
+            self.sample_counts(x, first_a, num_a, batch_size, sigma, seed, counts[0], law=law)
+            self.sample_counts(x, first_b, num_b, batch_size, sigma, seed, counts[1], law=law)
             return counts
         bs = max(1, min(int(batch_size), self.max_batch))
         total, done, answers = num_a + num_b, 0, []
         while done < total:
             nb = min(bs, total - done)
-            emb = self.encoder.encode_img_noisy(x, first_a + done, nb, float(sigma), int(seed))
+            emb = self._encode_noisy(x, first_a + done, nb, sigma, seed, law)
             batch_answers = self.generate_from_embeds(emb, self.prompt)
             logits = self.label_map.one_hot_logits(batch_answers, x.device)
             na = max(0, min(nb, num_a - done))                         # rows of this batch that belong to the selection range
@@ -508,14 +510,19 @@ class MiniGPT4Classifier:
         return counts
 
     # ---- the `_sample_noise` engine (smoothing.py:81-99): noise fused into encode_img, vote in HIP
-    def sample_counts(self, x, first_sample, num, batch_size, sigma, seed, counts=None):
+    def _encode_noisy(self, x, first, num, sigma, seed, law):
+        # the law keyword reaches the encoder only when it is not the default: Gaussian-only encoders keep working
+        kw = {} if law == "gaussian" else {"law": law}
+        return self.encoder.encode_img_noisy(x, first, num, float(sigma), int(seed), **kw)
+
+    def sample_counts(self, x, first_sample, num, batch_size, sigma, seed, counts=None, law="gaussian"):
         if counts is None:
             counts = torch.zeros(self.num_classes, dtype=torch.int64, device=x.device)
         bs = max(1, min(int(batch_size), self.max_batch))
         done = 0
         while done < num:
             nb = min(bs, num - done)
-            emb = self.encoder.encode_img_noisy(x, first_sample + done, nb, float(sigma), int(seed))
+            emb = self._encode_noisy(x, first_sample + done, nb, sigma, seed, law)
             vote(self._logits(self.generate_from_embeds(emb, self.prompt), x.device), counts)
             done += nb
         return counts

@@ -15,6 +15,8 @@ one step reuse the same smoothing-noise sample indices (common random numbers), 
 the image, not a fresh Monte-Carlo draw.  Directions come from the library's counter-based normal stream under `dir_seed`:
 u_i is exactly what cgpt_noise_batch adds for sample index i, and cgpt_rgf_step regenerates it on the device -- no direction
 is ever stored.  With torch.distributed initialised the n forwards of every evaluation are sharded by Smooth as usual.
+The vote shares are estimated through `smooth`, so they follow its noise law (`Smooth(..., noise="uniform")` included); the
+search directions u_i stay Gaussian under either law.
 """
 import ctypes as C
 
@@ -45,7 +47,8 @@ def rgf_step(x_adv, x_clean, first_dir, coeffs, lr, eps, dir_seed, out=None):
 
 
 class RGFAttack(object):
-    """Query attack on `smooth` (a certifiedgpt_amd.Smooth).  See the module docstring for the rule."""
+    """Query attack on `smooth` (a certifiedgpt_amd.Smooth).  See the module docstring for the rule.  The smoothing noise of every
+    share estimate is `smooth`'s law; the search directions are N(0,1) whatever that law is."""
 
     def __init__(self, smooth, steps: int = 8, num_dirs: int = 1, delta: float = 0.5, lr: float = 0.05, eps: float = 0.25,
                  dir_seed: int = 1234):

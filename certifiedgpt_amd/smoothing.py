@@ -10,7 +10,9 @@ conventions.  Differences, all build-side and documented in DESIGN.md:
     int64 histograms are summed with ONE all-reduce (RCCL over xGMI; gloo in CPU tests); `certify_images` is the other
     partition SURVEY.md 8(e) names: whole images per rank, no vote collective, results exchanged at 16 bytes per image;
   * the statistics (smoothing.py:46-56,73-79,107-117) are float64 host functions of the C-ABI -- no scipy /
-    statsmodels needed at run time.
+    statsmodels needed at run time;
+  * `noise="uniform"` smooths under the reference's fine-tuning noise x + sigma * U[0,1) (sigma = its noise_level,
+    agents/minigpt4_finetune_agent.py:142-147) and certifies the L1 radius sigma * (pA_lower - 1/2).
 There is no CPU fallback: without libcgpt.so import fails, without a GPU the engine cannot be created.
 """
 import ctypes as C
@@ -71,7 +73,7 @@ class Smooth(object):
     ABSTAIN = -1  # smoothing.py:17
 
     def __init__(self, base_classifier, num_classes: int, sigma: float, seed: int = 0, process_group=None,
-                 device_stats: bool = False, non_certifiable=(), force_collective=None):
+                 device_stats: bool = False, non_certifiable=(), force_collective=None, noise: str = "gaussian"):
         """
         :param base_classifier: an engine exposing `sample_counts(x, first_sample, num, batch_size, sigma, seed)`
                (certifiedgpt_amd.HipClassifier), or any callable mapping a [B,C,H,W] CUDA tensor to [B,num_classes]
@@ -90,7 +92,18 @@ class Smooth(object):
                so results do not change): lets a one-GPU box execute the RCCL path -- `dist.all_reduce` of the CUDA int64 histograms
                through backend "nccl" -- that a world of 1 otherwise skips.  Default: the environment variable
                CGPT_FORCE_COLLECTIVE=1, else off.  Ignored when torch.distributed is not initialised.
+        :param noise: the noise law.  "gaussian" (default): x + sigma * N(0,1), certified L2 radius sigma * Phi^-1(pA_lower)
+               (smoothing.py:55).  "uniform": x + sigma * U[0,1) per coordinate, sigma = the reference's noise_level, certified
+               L1 radius sigma * (pA_lower - 1/2).  `predict` is the same test under both laws.  An engine (an object with
+               `sample_counts`) must list the law in its `noise_laws` attribute; a plain callable supports both
         """
+        self._law = _lib.noise_law(noise)                 # ValueError for an unknown law
+        laws = getattr(base_classifier, "noise_laws", ("gaussian",)) if hasattr(base_classifier, "sample_counts") else tuple(_lib.NOISE_LAWS)
+        if noise not in laws:
+            raise ValueError(f"Smooth(noise={noise!r}): the engine {type(base_classifier).__name__} supports noise_laws={tuple(laws)}")
+        self.noise = noise
+        # the law keyword reaches an engine only when it is not the default: duck-typed Gaussian-only engines keep working
+        self._law_kw = {} if noise == "gaussian" else {"law": noise}
         self.base_classifier = base_classifier
         self.num_classes = num_classes
         self.sigma = sigma
@@ -105,6 +118,11 @@ class Smooth(object):
         self._next_sample = 0
         self._lib = _lib.lib()
         self._timing = None                                # see collect_timing()
+
+    @property
+    def norm(self) -> str:
+        """Norm of the certified radius: "l2" under Gaussian noise, "l1" under uniform noise."""
+        return "l1" if self._law == _lib.NOISE_LAWS["uniform"] else "l2"
 
     # ------------------------------------------------------------------ per-rank timing (measurement only)
     def collect_timing(self, on: bool = True):
@@ -163,7 +181,8 @@ class Smooth(object):
 
     # ------------------------------------------------------------------ reference API
     def certify(self, x: torch.tensor, n0: int, n: int, alpha: float, batch_size: int) -> (int, float):
-        """smoothing.py:29-56.  Returns (predicted class, certified L2 radius) or (ABSTAIN, 0.0)."""
+        """smoothing.py:29-56.  Returns (predicted class, certified radius) or (ABSTAIN, 0.0); the radius is in the norm
+        `self.norm` (L2 under Gaussian noise, L1 under uniform noise)."""
         self.base_classifier.eval()
         if hasattr(self.base_classifier, "sample_counts_pair"):
             # the n0 selection draws and the n estimation draws are independent (smoothing.py:44,48): run them in the same
@@ -192,7 +211,7 @@ class Smooth(object):
         lo_b, hi_b = shard_range(n, rank, world, mirrored=True)
         with torch.no_grad():
             counts = self._timed_compute(lambda: self.base_classifier.sample_counts_pair(
-                x, first + lo_a, hi_a - lo_a, first + n0 + lo_b, hi_b - lo_b, batch_size, float(self.sigma), self.seed))
+                x, first + lo_a, hi_a - lo_a, first + n0 + lo_b, hi_b - lo_b, batch_size, float(self.sigma), self.seed, **self._law_kw))
         if self._reduces(world):
             self._all_reduce(counts)
         if self.device_stats and counts.is_cuda:
@@ -218,7 +237,7 @@ class Smooth(object):
         lo_b, hi_b = shard_range(n, rank, world, mirrored=True)
         with torch.no_grad():
             counts = self._timed_compute(lambda: bc.sample_counts_images(xs, first + lo_a, hi_a - lo_a, first + n0 + lo_b, hi_b - lo_b,
-                                                                          n0 + n, float(self.sigma), self.seed))
+                                                                          n0 + n, float(self.sigma), self.seed, **self._law_kw))
         if self._reduces(world):
             self._all_reduce(counts)
         if self._timing is None:
@@ -298,12 +317,12 @@ class Smooth(object):
         bc.eval()
         g = int(xs.shape[0])
         if hasattr(bc, "sample_counts_images") and g > 1:
-            return bc.sample_counts_images(xs, first, n0, first + n0, n, n0 + n, float(self.sigma), self.seed)
+            return bc.sample_counts_images(xs, first, n0, first + n0, n, n0 + n, float(self.sigma), self.seed, **self._law_kw)
         out = []
         for i in range(g):
             f = first + i * (n0 + n)
             if hasattr(bc, "sample_counts_pair"):
-                out.append(bc.sample_counts_pair(xs[i], f, n0, f + n0, n, batch_size, float(self.sigma), self.seed))
+                out.append(bc.sample_counts_pair(xs[i], f, n0, f + n0, n, batch_size, float(self.sigma), self.seed, **self._law_kw))
             else:
                 out.append(torch.stack([self._local_counts(xs[i], f, n0, batch_size), self._local_counts(xs[i], f + n0, n, batch_size)]))
         return torch.stack(out)
@@ -329,7 +348,7 @@ class Smooth(object):
         lo, hi = shard_range(num, rank, world)
         with torch.no_grad():
             counts = self._timed_compute(lambda: bc.sample_counts_images(xs, first + lo, hi - lo, 0, 0, stride, float(self.sigma),
-                                                                          self.seed))[:, 0].contiguous()
+                                                                          self.seed, **self._law_kw))[:, 0].contiguous()
         if self._reduces(world):
             self._all_reduce(counts)
         return counts.cpu().numpy().astype(int)
@@ -383,7 +402,7 @@ class Smooth(object):
     def _local_counts(self, x, first_sample, num, batch_size):
         bc = self.base_classifier
         if hasattr(bc, "sample_counts"):
-            return bc.sample_counts(x, first_sample, num, batch_size, float(self.sigma), self.seed)
+            return bc.sample_counts(x, first_sample, num, batch_size, float(self.sigma), self.seed, **self._law_kw)
         # generic classifier on PyTorch-ROCm: HIP noise -> classifier -> HIP argmax/vote
         from .classifier import noise_batch, vote
         if not (isinstance(x, torch.Tensor) and x.is_cuda):
@@ -392,7 +411,7 @@ class Smooth(object):
         done = 0
         for _ in range(ceil(num / batch_size)):
             this_batch_size = min(batch_size, num - done)
-            batch = noise_batch(x.float(), first_sample + done, this_batch_size, float(self.sigma), self.seed)
+            batch = noise_batch(x.float(), first_sample + done, this_batch_size, float(self.sigma), self.seed, law=self.noise)
             vote(bc(batch), counts)
             done += this_batch_size
         return counts
@@ -400,6 +419,8 @@ class Smooth(object):
     def certify_from_counts(self, counts_selection, counts_estimation, n: int, alpha: float):
         cs = np.ascontiguousarray(counts_selection, dtype=np.int64)
         ce = np.ascontiguousarray(counts_estimation, dtype=np.int64)
+        if self.noise != "gaussian":                       # one image = the G = 1 case of the law-aware table function
+            return self.certify_many_from_counts(np.stack([cs, ce])[None], n, alpha)[0]
         label, radius = C.c_int32(), C.c_double()
         _lib.check(self._lib.cgpt_certify_from_counts(cs.ctypes.data_as(C.c_void_p), ce.ctypes.data_as(C.c_void_p),
                                                       len(cs), int(n), float(alpha), float(self.sigma),
@@ -413,8 +434,8 @@ class Smooth(object):
             raise ValueError("certify_many_from_counts: table must be [G, 2, num_classes]")
         G, K = int(t.shape[0]), int(t.shape[2])
         labels, radii = np.empty(G, dtype=np.int32), np.empty(G, dtype=np.float64)
-        _lib.check(self._lib.cgpt_certify_many_from_counts(t.ctypes.data_as(C.c_void_p), G, K, int(n), float(alpha), float(self.sigma),
-                                                           labels.ctypes.data_as(C.c_void_p), radii.ctypes.data_as(C.c_void_p)))
+        _lib.check(self._lib.cgpt_certify_many_from_counts_law(t.ctypes.data_as(C.c_void_p), G, K, int(n), float(alpha), float(self.sigma),
+                                                               self._law, labels.ctypes.data_as(C.c_void_p), radii.ctypes.data_as(C.c_void_p)))
         return [(int(labels[i]), float(radii[i])) for i in range(G)]
 
     def _finalize_device(self, csel, cest, n, alpha, predict):
@@ -424,8 +445,8 @@ class Smooth(object):
             _lib.check(self._lib.cgpt_predict_device(C.c_void_p(cest.data_ptr()), cest.numel(), float(alpha),
                                                      C.c_void_p(out.data_ptr()), st))
             return int(out[0].item())
-        _lib.check(self._lib.cgpt_certify_device(C.c_void_p(csel.data_ptr()), C.c_void_p(cest.data_ptr()), cest.numel(), int(n),
-                                                 float(alpha), float(self.sigma), C.c_void_p(out.data_ptr()), st))
+        _lib.check(self._lib.cgpt_certify_device_law(C.c_void_p(csel.data_ptr()), C.c_void_p(cest.data_ptr()), cest.numel(), int(n),
+                                                     float(alpha), float(self.sigma), self._law, C.c_void_p(out.data_ptr()), st))
         o = out.cpu()
         return int(o[0].item()), float(o[1].item())
 

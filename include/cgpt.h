@@ -40,6 +40,14 @@ enum {
 
 #define CGPT_ABSTAIN (-1)     /* Smooth.ABSTAIN, smoothing.py:17 */
 
+/* Noise law of the Monte-Carlo draws (cgpt_set_noise_law, cgpt_noise_batch_law) and of the certificate (*_law statistics).
+ * GAUSSIAN: x + sigma * eps, eps ~ N(0,1)^d (smoothing.py:96); certified L2 radius sigma * Phi^-1(pA_lower).
+ * UNIFORM:  x + level * u, u ~ U[0,1)^d per coordinate (the fine-tuning noise `image + torch.rand_like(image) * noise_level`,
+ *           agents/minigpt4_finetune_agent.py:142-147); certified L1 radius level * (pA_lower - 1/2).
+ * Both laws draw from the same counter-based Philox stream, keyed (noise_seed, sample index, element): counts stay invariant
+ * under any batching or sharding.  The `sigma` argument of every noisy entry point is the scale: sigma or level. */
+enum { CGPT_NOISE_GAUSSIAN = 0, CGPT_NOISE_UNIFORM = 1 };
+
 /* What the base classifier computes after the noise is added (smoothing.py:97 `base_classifier(batch + noise)`). */
 enum {
     CGPT_MODE_VIT_HEAD = 0,   /* EVA-ViT-G forward_features (eva_vit.py:332-349) -> ln_vision (base_model.py:281-287)
@@ -108,6 +116,10 @@ const char* cgpt_weight_name(cgpt_handle h, int32_t index);
  * trunc_normal(.02) Linear weights, zero biases, LN (1,0), proj/fc2 / sqrt(2*layer_id); Qformer.py:664-674:
  * normal(0,.02); minigpt4.py:99-102) from a counter-based generator.  There is no checkpoint in the container. */
 cgpt_status cgpt_init_synthetic_weights(cgpt_handle h, uint64_t seed, void* stream);
+/* Noise law (CGPT_NOISE_*) of every later noisy call of the handle: cgpt_sample_counts, cgpt_sample_counts2,
+ * cgpt_sample_counts_images, cgpt_forward_logits and cgpt_encode_img_noisy.  Default CGPT_NOISE_GAUSSIAN; any other value
+ * is CGPT_ERR_INVALID.  The law is read when a call ENQUEUES its kernels: a graph captured under one law keeps that law. */
+cgpt_status cgpt_set_noise_law(cgpt_handle h, int32_t law);
 
 /* ---- the hot loop: Smooth._sample_noise (smoothing.py:81-99) ----
  * For global sample indices s in [first_sample, first_sample + num): draw eps_s ~ N(0,1)^{3xHxW} from the
@@ -163,6 +175,10 @@ cgpt_status cgpt_get_activation(cgpt_handle h, const char* what, float* out_dev,
 /* smoothing.py:95-96: out[b] = x + sigma * eps_{first_sample+b}; out_dev is [num,3,H,W] float32.  Handle-free. */
 cgpt_status cgpt_noise_batch(const float* x_dev, int64_t chw, int64_t first_sample, int64_t num, float sigma,
                              uint64_t noise_seed, float* out_dev, void* stream);
+/* The same under noise law `law` (CGPT_NOISE_*): out[b] = x + scale * eps_{first_sample+b}, rounded exactly as the noisy
+ * classifier calls round it (one fma in fp32).  cgpt_noise_batch is this call with CGPT_NOISE_GAUSSIAN.  Handle-free. */
+cgpt_status cgpt_noise_batch_law(const float* x_dev, int64_t chw, int64_t first_sample, int64_t num, float scale, int32_t law,
+                                 uint64_t noise_seed, float* out_dev, void* stream);
 /* One step of the random-gradient-free black-box attack of BASELINE configs[4] (the reference has no code for it, only prose:
  * README.md:62-64,108-120; the rule is this library's): with u_s the N(0,1) image of sample index s of the noise stream (the
  * direction cgpt_noise_batch(x, s, 1, delta, seed) adds),
@@ -199,6 +215,11 @@ cgpt_status cgpt_certify_from_counts(const int64_t* counts_selection, const int6
  * GPU idles: 3 % of a rank's time at 8 GPUs). */
 cgpt_status cgpt_certify_many_from_counts(const int64_t* counts, int64_t num_images, int32_t num_classes, int64_t n, double alpha,
                                           double sigma, int32_t* labels_out, double* radii_out);
+/* The same under noise law `law` (CGPT_NOISE_*) with noise scale `scale`: the radius is scale * Phi^-1(pA_lower) (L2, Gaussian)
+ * or scale * (pA_lower - 1/2) (L1, uniform); labels and the abstain rule (pA_lower < 1/2) do not depend on the law.  One image is
+ * num_images = 1.  cgpt_certify_from_counts and cgpt_certify_many_from_counts are this function with CGPT_NOISE_GAUSSIAN. */
+cgpt_status cgpt_certify_many_from_counts_law(const int64_t* counts, int64_t num_images, int32_t num_classes, int64_t n, double alpha,
+                                              double scale, int32_t law, int32_t* labels_out, double* radii_out);
 /* Smooth.predict lines 73-79 given the histogram (smoothing.py:72). */
 cgpt_status cgpt_predict_from_counts(const int64_t* counts, int32_t num_classes, double alpha, int32_t* label_out);
 /* The same two decisions computed ON THE DEVICE from device histograms (no histogram copy, no host sync): one wavefront,
@@ -206,6 +227,9 @@ cgpt_status cgpt_predict_from_counts(const int64_t* counts, int32_t num_classes,
  * host functions.  out2_dev[0] = label (-1 = abstain) as a double, out2_dev[1] = radius (certify) or p-value (predict). */
 cgpt_status cgpt_certify_device(const int64_t* counts_selection_dev, const int64_t* counts_estimation_dev, int32_t num_classes,
                                 int64_t n, double alpha, double sigma, double* out2_dev, void* stream);
+/* cgpt_certify_device under noise law `law` (CGPT_NOISE_*), radius as in cgpt_certify_many_from_counts_law. */
+cgpt_status cgpt_certify_device_law(const int64_t* counts_selection_dev, const int64_t* counts_estimation_dev, int32_t num_classes,
+                                    int64_t n, double alpha, double scale, int32_t law, double* out2_dev, void* stream);
 cgpt_status cgpt_predict_device(const int64_t* counts_dev, int32_t num_classes, double alpha, double* out2_dev, void* stream);
 /* Smooth._lower_confidence_bound (smoothing.py:107-117) == statsmodels proportion_confint(NA,N,2*alpha,"beta")[0]. */
 double cgpt_lower_confidence_bound(int64_t NA, int64_t N, double alpha);
