@@ -33,6 +33,15 @@ class Config(C.Structure):
     ]
 
 
+class LlmConfig(C.Structure):
+    """struct cgpt_llm_config (include/cgpt.h) -- field order is ABI."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("device", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
+        ("kv_heads", C.c_int32), ("head_dim", C.c_int32), ("mlp", C.c_int32), ("vocab", C.c_int32), ("rms_eps", C.c_float),
+        ("rope_theta", C.c_float), ("max_batch", C.c_int32), ("max_len", C.c_int32),
+    ]
+
+
 # (name, restype, argtypes) of every symbol include/cgpt.h declares
 _P, _I64, _I32, _F, _D, _U64 = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_double, C.c_uint64
 SIGNATURES = {
@@ -80,6 +89,11 @@ SIGNATURES = {
     "cgpt_linear_f16": (_I32, [_P, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _I32, _P]),
     "cgpt_attention_f16": (_I32, [_P, _I64, _P, _P, _I64, _P, _I64, _I32, _I32, _I32, _I32, _I32, _F, _P]),
     "cgpt_layernorm": (_I32, [_P, _I64, _P, _P, _F, _P, _I64, _P, _I64, _I64, _I32, _P]),
+    "cgpt_llm_create": (_I32, [C.POINTER(LlmConfig), C.POINTER(_P)]),
+    "cgpt_llm_destroy": (_I32, [_P]),
+    "cgpt_llm_load_weight_f16": (_I32, [_P, C.c_char_p, _P, _I64, _P]),
+    "cgpt_llm_step": (_I32, [_P, _P, _I32, _I32, _P, _P, _I64, _P, _P]),
+    "cgpt_llm_greedy": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _P, _I32, _I64, _P, _P, _I64, _P, _P, _P]),
 }
 
 _lib = None

@@ -161,7 +161,7 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
     causal LM on PyTorch-ROCm, loaded BY LOCAL PATH only (base_model.py:181-247 loads `llama_model` the same way; nothing is
     ever fetched), + the answer vocabulary that defines the classes.
         gen_cfg: {llama_model: <local dir>, prompt: "... <ImageHere> ...", answers: [...], max_new_tokens: 20,
-                  decode: "hf" | "graph", prefill_linear: "torch" | "cgpt"}   (decode / prefill_linear: see MiniGPT4Classifier)"""
+                  decode: "hf" | "graph" | "hip", prefill_linear: "torch" | "cgpt"}   (decode / prefill_linear: see MiniGPT4Classifier)"""
     from ..minigpt4 import MiniGPT4Classifier, prepare_texts
     from .label_adapter import AnswerLabelMap
     if llama_model is None:

@@ -1,0 +1,491 @@
+// llm.hip -- the LLaMA token step of MiniGPT-4's greedy decode, and its C-ABI (include/cgpt.h, "LLaMA decode steps").
+//
+// Reference call replaced: every forward after the prefill inside `self.llama_model.generate(...)`
+// (graphs/models/minigpt4/models/minigpt_base.py:418-431, greedy: do_sample=False, num_beams=1), i.e. HF LlamaForCausalLM
+// on one new token per row with a K/V cache.  The prefill stays the model's own forward; its K/V are used in place.
+//
+// One step = embedding lookup, layers x (RMSNorm, fused q/k/v GEMM, rotary + K/V append + one-query attention, o_proj GEMM +
+// residual, RMSNorm, fused gate/up GEMM + SwiGLU, down GEMM + residual), final RMSNorm, lm_head GEMM.  The GEMMs are
+// llm_gemm.hip; the rest is here.  Every kernel rounds where HF's fp16 eager model rounds: what is left between
+// the two is summation order.  Nothing here synchronises, allocates or copies from the host after cgpt_llm_create, so a whole
+// greedy loop can be captured into one graph.
+#include <math.h>
+#include <string.h>
+
+#include <set>
+#include <string>
+#include <vector>
+
+#include "../../include/cgpt.h"
+#include "common_host.h"
+#include "llm.h"
+
+using namespace cgpt;
+
+#define HIPCHK(expr)                                                                                   \
+    do {                                                                                               \
+        hipError_t e_ = (expr);                                                                        \
+        if (e_ != hipSuccess)                                                                          \
+            return cgpt_fail(CGPT_ERR_HIP, std::string(#expr) + " -> " + hipGetErrorString(e_));       \
+    } while (0)
+#define CGCHK(expr)                         \
+    do {                                    \
+        cgpt_status s_ = (expr);            \
+        if (s_ != CGPT_OK) return s_;       \
+    } while (0)
+
+namespace {
+
+typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
+constexpr int HD = 128;                // head size the attention kernel is written for
+constexpr int MAX_ROWS = 256;          // one GEMM row tile
+constexpr int MAX_EOS = 8;
+
+__device__ __forceinline__ float rf16(float v) { return (float)(half_t)v; }
+// fp16(a * b) as a value of its own: without the barrier the compiler contracts fp16(a * b) + c into one v_fma_f16, which skips
+// the product's rounding -- closer to the exact result, but not where HF's eager model rounds (16 % of a rotated key row differed).
+__device__ __forceinline__ float mul_f16(float a, float b) {
+    float r = rf16(a * b);
+    asm volatile("" : "+v"(r));
+    return r;
+}
+
+// h[b, :] = embed[token[b], :].  A token outside the table reads row 0 (never out of bounds).
+__global__ __launch_bounds__(256) void llm_embed_kernel(const long long* __restrict__ tokens, const half_t* __restrict__ table,
+                                                        int vocab, int hidden, half_t* __restrict__ h) {
+    long long t = tokens[blockIdx.x];
+    if (t < 0 || t >= vocab) t = 0;
+    const h16x8* src = reinterpret_cast<const h16x8*>(table + (int64_t)t * hidden);
+    h16x8* dst = reinterpret_cast<h16x8*>(h + (int64_t)blockIdx.x * hidden);
+    for (int i = threadIdx.x; i < hidden / 8; i += 256) dst[i] = src[i];
+}
+
+// LlamaRMSNorm: y = weight * fp16(x * rsqrt(mean(x^2) + eps)), statistics in fp32, both products rounded to fp16.
+// One workgroup per row; the sum runs in a fixed order (per-thread strided, wave butterfly, 4 wave sums in order).
+__global__ __launch_bounds__(256) void llm_rmsnorm_kernel(const half_t* __restrict__ x, const half_t* __restrict__ w, int hidden,
+                                                          float eps, half_t* __restrict__ y) {
+    __shared__ float wsum[4];
+    const half_t* xr = x + (int64_t)blockIdx.x * hidden;
+    half_t* yr = y + (int64_t)blockIdx.x * hidden;
+    float ss = 0.0f;
+    for (int i = threadIdx.x; i < hidden / 8; i += 256) {
+        const h16x8 v = reinterpret_cast<const h16x8*>(xr)[i];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) ss += (float)v[e] * (float)v[e];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = ss;
+    __syncthreads();
+    const float total = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+    const float inv = rsqrtf(total / (float)hidden + eps);
+    for (int i = threadIdx.x; i < hidden / 8; i += 256) {
+        const h16x8 v = reinterpret_cast<const h16x8*>(xr)[i];
+        const h16x8 g = reinterpret_cast<const h16x8*>(w)[i];
+        h16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (half_t)((float)g[e] * rf16((float)v[e] * inv));
+        reinterpret_cast<h16x8*>(yr)[i] = o;
+    }
+}
+
+// cos / sin of the default rotary law: table[pos][0..63] = fp16(cos(pos * inv_freq[i])), [64..127] = fp16(sin(...)),
+// the angle in fp32 as HF's LlamaRotaryEmbedding forms it.
+__global__ __launch_bounds__(64) void llm_rope_table_kernel(const float* __restrict__ inv_freq, half_t* __restrict__ table) {
+    const float a = (float)blockIdx.x * inv_freq[threadIdx.x];
+    table[(int64_t)blockIdx.x * HD + threadIdx.x] = (half_t)cosf(a);
+    table[(int64_t)blockIdx.x * HD + 64 + threadIdx.x] = (half_t)sinf(a);
+}
+
+// Rotary + K/V append + attention of one query, one wavefront per (row, head).
+//   q, k, v  = the head's 128 columns of the fused projection row qkv[b, 0 | hidden | 2 hidden + h * 128 ...]
+//   q', k'   = x * cos + rotate_half(x) * sin at position `pos`, each product and the sum rounded to fp16
+//   K[b, h, pos, :] = k',  V[b, h, pos, :] = v        (the only cache rows written)
+//   out[b, h * 128 ...] = fp16(softmax(q' . K[0..pos] / sqrt(128)) . V[0..pos]),  scores, probabilities and the sum in fp32
+// HBM-bound: a head reads (pos + 1) x 2 x 256 B; a wave instruction covers 4 keys x 256 B in 16-byte lanes.
+__global__ __launch_bounds__(64) void llm_attn_kernel(const half_t* __restrict__ qkv, int hidden, int heads, half_t* Kc, half_t* Vc,
+                                                      int64_t len_stride, const half_t* __restrict__ rope, int pos,
+                                                      half_t* __restrict__ out) {
+    extern __shared__ float asmem[];                   // [128] rotated query, [128 + 128] halfs: the new key and value, [pos + 1] scores
+    float* qs = asmem;
+    half_t* knew = reinterpret_cast<half_t*>(asmem + HD);
+    half_t* vnew = knew + HD;
+    float* sc = asmem + 2 * HD;
+    const int b = blockIdx.x / heads, h = blockIdx.x % heads, lane = threadIdx.x;
+    const half_t* q = qkv + (int64_t)b * 3 * hidden + h * HD;
+    const half_t* k = q + hidden;
+    const half_t* v = k + hidden;
+    half_t* Kh = Kc + (int64_t)(b * heads + h) * len_stride * HD;
+    half_t* Vh = Vc + (int64_t)(b * heads + h) * len_stride * HD;
+
+    {   // lane i owns the rotary pair (i, i + 64)
+        const float c = (float)rope[(int64_t)pos * HD + lane], s = (float)rope[(int64_t)pos * HD + 64 + lane];
+        const float q0 = (float)q[lane], q1 = (float)q[lane + 64], k0 = (float)k[lane], k1 = (float)k[lane + 64];
+        qs[lane] = rf16(mul_f16(q0, c) - mul_f16(q1, s));
+        qs[lane + 64] = rf16(mul_f16(q1, c) + mul_f16(q0, s));
+        const half_t r0 = (half_t)(mul_f16(k0, c) - mul_f16(k1, s)), r1 = (half_t)(mul_f16(k1, c) + mul_f16(k0, s));
+        const half_t v0 = v[lane], v1 = v[lane + 64];
+        Kh[(int64_t)pos * HD + lane] = knew[lane] = r0;
+        Kh[(int64_t)pos * HD + lane + 64] = knew[lane + 64] = r1;
+        Vh[(int64_t)pos * HD + lane] = vnew[lane] = v0;
+        Vh[(int64_t)pos * HD + lane + 64] = vnew[lane + 64] = v1;
+    }
+    __syncthreads();                                   // key `pos` is attended from LDS: the cache row just stored is not read back
+
+    const int n = pos + 1;
+    const int kk = lane >> 4, dc = (lane & 15) * 8;    // key within a group of 4, first of the lane's 8 dims
+    float qr[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) qr[e] = qs[dc + e];
+    const float scale = 0.08838834764831845f;          // 1 / sqrt(128)
+    float mx = -INFINITY;
+    for (int t0 = 0; t0 < n; t0 += 4) {
+        const int t = t0 + kk;
+        float d = 0.0f;
+        if (t < n) {
+            const h16x8 kv = *reinterpret_cast<const h16x8*>(t == pos ? knew + dc : Kh + (int64_t)t * HD + dc);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) d += qr[e] * (float)kv[e];
+        }
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) d += __shfl_xor(d, o);
+        d *= scale;
+        if (t < n) {
+            mx = fmaxf(mx, d);
+            if ((lane & 15) == 0) sc[t] = d;
+        }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16));
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    __syncthreads();
+
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float l = 0.0f;
+    for (int t0 = 0; t0 < n; t0 += 4) {
+        const int t = t0 + kk;
+        if (t < n) {
+            const float p = expf(sc[t] - mx);
+            const h16x8 vv = *reinterpret_cast<const h16x8*>(t == pos ? vnew + dc : Vh + (int64_t)t * HD + dc);
+            l += p;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] += p * (float)vv[e];
+        }
+    }
+    l += __shfl_xor(l, 16);
+    l += __shfl_xor(l, 32);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        acc[e] += __shfl_xor(acc[e], 16);
+        acc[e] += __shfl_xor(acc[e], 32);
+    }
+    if (kk == 0) {
+        h16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (half_t)(acc[e] / l);
+        *reinterpret_cast<h16x8*>(out + (int64_t)b * hidden + h * HD + dc) = o;
+    }
+}
+
+struct EosIds { long long id[MAX_EOS]; int n; };
+
+// Greedy bookkeeping of one step, one workgroup per row (greedy_tokens in minigpt4.py): EOS columns read as -inf while
+// `mask_eos` (the first min_new_tokens steps), first-max arg-max, pad once the row has produced an EOS.
+//   dst != null: the (masked) logits are also written there (row stride ldd); dst may be src.
+//   first != 0:  every row starts unfinished (step 0)
+__global__ __launch_bounds__(256) void llm_select_kernel(const float* src, int64_t lds, float* dst, int64_t ldd, int vocab,
+                                                         int mask_eos, EosIds eos, long long pad, int first, int* __restrict__ unfinished,
+                                                         long long* __restrict__ tokens_out, int64_t ld_tokens,
+                                                         long long* __restrict__ next_tok) {
+    __shared__ float bv[4];
+    __shared__ int bi[4];
+    const int row = blockIdx.x;
+    const float* s = src + (int64_t)row * lds;
+    float* d = dst ? dst + (int64_t)row * ldd : nullptr;
+    float best = -INFINITY;
+    int idx = 0x7fffffff;
+    for (int j = threadIdx.x; j < vocab; j += 256) {
+        float v = s[j];
+        if (mask_eos)
+            for (int e = 0; e < eos.n; ++e)
+                if (eos.id[e] == j) v = -INFINITY;
+        if (d) d[j] = v;
+        if (idx == 0x7fffffff || v > best) { best = v; idx = j; }          // ascending j: the first maximum stays
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o);
+        const int oi = __shfl_xor(idx, o);
+        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
+    }
+    if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = idx; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w)
+            if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
+        int u = first ? 1 : unfinished[row];
+        const long long tok = u ? (long long)idx : pad;
+        for (int e = 0; e < eos.n; ++e)
+            if (tok == eos.id[e]) u = 0;
+        unfinished[row] = u;
+        tokens_out[(int64_t)row * ld_tokens] = tok;
+        next_tok[row] = tok;
+    }
+}
+
+struct Layer {
+    half_t *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wdown = nullptr, *ln1 = nullptr, *ln2 = nullptr;
+};
+
+}  // namespace
+
+struct cgpt_llm {
+    cgpt_llm_config cfg;
+    std::vector<Layer> layers;
+    half_t *embed = nullptr, *norm = nullptr, *lm_head = nullptr, *rope = nullptr;
+    half_t *h = nullptr, *xn = nullptr, *qkv = nullptr, *attn = nullptr, *act = nullptr;
+    float *slabs = nullptr, *logits = nullptr;
+    long long* tok = nullptr;
+    int* unfinished = nullptr;
+    std::set<std::string> loaded;
+    size_t expected = 0;
+    std::vector<void*> allocs;
+};
+
+namespace {
+
+cgpt_status dev_zalloc(cgpt_llm* m, size_t bytes, void** out) {
+    HIPCHK(hipMalloc(out, bytes));
+    m->allocs.push_back(*out);
+    HIPCHK(hipMemset(*out, 0, bytes));
+    return CGPT_OK;
+}
+
+cgpt_status ready(cgpt_llm* m, const char* who) {
+    if (m->loaded.size() != m->expected)
+        return cgpt_fail(CGPT_ERR_STATE, std::string(who) + ": " + std::to_string(m->expected - m->loaded.size()) + " of " +
+                                             std::to_string(m->expected) + " weights have not been loaded");
+    return CGPT_OK;
+}
+
+cgpt_status check_cache(cgpt_llm* m, const char* who, int B, int last_pos, void* const* k, void* const* v, int64_t len_stride) {
+    if (!k || !v) return cgpt_fail(CGPT_ERR_INVALID, std::string(who) + ": null K/V pointer table");
+    if (B < 1 || B > m->cfg.max_batch) return cgpt_fail(CGPT_ERR_INVALID, std::string(who) + ": rows outside 1..max_batch");
+    if (last_pos < 0 || last_pos >= len_stride || last_pos >= m->cfg.max_len)
+        return cgpt_fail(CGPT_ERR_INVALID, std::string(who) + ": position outside the cache (kv_len_stride) or max_len");
+    for (int l = 0; l < m->cfg.layers; ++l)
+        if (!k[l] || !v[l]) return cgpt_fail(CGPT_ERR_INVALID, std::string(who) + ": null K/V buffer");
+    return CGPT_OK;
+}
+
+#define LAUNCHED() HIPCHK(hipGetLastError())
+
+cgpt_status gemm(cgpt_llm* m, int epi, const half_t* A, int K, const half_t* W, int N, void* out, int64_t ldo, const half_t* resid,
+                 int B, hipStream_t st) {
+    DecodeGemmParams p{};
+    p.A = A; p.lda = K; p.W = W; p.ldw = K; p.out = out; p.ldo = ldo; p.resid = resid; p.ldr = ldo; p.slabs = m->slabs;
+    p.M = B; p.N = N; p.K = K;
+    HIPCHK(launch_decode_gemm(epi, p, st));
+    return CGPT_OK;
+}
+
+// One token step on rows 0..B-1: tokens -> logits (fp32, row stride ld_logits).
+cgpt_status run_step(cgpt_llm* m, const long long* tokens, int B, int pos, void* const* kp, void* const* vp, int64_t len_stride,
+                     float* logits, int64_t ld_logits, hipStream_t st) {
+    const cgpt_llm_config& c = m->cfg;
+    const int H = c.hidden;
+    hipLaunchKernelGGL(llm_embed_kernel, dim3(B), dim3(256), 0, st, tokens, m->embed, c.vocab, H, m->h);
+    LAUNCHED();
+    const size_t attn_lds = (size_t)(2 * HD + pos + 1) * sizeof(float);
+    for (int l = 0; l < c.layers; ++l) {
+        const Layer& L = m->layers[l];
+        hipLaunchKernelGGL(llm_rmsnorm_kernel, dim3(B), dim3(256), 0, st, m->h, L.ln1, H, c.rms_eps, m->xn);
+        LAUNCHED();
+        CGCHK(gemm(m, DEC_F16, m->xn, H, L.wqkv, 3 * H, m->qkv, 3 * H, nullptr, B, st));
+        hipLaunchKernelGGL(llm_attn_kernel, dim3(B * c.heads), dim3(64), attn_lds, st, m->qkv, H, c.heads, (half_t*)kp[l], (half_t*)vp[l],
+                           len_stride, m->rope, pos, m->attn);
+        LAUNCHED();
+        CGCHK(gemm(m, DEC_F16_RESID, m->attn, H, L.wo, H, m->h, H, m->h, B, st));
+        hipLaunchKernelGGL(llm_rmsnorm_kernel, dim3(B), dim3(256), 0, st, m->h, L.ln2, H, c.rms_eps, m->xn);
+        LAUNCHED();
+        CGCHK(gemm(m, DEC_SWIGLU, m->xn, H, L.wgu, 2 * c.mlp, m->act, c.mlp, nullptr, B, st));
+        CGCHK(gemm(m, DEC_F16_RESID, m->act, c.mlp, L.wdown, H, m->h, H, m->h, B, st));
+    }
+    hipLaunchKernelGGL(llm_rmsnorm_kernel, dim3(B), dim3(256), 0, st, m->h, m->norm, H, c.rms_eps, m->xn);
+    LAUNCHED();
+    return gemm(m, DEC_F32, m->xn, H, m->lm_head, c.vocab, logits, ld_logits, nullptr, B, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
+    if (!cfg || !out) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: null argument");
+    if (cfg->struct_size != (int32_t)sizeof(cgpt_llm_config))
+        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: cgpt_llm_config.struct_size mismatch (header/library drift)");
+    const cgpt_llm_config& c = *cfg;
+    if (c.head_dim != HD) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: head_dim must be 128");
+    if (c.heads < 1 || c.kv_heads != c.heads)
+        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: kv_heads must equal heads (no grouped-query attention)");
+    if (c.hidden < 64 || c.hidden % 64 || c.hidden != c.heads * HD)
+        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: hidden must be heads * 128 and a multiple of 64");
+    if (c.layers < 1 || c.mlp < 64 || c.mlp % 64 || c.vocab < 64 || c.vocab % 64)
+        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: layers >= 1, mlp and vocab multiples of 64");
+    if (c.max_batch < 1 || c.max_batch > MAX_ROWS) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: max_batch must be 1..256");
+    if (c.max_len < 1 || c.max_len > 8192) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: max_len must be 1..8192");
+    if (!(c.rms_eps > 0.0f) || !(c.rope_theta > 0.0f)) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: rms_eps and rope_theta must be positive");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return cgpt_fail(CGPT_ERR_NO_DEVICE, "cgpt_llm_create: no HIP device visible (this library has no CPU fallback)");
+    if (c.device < 0 || c.device >= ndev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: bad device ordinal");
+    HIPCHK(hipSetDevice(c.device));
+    HIPCHK(decode_gemm_prepare());                        // kernel attributes now: nothing but launches is left for a captured stream
+    cgpt_llm* m = new cgpt_llm();
+    m->cfg = c;
+    m->layers.resize(c.layers);
+    m->expected = 3 + (size_t)c.layers * 9;
+    const size_t H = c.hidden, F = c.mlp, V = c.vocab, hs = sizeof(half_t);
+    auto fail = [&](cgpt_status s) { cgpt_llm_destroy(m); return s; };
+    cgpt_status s = CGPT_OK;
+    auto za = [&](size_t bytes, void* out_ptr) { if (s == CGPT_OK) s = dev_zalloc(m, bytes, (void**)out_ptr); };
+    za(V * H * hs, &m->embed);
+    za(H * hs, &m->norm);
+    za(V * H * hs, &m->lm_head);
+    for (Layer& L : m->layers) {
+        za(3 * H * H * hs, &L.wqkv);
+        za(H * H * hs, &L.wo);
+        za(2 * F * H * hs, &L.wgu);
+        za(H * F * hs, &L.wdown);
+        za(H * hs, &L.ln1);
+        za(H * hs, &L.ln2);
+    }
+    // activations: whole 256-row tiles (the GEMM stages every row of its tile; rows past the batch hold zeros)
+    za(MAX_ROWS * H * hs, &m->h);
+    za(MAX_ROWS * H * hs, &m->xn);
+    za(MAX_ROWS * 3 * H * hs, &m->qkv);
+    za(MAX_ROWS * H * hs, &m->attn);
+    za(MAX_ROWS * F * hs, &m->act);
+    za(MAX_ROWS * V * sizeof(float), &m->logits);
+    za(MAX_ROWS * sizeof(long long), &m->tok);
+    za(MAX_ROWS * sizeof(int), &m->unfinished);
+    size_t slab = 0;
+    const int shapes[5][2] = {{(int)(3 * H), (int)H}, {(int)H, (int)H}, {(int)(2 * F), (int)H}, {(int)H, (int)F}, {(int)V, (int)H}};
+    for (auto& sh : shapes) slab = std::max(slab, decode_gemm_slab_bytes(sh[0], sh[1]));
+    za(std::max(slab, (size_t)16), &m->slabs);
+    za((size_t)c.max_len * HD * hs, &m->rope);
+    float* inv_freq = nullptr;
+    za(64 * sizeof(float), &inv_freq);
+    if (s != CGPT_OK) return fail(s);
+    float inv_host[64];
+    for (int i = 0; i < 64; ++i) inv_host[i] = 1.0f / powf(c.rope_theta, (float)(2 * i) / (float)HD);
+    if (hipMemcpy(inv_freq, inv_host, sizeof(inv_host), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(cgpt_fail(CGPT_ERR_HIP, "cgpt_llm_create: inv_freq upload failed"));
+    hipLaunchKernelGGL(llm_rope_table_kernel, dim3(c.max_len), dim3(64), 0, 0, inv_freq, m->rope);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+        return fail(cgpt_fail(CGPT_ERR_HIP, "cgpt_llm_create: rotary table kernel failed"));
+    *out = m;
+    return CGPT_OK;
+}
+
+cgpt_status cgpt_llm_destroy(cgpt_llm_handle h) {
+    if (!h) return CGPT_OK;
+    (void)hipSetDevice(h->cfg.device);
+    (void)hipDeviceSynchronize();
+    for (void* p : h->allocs) (void)hipFree(p);
+    delete h;
+    return CGPT_OK;
+}
+
+cgpt_status cgpt_llm_load_weight_f16(cgpt_llm_handle h, const char* name, const void* data_dev, int64_t numel, void* stream) {
+    if (!h || !name || !data_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_load_weight_f16: null argument");
+    const cgpt_llm_config& c = h->cfg;
+    const int64_t H = c.hidden, F = c.mlp, V = c.vocab;
+    hipStream_t st = (hipStream_t)stream;
+    const std::string n(name);
+    half_t* dst = nullptr;
+    int64_t want = 0;
+    int interleave = -1;                                   // 0 = gate, 1 = up: rows go to alternate blocks of 16
+    if (n == "model.embed_tokens.weight") { dst = h->embed; want = V * H; }
+    else if (n == "model.norm.weight") { dst = h->norm; want = H; }
+    else if (n == "lm_head.weight") { dst = h->lm_head; want = V * H; }
+    else {
+        int li = -1, used = 0;
+        if (sscanf(name, "model.layers.%d.%n", &li, &used) != 1 || li < 0 || li >= c.layers)
+            return cgpt_fail(CGPT_ERR_NOT_FOUND, "cgpt_llm_load_weight_f16: unknown weight '" + n + "'");
+        const std::string rest(name + used);
+        Layer& L = h->layers[li];
+        if (rest == "self_attn.q_proj.weight") { dst = L.wqkv; want = H * H; }
+        else if (rest == "self_attn.k_proj.weight") { dst = L.wqkv + H * H; want = H * H; }
+        else if (rest == "self_attn.v_proj.weight") { dst = L.wqkv + 2 * H * H; want = H * H; }
+        else if (rest == "self_attn.o_proj.weight") { dst = L.wo; want = H * H; }
+        else if (rest == "mlp.gate_proj.weight") { dst = L.wgu; want = F * H; interleave = 0; }
+        else if (rest == "mlp.up_proj.weight") { dst = L.wgu; want = F * H; interleave = 1; }
+        else if (rest == "mlp.down_proj.weight") { dst = L.wdown; want = H * F; }
+        else if (rest == "input_layernorm.weight") { dst = L.ln1; want = H; }
+        else if (rest == "post_attention_layernorm.weight") { dst = L.ln2; want = H; }
+        else return cgpt_fail(CGPT_ERR_NOT_FOUND, "cgpt_llm_load_weight_f16: unknown weight '" + n + "'");
+    }
+    if (numel != want)
+        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_load_weight_f16: '" + n + "' expects " + std::to_string(want) + " elements, got " +
+                                               std::to_string(numel));
+    HIPCHK(hipSetDevice(c.device));
+    if (interleave < 0) {
+        HIPCHK(hipMemcpyAsync(dst, data_dev, (size_t)want * sizeof(half_t), hipMemcpyDeviceToDevice, st));
+    } else {                                               // 16 source rows -> rows 32 t + 16 * interleave .. of the fused matrix
+        const size_t blk = (size_t)16 * H * sizeof(half_t);
+        HIPCHK(hipMemcpy2DAsync(dst + (int64_t)interleave * 16 * H, 2 * blk, data_dev, blk, blk, (size_t)(F / 16),
+                                hipMemcpyDeviceToDevice, st));
+    }
+    h->loaded.insert(n);
+    return CGPT_OK;
+}
+
+cgpt_status cgpt_llm_step(cgpt_llm_handle h, const int64_t* tokens_dev, int32_t B, int32_t pos, void* const* k_ptrs_host,
+                          void* const* v_ptrs_host, int64_t kv_len_stride, float* logits_dev, void* stream) {
+    if (!h || !tokens_dev || !logits_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_step: null argument");
+    CGCHK(ready(h, "cgpt_llm_step"));
+    HIPCHK(hipSetDevice(h->cfg.device));
+    CGCHK(check_cache(h, "cgpt_llm_step", B, pos, k_ptrs_host, v_ptrs_host, kv_len_stride));
+    return run_step(h, (const long long*)tokens_dev, B, pos, k_ptrs_host, v_ptrs_host, kv_len_stride, logits_dev, h->cfg.vocab,
+                    (hipStream_t)stream);
+}
+
+cgpt_status cgpt_llm_greedy(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len, int32_t num_new,
+                            int32_t min_new, const int64_t* eos_ids_host, int32_t num_eos, int64_t pad_id, void* const* k_ptrs_host,
+                            void* const* v_ptrs_host, int64_t kv_len_stride, int64_t* tokens_out_dev, float* step_logits_out_dev,
+                            void* stream) {
+    if (!h || !first_logits_dev || !tokens_out_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_greedy: null argument");
+    if (num_new < 1 || prompt_len < 1 || min_new < 0 || num_eos < 0 || num_eos > MAX_EOS || (num_eos > 0 && !eos_ids_host))
+        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_greedy: bad lengths (num_new, prompt_len >= 1; at most 8 EOS ids)");
+    CGCHK(ready(h, "cgpt_llm_greedy"));
+    HIPCHK(hipSetDevice(h->cfg.device));
+    // the last step appends at prompt_len + num_new - 2; with num_new == 1 no step runs but the table must still be sane
+    CGCHK(check_cache(h, "cgpt_llm_greedy", B, num_new > 1 ? prompt_len + num_new - 2 : 0, k_ptrs_host, v_ptrs_host,
+                      num_new > 1 ? kv_len_stride : 1));
+    hipStream_t st = (hipStream_t)stream;
+    EosIds eos{};
+    eos.n = num_eos;
+    for (int e = 0; e < num_eos; ++e) eos.id[e] = eos_ids_host[e];
+    const int V = h->cfg.vocab;
+    const int64_t ld_out = (int64_t)num_new * V;
+    for (int i = 0; i < num_new; ++i) {
+        const float* src;
+        int64_t lds;
+        if (i == 0) { src = first_logits_dev; lds = V; }
+        else if (step_logits_out_dev) { src = step_logits_out_dev + (int64_t)i * V; lds = ld_out; }
+        else { src = h->logits; lds = V; }
+        const int mask = (i < min_new && num_eos > 0) ? 1 : 0;
+        float* dst = nullptr;
+        if (step_logits_out_dev && (i == 0 || mask)) dst = step_logits_out_dev + (int64_t)i * V;
+        hipLaunchKernelGGL(llm_select_kernel, dim3(B), dim3(256), 0, st, src, lds, dst, ld_out, V, mask, eos, (long long)pad_id,
+                           i == 0 ? 1 : 0, h->unfinished, (long long*)tokens_out_dev + i, (int64_t)num_new, h->tok);
+        LAUNCHED();
+        if (i + 1 == num_new) break;
+        float* next = step_logits_out_dev ? step_logits_out_dev + (int64_t)(i + 1) * V : h->logits;
+        CGCHK(run_step(h, h->tok, B, prompt_len + i, k_ptrs_host, v_ptrs_host, kv_len_stride, next,
+                       step_logits_out_dev ? ld_out : (int64_t)V, st));
+    }
+    return CGPT_OK;
+}
+
+}  // extern "C"

@@ -180,6 +180,150 @@ class _LinearRoute:
         return ctx()
 
 
+def hip_decode_unsupported(llama_model, max_batch=None):
+    """Every property of `llama_model` (and of the classifier batch) that keeps it off the native token step (`decode="hip"`,
+    csrc/llm.hip), as a list of sentences; empty = supported.  The step kernels are written for HF `LlamaForCausalLM` in fp16 on
+    a HIP device: bias-free linears, RMSNorm, `rotate_half` rotary with the default (unscaled) rope_theta law, as many K/V heads
+    as query heads, head size 128, SwiGLU, no sliding window -- Vicuna-7B / 13B.  ALL failing properties are collected, so one
+    message names them all."""
+    cfg = getattr(llama_model, "config", None)
+    bad = []
+    if type(llama_model).__name__ != "LlamaForCausalLM" or cfg is None:
+        return [f"architecture: {type(llama_model).__name__} (HF LlamaForCausalLM required)"]
+    prm = next(llama_model.parameters())
+    if not (prm.is_cuda and getattr(torch.version, "hip", None)):
+        bad.append(f"device: {prm.device} (a HIP device is required)")
+    dtypes = sorted({str(q.dtype) for q in llama_model.parameters()})
+    if dtypes != ["torch.float16"]:
+        bad.append(f"dtype: {', '.join(dtypes)} (torch.float16 required)")
+    heads, hidden = int(cfg.num_attention_heads), int(cfg.hidden_size)
+    head_dim = int(getattr(cfg, "head_dim", None) or hidden // heads)
+    if head_dim != 128 or hidden != heads * 128:
+        bad.append(f"head size: head_dim {head_dim} with hidden_size {hidden} / {heads} heads (head_dim 128 and hidden = heads x 128 required)")
+    kv = int(getattr(cfg, "num_key_value_heads", None) or heads)
+    if kv != heads:
+        bad.append(f"K/V heads: num_key_value_heads {kv} != num_attention_heads {heads} (grouped-query attention is not supported)")
+    with_bias = [n for n, m in llama_model.named_modules() if isinstance(m, torch.nn.Linear) and m.bias is not None]
+    if getattr(cfg, "attention_bias", False) or getattr(cfg, "mlp_bias", False) or with_bias:
+        bad.append(f"biases: {len(with_bias)} linear layers carry a bias (bias-free linears required)")
+    rope = getattr(cfg, "rope_parameters", None) or getattr(cfg, "rope_scaling", None) or {}
+    rope_type = rope.get("rope_type", rope.get("type", "default")) if isinstance(rope, dict) else str(rope)
+    if rope_type != "default":
+        bad.append(f"rotary law: rope type {rope_type!r} (only the default, unscaled rope_theta law is supported)")
+    if getattr(cfg, "sliding_window", None):
+        bad.append(f"sliding window: {cfg.sliding_window} (full attention required)")
+    if getattr(cfg, "hidden_act", "silu") != "silu":
+        bad.append(f"activation: {cfg.hidden_act} (SwiGLU with silu required)")
+    for name, val in (("hidden_size", hidden), ("intermediate_size", int(cfg.intermediate_size)), ("vocab_size", int(cfg.vocab_size))):
+        if val % 64:
+            bad.append(f"shape: {name} {val} is not a multiple of 64")
+    if max_batch is not None and int(max_batch) > 256:
+        bad.append(f"batch: max_batch {int(max_batch)} > 256 rows (one GEMM row tile)")
+    eos = getattr(getattr(llama_model, "generation_config", None), "eos_token_id", None)      # as greedy_tokens resolves it
+    eos = getattr(cfg, "eos_token_id", None) if eos is None else eos
+    if isinstance(eos, (list, tuple)) and len(eos) > 8:
+        bad.append(f"EOS ids: {len(eos)} end-of-sequence ids (the token select takes at most 8)")
+    return bad
+
+
+def _rope_theta(cfg):
+    rope = getattr(cfg, "rope_parameters", None) or getattr(cfg, "rope_scaling", None) or {}
+    theta = rope.get("rope_theta") if isinstance(rope, dict) else None
+    return float(theta or getattr(cfg, "rope_theta", None) or 10000.0)
+
+
+class _HipDecoder:
+    """The native token step of a frozen LlamaForCausalLM (`cgpt_llm_*`, include/cgpt.h): validates the model, creates the handle
+    and hands it the module's own fp16 parameters ONCE (the library keeps fused copies: 2 bytes per parameter more HBM, 13.5 GB at
+    7B; a later change of the module's weights is not seen).  `greedy` enqueues the whole loop after the prefill on the current
+    stream -- no host sync, capturable -- on the K/V buffers the prefill filled, in place."""
+    MAX_LEN = 4096                                                     # positions the rotary table covers (prompt + new tokens)
+
+    def __init__(self, llama_model, max_batch):
+        import ctypes as C
+        from . import _lib
+        bad = hip_decode_unsupported(llama_model, max_batch)
+        if bad:
+            raise ValueError('decode="hip" does not support this decoder -- ' + "; ".join(bad))
+        self._C, self._lib_mod, self.L = C, _lib, _lib.lib()
+        cfg = llama_model.config
+        self.device = next(llama_model.parameters()).device
+        self.layers, self.heads, self.vocab = int(cfg.num_hidden_layers), int(cfg.num_attention_heads), int(cfg.vocab_size)
+        self.max_batch = int(max_batch)
+        c = _lib.LlmConfig(struct_size=C.sizeof(_lib.LlmConfig), device=self.device.index or 0, hidden=int(cfg.hidden_size),
+                           layers=self.layers, heads=self.heads, kv_heads=self.heads, head_dim=128, mlp=int(cfg.intermediate_size),
+                           vocab=self.vocab, rms_eps=float(cfg.rms_norm_eps), rope_theta=_rope_theta(cfg),
+                           max_batch=self.max_batch, max_len=self.MAX_LEN)
+        self.handle = C.c_void_p()
+        _lib.check(self.L.cgpt_llm_create(C.byref(c), C.byref(self.handle)))
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        wanted = ["model.embed_tokens.weight", "model.norm.weight", "lm_head.weight"]
+        for i in range(self.layers):
+            wanted += [f"model.layers.{i}.self_attn.{n}_proj.weight" for n in "qkvo"]
+            wanted += [f"model.layers.{i}.mlp.{n}_proj.weight" for n in ("gate", "up", "down")]
+            wanted += [f"model.layers.{i}.{n}_layernorm.weight" for n in ("input", "post_attention")]
+        sd = llama_model.state_dict()
+        for name in wanted:
+            w = sd[name].detach()
+            assert w.dtype == torch.float16 and w.device == self.device, name
+            w = w.contiguous()
+            _lib.check(self.L.cgpt_llm_load_weight_f16(self.handle, name.encode(), C.c_void_p(w.data_ptr()), w.numel(), st))
+        torch.cuda.current_stream(self.device).synchronize()           # contiguous() temporaries may go once the copies have run
+
+    def close(self):
+        if getattr(self, "handle", None) is not None and self.handle.value:
+            self.L.cgpt_llm_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _cache_tables(self, k_bufs, v_bufs, B, need_len):
+        """Host tables of the per-layer K / V device pointers, after checking every buffer is what the kernels index:
+        [B, heads, len_stride, 128] fp16, contiguous, on the handle's device, long enough for the last appended row."""
+        C = self._C
+        assert len(k_bufs) == len(v_bufs) == self.layers, "one K and one V buffer per layer"
+        stride = int(k_bufs[0].shape[2])
+        assert need_len <= stride and need_len <= self.MAX_LEN, (need_len, stride, self.MAX_LEN)
+        for t in list(k_bufs) + list(v_bufs):
+            assert (t.dtype == torch.float16 and t.device == self.device and t.is_contiguous()
+                    and tuple(t.shape) == (B, self.heads, stride, 128)), (tuple(t.shape), t.dtype, t.device)
+        kp = (C.c_void_p * self.layers)(*[t.data_ptr() for t in k_bufs])
+        vp = (C.c_void_p * self.layers)(*[t.data_ptr() for t in v_bufs])
+        return kp, vp, stride
+
+    def step(self, tokens, pos, k_bufs, v_bufs):
+        """One teacher-forced step: tokens [B] int64 at position `pos` -> logits [B, vocab] fp32; K / V row `pos` appended in place."""
+        C = self._C
+        B = int(tokens.shape[0])
+        assert tokens.dtype == torch.int64 and tokens.device == self.device and tokens.is_contiguous() and 1 <= B <= self.max_batch
+        kp, vp, stride = self._cache_tables(k_bufs, v_bufs, B, int(pos) + 1)
+        logits = torch.empty((B, self.vocab), dtype=torch.float32, device=self.device)
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._lib_mod.check(self.L.cgpt_llm_step(self.handle, C.c_void_p(tokens.data_ptr()), B, int(pos), kp, vp, stride,
+                                                 C.c_void_p(logits.data_ptr()), st))
+        return logits
+
+    def greedy(self, first_logits, prompt_len, num_new, min_new, eos_ids, pad_id, k_bufs, v_bufs, return_logits=False):
+        """The loop of `greedy_tokens` after the prefill: tokens [B, num_new] int64 (and the logits each arg-max saw)."""
+        C = self._C
+        B, V = first_logits.shape
+        assert (first_logits.dtype == torch.float32 and first_logits.device == self.device and first_logits.is_contiguous()
+                and V == self.vocab and 1 <= B <= self.max_batch and num_new >= 1 and len(eos_ids) <= 8)
+        kp, vp, stride = self._cache_tables(k_bufs, v_bufs, B, prompt_len + num_new - 1)
+        tokens = torch.empty((B, num_new), dtype=torch.int64, device=self.device)
+        steps = torch.empty((B, num_new, V), dtype=torch.float32, device=self.device) if return_logits else None
+        eos = (C.c_int64 * max(1, len(eos_ids)))(*[int(e) for e in eos_ids])
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._lib_mod.check(self.L.cgpt_llm_greedy(
+            self.handle, C.c_void_p(first_logits.data_ptr()), B, int(prompt_len), int(num_new), int(min_new), eos, len(eos_ids),
+            int(pad_id), kp, vp, stride, C.c_void_p(tokens.data_ptr()), C.c_void_p(steps.data_ptr()) if return_logits else None, st))
+        return (tokens, steps) if return_logits else tokens
+
+
 class MiniGPT4Classifier:
     """:param encoder: a `HipClassifier(mode="encode_img")` (or any object with `encode_img(images) -> (emb, atts)` and
                `encode_img_noisy(x, first_sample, num, sigma, seed) -> emb`, emb = [B, queries, llm_hidden])
@@ -218,15 +362,21 @@ class MiniGPT4Classifier:
         # prefill_linear = "cgpt" (with decode = "graph"): the decoder's bias-free fp16 linears run the prefill's rows through this
         #   library's GEMM (see _LinearRoute); same arithmetic contract (fp16 operands, fp32 accumulation, fp16 result), other rounding
         #   order than the vendor library: first-token logits within 4 fp16 ulp, same decisive-row rule.
-        assert decode in ("hf", "graph") and prefill_linear in ("torch", "cgpt")
+        # decode = "hip": the prefill as under "graph" (routed or not), then every token step in this library's own kernels
+        #   (csrc/llm.hip: RMSNorm, decode-shape GEMMs, rotary + K/V append + one-query attention, token select) on the K/V the
+        #   prefill wrote, captured into the same kind of graph.  Opt-in; a decoder the kernels do not support is a ValueError here,
+        #   never another engine.  Parity: tests/test_gpu_llm_decode.py (teacher-forced logit error against HF's own fp16 error).
+        assert decode in ("hf", "graph", "hip") and prefill_linear in ("torch", "cgpt")
         self.decode = decode
         self.prefill_linear = prefill_linear
-        self.routed_linears = _LinearRoute.install(llama_model) if (decode == "graph" and prefill_linear == "cgpt") else 0
+        self._hip = _HipDecoder(llama_model, self.max_batch) if decode == "hip" else None
+        self.routed_linears = _LinearRoute.install(llama_model) if (decode in ("graph", "hip") and prefill_linear == "cgpt") else 0
         import collections
         self._graphs = collections.OrderedDict()            # LRU of captured decode graphs, see _generate_graph
         self.max_graphs = 4
         self._eos_mask = None
-        self.decode_stats = {"graph_replays": 0, "graph_captures": 0, "graph_evictions": 0, "hf_calls": 0, "hf_fallback_kwargs": 0}
+        self.decode_stats = {"graph_replays": 0, "graph_captures": 0, "graph_evictions": 0, "hf_calls": 0, "hf_fallback_kwargs": 0,
+                             "hip_steps": 0}                      # token steps enqueued on the native engine (decode = "hip")
 
     # ---- nn.Module-shaped surface used by Smooth (smoothing.py:42,71)
     def eval(self):
@@ -279,11 +429,11 @@ class MiniGPT4Classifier:
                 embs[i, -emb.shape[1]:] = emb[0]
                 attn_mask[i, -emb.shape[1]:] = 1
         shared = isinstance(texts, str) or len(set(texts)) == 1
-        if self.decode == "graph" and shared and embs.is_cuda and self._greedy_defaults():
+        if self.decode in ("graph", "hip") and shared and embs.is_cuda and self._greedy_defaults():
             outputs = self._generate_graph(embs)
         else:
             self.decode_stats["hf_calls"] += 1
-            if self.decode == "graph" and shared and embs.is_cuda:
+            if self.decode in ("graph", "hip") and shared and embs.is_cuda:
                 self.decode_stats["hf_fallback_kwargs"] += 1            # generation arguments outside the greedy whitelist
             outputs = self.llama_model.generate(inputs_embeds=embs, attention_mask=attn_mask, max_new_tokens=self.max_new_tokens,
                                                 **self.hf_generate_kwargs())
@@ -410,6 +560,11 @@ class MiniGPT4Classifier:
                 m = torch.zeros(logits.shape[-1], dtype=torch.bool)
                 m[eos_ids] = True
                 self._eos_mask = (key, m.to(embs.device))
+        if self._hip is not None:                                      # decode = "hip": the loop below, in this library's kernels
+            assert B <= self.max_batch, f"{B} rows > max_batch {self.max_batch} (the native decoder's workspace)"
+            self.decode_stats["hip_steps"] += self.max_new_tokens - 1
+            return self._hip.greedy(logits.contiguous(), L, self.max_new_tokens, min_new, eos_ids, pad,
+                                    [l.buf_k for l in cache.layers], [l.buf_v for l in cache.layers], return_logits=return_logits)
         unfinished = torch.ones(B, dtype=torch.long, device=embs.device)
         tokens, step_logits = [], []
         for i in range(self.max_new_tokens):
@@ -432,11 +587,11 @@ class MiniGPT4Classifier:
         return torch.stack(tokens, dim=1)
 
     def _generate_graph(self, embs):
-        """One captured hipGraph per (batch, prompt length, dtype, device, max_new_tokens, routed prefill), kept in an LRU of
+        """One captured hipGraph per (batch, prompt length, dtype, device, max_new_tokens, routed prefill, engine), kept in an LRU of
         `max_graphs` entries: a graph pins its private pool -- the pre-allocated K / V of every layer plus activations, ~6.7 GB of K / V
         alone at 200 rows x 32 layers x 64 positions -- and ragged last batches or new prompt lengths add entries; the least recently
         used one is dropped (graph and static tensors freed) before a new capture."""
-        key = (embs.shape[0], embs.shape[1], embs.dtype, embs.device.index, self.max_new_tokens, bool(self.routed_linears))
+        key = (embs.shape[0], embs.shape[1], embs.dtype, embs.device.index, self.max_new_tokens, bool(self.routed_linears), self.decode)
         entry = self._graphs.get(key)
         if entry is not None:
             self._graphs.move_to_end(key)
@@ -451,6 +606,7 @@ class MiniGPT4Classifier:
             side.wait_stream(torch.cuda.current_stream())
             import contextlib
             route = _LinearRoute.enabled() if self.routed_linears else contextlib.nullcontext()
+            hip_steps = self.decode_stats["hip_steps"]                 # counted per replay below, not for warm-up and capture
             with route:
                 with torch.cuda.stream(side):                          # warm-up outside the capture (lazy initialisations)
                     self.greedy_tokens(static_in)
@@ -458,6 +614,7 @@ class MiniGPT4Classifier:
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
                     static_out = self.greedy_tokens(static_in)
+            self.decode_stats["hip_steps"] = hip_steps
             entry = (graph, static_in, static_out)
             self._graphs[key] = entry
             self.decode_stats["graph_captures"] += 1
@@ -465,6 +622,8 @@ class MiniGPT4Classifier:
         static_in.copy_(embs)
         graph.replay()
         self.decode_stats["graph_replays"] += 1
+        if self._hip is not None:
+            self.decode_stats["hip_steps"] += self.max_new_tokens - 1
         return static_out.clone()
 
     @torch.no_grad()

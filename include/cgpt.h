@@ -310,6 +310,63 @@ cgpt_status cgpt_layernorm(const float* x_dev, int64_t ldx, const float* gamma_d
                            void* y_dev, int64_t ldy, float* y32_dev, int64_t ldy32, int64_t rows, int32_t D,
                            void* stream);
 
+/* ---- LLaMA decode steps (replaces: every forward after the prefill inside `self.llama_model.generate(...)`,
+ *      minigpt_base.py:418-431 -- greedy, one new token per row, K/V cache) ----
+ * A decoder is not a cgpt_model: it has its own handle.  Supported architecture (checked by cgpt_llm_create BEFORE any device
+ * call): HF LlamaForCausalLM in fp16 -- bias-free linears, RMSNorm, rotate_half rotary with the default (unscaled) rope_theta
+ * law, kv_heads == heads (no grouped-query attention), head_dim == 128, hidden == heads * 128, SwiGLU MLP; hidden, mlp and
+ * vocab multiples of 64; max_batch <= 256 (one GEMM row tile); max_len <= 8192 (positions the rotary table covers).
+ * That is Vicuna-7B / 13B.  The PREFILL stays with the caller (the model's own forward): the step entries work on the caller's
+ * K/V buffers in place, layout [B, heads, kv_len_stride, 128] fp16 per layer, rows 0 .. pos-1 filled by the prefill.
+ * Rounding: where HF's fp16 eager model rounds ("LLaMA decode steps"); split-K partial sums are combined in slice
+ * order, so results are bit-identical from launch to launch and a row's result does not depend on the batch around it.
+ * All work is enqueued on `stream`; no host sync, no allocation and no host->device copy after create: capturable in a graph
+ * without a warm-up call (kernel attributes are set by create).  The step entries select the handle's device.  A handle owns ONE
+ * step workspace: one stream at a time per handle -- calls on two streams must be ordered by the caller. */
+typedef struct cgpt_llm_config {
+    int32_t struct_size;      /* = sizeof(cgpt_llm_config)                                         */
+    int32_t device;           /* HIP device ordinal                                                */
+    int32_t hidden;           /* 4096 (Vicuna-7B)                                                  */
+    int32_t layers;           /* 32                                                                */
+    int32_t heads;            /* 32                                                                */
+    int32_t kv_heads;         /* must equal heads                                                  */
+    int32_t head_dim;         /* must be 128                                                       */
+    int32_t mlp;              /* 11008 (intermediate_size)                                         */
+    int32_t vocab;            /* 32000                                                             */
+    float   rms_eps;          /* 1e-5 / 1e-6 (config.rms_norm_eps)                                 */
+    float   rope_theta;       /* 10000                                                             */
+    int32_t max_batch;        /* rows of a step, <= 256                                            */
+    int32_t max_len;          /* positions (prompt + new tokens) the rotary table covers           */
+} cgpt_llm_config;
+
+typedef struct cgpt_llm* cgpt_llm_handle;
+
+/* Allocates the library's own weight copies (fused q/k/v and gate/up, 2 bytes per parameter: 13.5 GB MORE HBM at 7B, beside the
+ * HF module's) and the step workspace.  CGPT_ERR_INVALID for an unsupported config, CGPT_ERR_NO_DEVICE without a GPU. */
+cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out);
+cgpt_status cgpt_llm_destroy(cgpt_llm_handle h);
+/* Device-to-device copy of one fp16 parameter of the HF module under its state_dict name: "model.embed_tokens.weight",
+ * "model.layers.<i>.self_attn.{q,k,v,o}_proj.weight", "model.layers.<i>.mlp.{gate,up,down}_proj.weight",
+ * "model.layers.<i>.{input,post_attention}_layernorm.weight", "model.norm.weight", "lm_head.weight" (contiguous, PyTorch shape;
+ * numel must match).  Enqueued on `stream`.  The step entries return CGPT_ERR_STATE until every name has been loaded. */
+cgpt_status cgpt_llm_load_weight_f16(cgpt_llm_handle h, const char* name, const void* data_dev, int64_t numel, void* stream);
+/* One token step: row b feeds token tokens_dev[b] (int64) at position `pos`; layer l appends its rotated key and its value to
+ * row `pos` of k_ptrs_host[l] / v_ptrs_host[l] (device buffers [B, heads, kv_len_stride, 128] fp16; the two tables are HOST
+ * arrays of `layers` device pointers, read when the call enqueues) and attends over rows 0 .. pos.  No other cache row is
+ * written.  logits_dev: [B, vocab] fp32 (fp16-rounded values, as HF's `.float()` of fp16 logits).  Tests drive this entry
+ * teacher-forced. */
+cgpt_status cgpt_llm_step(cgpt_llm_handle h, const int64_t* tokens_dev, int32_t B, int32_t pos, void* const* k_ptrs_host,
+                          void* const* v_ptrs_host, int64_t kv_len_stride, float* logits_dev, void* stream);
+/* The greedy loop after a prefill of prompt_len positions whose last-position logits are first_logits_dev [B, vocab] fp32 (not
+ * modified): num_new x select, with num_new - 1 steps between them, all enqueued by this one call.  Select = HF greedy search:
+ * the num_eos ids of eos_ids_host (<= 8) read as -inf on the first min_new tokens, first-max arg-max, pad_id for a row that has
+ * produced an EOS.  tokens_out_dev: [B, num_new] int64.  step_logits_out_dev (or NULL): [B, num_new, vocab] fp32, the logits each
+ * arg-max was taken on (EOS columns at -inf where suppressed). */
+cgpt_status cgpt_llm_greedy(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len, int32_t num_new,
+                            int32_t min_new, const int64_t* eos_ids_host, int32_t num_eos, int64_t pad_id, void* const* k_ptrs_host,
+                            void* const* v_ptrs_host, int64_t kv_len_stride, int64_t* tokens_out_dev, float* step_logits_out_dev,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,123 @@
+"""Device time of the greedy decode of BASELINE configs[2] on the "graph" engine (PyTorch-ROCm steps, cgpt prefill) and on the
+"hip" engine (this library's token steps), interleaved in one process.
+
+Vicuna-7B-shaped random-init decoder (no checkpoint exists here; nothing is downloaded), 200 rows, a prompt of 44 positions, 20 new
+tokens.  Per repetition and engine, by HIP events around graph replays:
+    generate_ms  = one whole `generate_from_embeds`-shaped replay (prefill + 20 selects + 19 steps)
+    prefill_ms   = the same classifier with max_new_tokens = 1 (prefill + 1 select, no step)
+    steps_ms     = generate_ms - prefill_ms  (the 19 steps and their selects), step_ms = steps_ms / 19
+Prints ONE JSON line.  The floor quoted beside it is bytes / copy rate: the decoder's weight bytes plus the mean K / V bytes a step
+reads, over 6.3 TB/s (the copy rate the box reaches)."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from certifiedgpt_amd.agents.label_adapter import AnswerLabelMap  # noqa: E402
+from certifiedgpt_amd.minigpt4 import MiniGPT4Classifier, WordHashTokenizer  # noqa: E402
+
+COPY_RATE = 6.3e12
+
+
+class _Rows:
+    """Stands where the encoder stands: only `max_batch` is read on this path."""
+    def __init__(self, n):
+        self.max_batch = n
+
+
+def _decoder(layers, dev):
+    from transformers import LlamaConfig, LlamaForCausalLM
+    lcfg = LlamaConfig(vocab_size=32000, hidden_size=4096, intermediate_size=11008, num_hidden_layers=layers, num_attention_heads=32,
+                       num_key_value_heads=32, max_position_embeddings=2048, pad_token_id=0, bos_token_id=1, eos_token_id=2)
+    torch.manual_seed(0)
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float16)
+    try:
+        with torch.device(dev):
+            llm = LlamaForCausalLM(lcfg).eval()
+    finally:
+        torch.set_default_dtype(prev)
+    for prm in llm.parameters():
+        prm.requires_grad = False
+    return llm
+
+
+def _clock():
+    try:
+        return int(torch.cuda.clock_rate())
+    except Exception as e:  # noqa: BLE001 -- the figure is a note beside the result, never an input to it
+        return f"unavailable ({type(e).__name__})"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=200)
+    ap.add_argument("--prompt", type=int, default=44)
+    ap.add_argument("--new", type=int, default=20)
+    ap.add_argument("--layers", type=int, default=32)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--engines", default="graph,hip")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "this benchmark measures device time: it needs the GPU"
+    assert 1 <= args.rows <= 256 and args.new >= 2 and args.prompt >= 1
+    dev = "cuda:0"
+    engines = args.engines.split(",")
+    llm = _decoder(args.layers, dev)
+    g = torch.Generator(device="cpu").manual_seed(1)
+    embs = llm.get_input_embeddings()(torch.randint(3, 32000, (args.rows, args.prompt), generator=g).to(dev))
+    tok, lm = WordHashTokenizer(32000), AnswerLabelMap(4, ())
+    clfs = {(e, n): MiniGPT4Classifier(_Rows(args.rows), llm, tok, "<ImageHere>", lm, max_new_tokens=n, max_batch=args.rows, decode=e,
+                                       prefill_linear="cgpt") for e in engines for n in (args.new, 1)}
+
+    def timed(clf):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = clf._generate_graph(embs)
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b), out
+
+    clock_before = _clock()
+    with torch.no_grad():
+        for _ in range(args.warmup):                                   # capture + warm replays of every graph
+            for clf in clfs.values():
+                timed(clf)
+        res = {e: {"generate_ms": [], "prefill_ms": []} for e in engines}
+        tokens = {}
+        for _ in range(args.reps):                                     # interleaved: engine by engine inside every repetition
+            for e in engines:
+                t, out = timed(clfs[(e, args.new)])
+                res[e]["generate_ms"].append(t)
+                tokens[e] = out
+                res[e]["prefill_ms"].append(timed(clfs[(e, 1)])[0])
+    clock_after = _clock()
+    steps = args.new - 1
+    for e in engines:
+        r = res[e]
+        r["steps_ms"] = [gm - pm for gm, pm in zip(r["generate_ms"], r["prefill_ms"])]
+        r["step_ms"] = [s / steps for s in r["steps_ms"]]
+        r["step_ms_min_max"] = [min(r["step_ms"]), max(r["step_ms"])]
+        r["generate_ms_min_max"] = [min(r["generate_ms"]), max(r["generate_ms"])]
+    weight_bytes = 2 * sum(p.numel() for n, p in llm.named_parameters() if "embed_tokens" not in n)
+    kv_mean = 2 * 2 * args.rows * args.layers * 4096 * (args.prompt + (steps + 1) / 2.0)
+    line = {"tool": "decode_step_bench", "rows": args.rows, "prompt": args.prompt, "new_tokens": args.new, "layers": args.layers,
+            "reps": args.reps, "warmup": args.warmup, "engines": res,
+            "floor_ms_per_step": (weight_bytes + kv_mean) / COPY_RATE * 1e3, "weight_bytes": weight_bytes, "kv_bytes_mean_step": kv_mean,
+            "copy_rate_bytes_per_s": COPY_RATE, "shader_clock_mhz_before_after": [clock_before, clock_after],
+            "device": torch.cuda.get_device_name(0)}
+    if "graph" in res and "hip" in res:
+        line["slowest_hip_beats_fastest_graph"] = {
+            "step": max(res["hip"]["step_ms"]) < min(res["graph"]["step_ms"]),
+            "generate": max(res["hip"]["generate_ms"]) < min(res["graph"]["generate_ms"])}
+        line["rows_with_identical_tokens"] = int((tokens["hip"] == tokens["graph"]).all(dim=1).sum())
+    print(json.dumps(line))
+
+
+if __name__ == "__main__":
+    main()
