@@ -94,6 +94,8 @@ SIGNATURES = {
     "cgpt_llm_load_weight_f16": (_I32, [_P, C.c_char_p, _P, _I64, _P]),
     "cgpt_llm_step": (_I32, [_P, _P, _I32, _I32, _P, _P, _I64, _P, _P]),
     "cgpt_llm_greedy": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _P, _I32, _I64, _P, _P, _I64, _P, _P, _P]),
+    "cgpt_llm_prefill_reserve": (_I32, [_P, _I32, _I32]),
+    "cgpt_llm_prefill": (_I32, [_P, _P, _I32, _I32, _P, _P, _I64, _P, _P]),
 }
 
 _lib = None

@@ -13,6 +13,8 @@ Config (a plain dict or any mapping; the reference's YAMLs define no smoothing k
             #                                       (all their draws) of each group of images_per_pass x world; no vote all-reduce
     model: {generate: {llama_model: <LOCAL dir>, prompt | question: ..., answers: [...], max_new_tokens: 20},   # optional: full
             #          MiniGPT-4 `generate` as the base classifier (certifiedgpt_amd/minigpt4.py); classes = the answer vocabulary
+            #          also: decode: "hf" | "graph" | "hip", prefill_linear: "torch" | "cgpt", prefill: "model" | "hip" (the native
+            #          prefill; needs decode "hip") -- see build_generating_classifier
             mode: vit_head | encode_img, weights: <path to a torch state_dict saved with torch.save> | null, dims: {...},
             partial_weights: false}   # true: load what the checkpoint has on top of the synthetic initialisation
     data:  {num_images: 10, seed: 1234}      # synthetic CLIP-normalised images unless `dataset` is passed to the agent
@@ -161,7 +163,8 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
     causal LM on PyTorch-ROCm, loaded BY LOCAL PATH only (base_model.py:181-247 loads `llama_model` the same way; nothing is
     ever fetched), + the answer vocabulary that defines the classes.
         gen_cfg: {llama_model: <local dir>, prompt: "... <ImageHere> ...", answers: [...], max_new_tokens: 20,
-                  decode: "hf" | "graph" | "hip", prefill_linear: "torch" | "cgpt"}   (decode / prefill_linear: see MiniGPT4Classifier)"""
+                  decode: "hf" | "graph" | "hip", prefill_linear: "torch" | "cgpt", prefill: "model" | "hip"}
+                  (decode / prefill_linear / prefill: see MiniGPT4Classifier; prefill "hip" needs decode "hip")"""
     from ..minigpt4 import MiniGPT4Classifier, prepare_texts
     from .label_adapter import AnswerLabelMap
     if llama_model is None:
@@ -188,7 +191,8 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
     label_map = AnswerLabelMap(num_classes, answers, frozen=True)
     return MiniGPT4Classifier(encoder, llama_model, tokenizer, prompt, label_map,
                               max_new_tokens=int(gen_cfg.get("max_new_tokens", 20)), max_batch=encoder.max_batch,
-                              decode=gen_cfg.get("decode", "hf"), prefill_linear=gen_cfg.get("prefill_linear", "torch"))
+                              decode=gen_cfg.get("decode", "hf"), prefill_linear=gen_cfg.get("prefill_linear", "torch"),
+                              prefill=gen_cfg.get("prefill", "model"))
 
 
 def build_classifier(model_cfg, num_classes, max_batch, device_index, tokenizer=None, llama_model=None):

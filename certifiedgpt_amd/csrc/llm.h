@@ -34,4 +34,19 @@ size_t decode_gemm_slab_bytes(int N, int K);                // workspace the sha
 hipError_t decode_gemm_prepare();
 hipError_t launch_decode_gemm(int epilogue, const DecodeGemmParams& p, hipStream_t stream);
 
+// ------------------------------------------------------------------------------------- prefill (llm_prefill.hip)
+// Token row r = b * L + p of B prompts of L positions.  All fp16, rows `hidden` (or 3 hidden / 2 mlp / mlp) elements apart.
+// x_out[r] = fp16(x[s] + delta[s]) (delta may be null), y[r] = LlamaRMSNorm(x_out[r]) * w, with s = r * src_mul + src_add
+// (identity: 1, 0; the last position of every prompt: L, L - 1).  x_out may alias x.
+hipError_t launch_prefill_addnorm(const half_t* x, const half_t* delta, int64_t src_mul, int64_t src_add, const half_t* w, int hidden,
+                                  float eps, half_t* x_out, half_t* y, int64_t rows, hipStream_t stream);
+// Rotates q in place in qkv [B L, 3 hidden] and writes rotated k and v to rows 0 .. L-1 of Kc / Vc [B, heads, len_stride, 128].
+hipError_t launch_prefill_rope(half_t* qkv, int B, int L, int hidden, int heads, half_t* Kc, half_t* Vc, int64_t len_stride,
+                               const half_t* rope, hipStream_t stream);
+// out[B L, hidden] = causal softmax(q . K^T / sqrt(128)) . V per head, q from qkv (already rotated), K / V rows 0 .. L-1 of the cache.
+hipError_t launch_prefill_attention(const half_t* qkv, int B, int L, int hidden, int heads, const half_t* Kc, const half_t* Vc,
+                                    int64_t len_stride, half_t* out, hipStream_t stream);
+// act[rows, mlp] = fp16(fp16(silu(gate)) * up) from gu [rows, 2 mlp] with gate / up columns interleaved in blocks of 16.
+hipError_t launch_prefill_swiglu(const half_t* gu, int64_t rows, int mlp, half_t* act, hipStream_t stream);
+
 }  // namespace cgpt

@@ -2,7 +2,8 @@
 //
 // Reference call replaced: every forward after the prefill inside `self.llama_model.generate(...)`
 // (graphs/models/minigpt4/models/minigpt_base.py:418-431, greedy: do_sample=False, num_beams=1), i.e. HF LlamaForCausalLM
-// on one new token per row with a K/V cache.  The prefill stays the model's own forward; its K/V are used in place.
+// on one new token per row with a K/V cache.  The prefill is the caller's (the model's own forward; its K/V are used in place) or
+// cgpt_llm_prefill below: the same layer sequence on B x L token rows, large-shape GEMMs (gemm.hip) and llm_prefill.hip's kernels.
 //
 // One step = embedding lookup, layers x (RMSNorm, fused q/k/v GEMM, rotary + K/V append + one-query attention, o_proj GEMM +
 // residual, RMSNorm, fused gate/up GEMM + SwiGLU, down GEMM + residual), final RMSNorm, lm_head GEMM.  The GEMMs are
@@ -249,6 +250,10 @@ struct cgpt_llm {
     std::set<std::string> loaded;
     size_t expected = 0;
     std::vector<void*> allocs;
+    // prefill workspace (cgpt_llm_prefill_reserve): `p_rows` token rows, a multiple of 256.  A workspace that a larger one replaced
+    // stays allocated (in `allocs`) until destroy: a graph captured earlier still holds its addresses.
+    int64_t p_rows = 0;
+    half_t *p_h = nullptr, *p_xn = nullptr, *p_qkv = nullptr, *p_attn = nullptr, *p_proj = nullptr, *p_gu = nullptr, *p_act = nullptr;
 };
 
 namespace {
@@ -315,6 +320,43 @@ cgpt_status run_step(cgpt_llm* m, const long long* tokens, int B, int pos, void*
     return gemm(m, DEC_F32, m->xn, H, m->lm_head, c.vocab, logits, ld_logits, nullptr, B, st);
 }
 
+// C[M, N] = A[M, K] * W[N, K]^T, fp16 result of the fp32 sum, through the large-shape GEMM of the ViT (gemm.hip / gemm9.hip).
+cgpt_status big_gemm(const half_t* A, int K, const half_t* W, int N, half_t* out, int64_t M, hipStream_t st) {
+    GemmParams p{};
+    p.A = A; p.lda = K; p.W = W; p.ldw = K; p.bias = nullptr; p.out = out; p.ldo = N; p.aux = nullptr; p.ldaux = 0;
+    p.M = (int)M; p.N = N; p.K = K; p.patches = 0;
+    HIPCHK(launch_gemm(EPI_F16, p, st));
+    return CGPT_OK;
+}
+
+// The prefill of B prompts of L positions: embeds [B, L, hidden] -> cache rows 0 .. L-1 of every layer, last-position logits.
+// The residual stream stays fp16 as in HF; a projection's output is added by the NEXT add + RMSNorm pass (`pending`).
+cgpt_status run_prefill(cgpt_llm* m, const half_t* embeds, int B, int L, void* const* kp, void* const* vp, int64_t len_stride,
+                        float* logits, hipStream_t st) {
+    const cgpt_llm_config& c = m->cfg;
+    const int H = c.hidden, F = c.mlp;
+    const int64_t M = (int64_t)B * L;
+    const half_t* x = embeds;                              // layer 0 reads the caller's rows and writes the stream
+    const half_t* pending = nullptr;
+    for (int l = 0; l < c.layers; ++l) {
+        const Layer& Lw = m->layers[l];
+        HIPCHK(launch_prefill_addnorm(x, pending, 1, 0, Lw.ln1, H, c.rms_eps, m->p_h, m->p_xn, M, st));
+        x = m->p_h;
+        CGCHK(big_gemm(m->p_xn, H, Lw.wqkv, 3 * H, m->p_qkv, M, st));
+        HIPCHK(launch_prefill_rope(m->p_qkv, B, L, H, c.heads, (half_t*)kp[l], (half_t*)vp[l], len_stride, m->rope, st));
+        HIPCHK(launch_prefill_attention(m->p_qkv, B, L, H, c.heads, (const half_t*)kp[l], (const half_t*)vp[l], len_stride, m->p_attn, st));
+        CGCHK(big_gemm(m->p_attn, H, Lw.wo, H, m->p_proj, M, st));
+        HIPCHK(launch_prefill_addnorm(m->p_h, m->p_proj, 1, 0, Lw.ln2, H, c.rms_eps, m->p_h, m->p_xn, M, st));
+        CGCHK(big_gemm(m->p_xn, H, Lw.wgu, 2 * F, m->p_gu, M, st));
+        HIPCHK(launch_prefill_swiglu(m->p_gu, M, F, m->p_act, st));
+        CGCHK(big_gemm(m->p_act, F, Lw.wdown, H, m->p_proj, M, st));
+        pending = m->p_proj;
+    }
+    // tail, as run_step ends: the last position's row of every prompt (with its pending update) into the step workspace
+    HIPCHK(launch_prefill_addnorm(m->p_h, pending, L, L - 1, m->norm, H, c.rms_eps, m->h, m->xn, B, st));
+    return gemm(m, DEC_F32, m->xn, H, m->lm_head, c.vocab, logits, c.vocab, nullptr, B, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -345,6 +387,7 @@ cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
     m->layers.resize(c.layers);
     m->expected = 3 + (size_t)c.layers * 9;
     const size_t H = c.hidden, F = c.mlp, V = c.vocab, hs = sizeof(half_t);
+    auto up256 = [](size_t n) { return (n + 255) / 256 * 256; };   // the prefill's GEMM reads whole 256-row tiles of W (pad rows: zeros)
     auto fail = [&](cgpt_status s) { cgpt_llm_destroy(m); return s; };
     cgpt_status s = CGPT_OK;
     auto za = [&](size_t bytes, void* out_ptr) { if (s == CGPT_OK) s = dev_zalloc(m, bytes, (void**)out_ptr); };
@@ -352,10 +395,10 @@ cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
     za(H * hs, &m->norm);
     za(V * H * hs, &m->lm_head);
     for (Layer& L : m->layers) {
-        za(3 * H * H * hs, &L.wqkv);
-        za(H * H * hs, &L.wo);
-        za(2 * F * H * hs, &L.wgu);
-        za(H * F * hs, &L.wdown);
+        za(up256(3 * H) * H * hs, &L.wqkv);
+        za(up256(H) * H * hs, &L.wo);
+        za(up256(2 * F) * H * hs, &L.wgu);
+        za(up256(H) * F * hs, &L.wdown);
         za(H * hs, &L.ln1);
         za(H * hs, &L.ln2);
     }
@@ -486,6 +529,51 @@ cgpt_status cgpt_llm_greedy(cgpt_llm_handle h, const float* first_logits_dev, in
                        step_logits_out_dev ? ld_out : (int64_t)V, st));
     }
     return CGPT_OK;
+}
+
+cgpt_status cgpt_llm_prefill_reserve(cgpt_llm_handle h, int32_t max_rows, int32_t max_prompt_len) {
+    if (!h) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_prefill_reserve: null handle");
+    if (max_rows < 1 || max_rows > h->cfg.max_batch || max_prompt_len < 1 || max_prompt_len > h->cfg.max_len)
+        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_prefill_reserve: rows outside 1..max_batch or prompt length outside 1..max_len");
+    const int64_t rows = ((int64_t)max_rows * max_prompt_len + 255) / 256 * 256;
+    if (rows <= h->p_rows) return CGPT_OK;                 // grows only; a second call with the same sizes does nothing
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t H = h->cfg.hidden, F = h->cfg.mlp, hs = sizeof(half_t);
+    const size_t cols[7] = {H, H, 3 * H, H, H, 2 * F, F};
+    // The larger workspace is built beside the one in use and takes its place only when it is complete: a failure leaves the
+    // handle as it was.  The replaced buffers are NOT freed (they stay in `allocs` until destroy): a graph captured before this
+    // call replays on their addresses.
+    half_t* fresh[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 7 && e == hipSuccess; ++i) {
+        e = hipMalloc((void**)&fresh[i], (size_t)rows * cols[i] * hs);
+        if (e == hipSuccess) e = hipMemset(fresh[i], 0, (size_t)rows * cols[i] * hs);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        for (half_t* p : fresh) (void)hipFree(p);
+        return cgpt_fail(CGPT_ERR_HIP, std::string("cgpt_llm_prefill_reserve: workspace allocation failed -> ") + hipGetErrorString(e));
+    }
+    half_t** bufs[7] = {&h->p_h, &h->p_xn, &h->p_qkv, &h->p_attn, &h->p_proj, &h->p_gu, &h->p_act};
+    for (int i = 0; i < 7; ++i) {
+        *bufs[i] = fresh[i];
+        h->allocs.push_back(fresh[i]);
+    }
+    h->p_rows = rows;
+    return CGPT_OK;
+}
+
+cgpt_status cgpt_llm_prefill(cgpt_llm_handle h, const void* embeds_dev, int32_t B, int32_t L, void* const* k_ptrs_host,
+                             void* const* v_ptrs_host, int64_t kv_len_stride, float* logits_dev, void* stream) {
+    if (!h || !embeds_dev || !logits_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_prefill: null argument");
+    if (L < 1) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_prefill: prompt length must be at least 1");
+    CGCHK(check_cache(h, "cgpt_llm_prefill", B, L - 1, k_ptrs_host, v_ptrs_host, kv_len_stride));
+    CGCHK(ready(h, "cgpt_llm_prefill"));
+    if ((int64_t)B * L > h->p_rows)
+        return cgpt_fail(CGPT_ERR_STATE, "cgpt_llm_prefill: " + std::to_string((int64_t)B * L) + " token rows, the reserved workspace holds " +
+                                             std::to_string(h->p_rows) + " (call cgpt_llm_prefill_reserve outside any capture first)");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    return run_prefill(h, (const half_t*)embeds_dev, B, L, k_ptrs_host, v_ptrs_host, kv_len_stride, logits_dev, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -307,6 +307,25 @@ class _HipDecoder:
                                                  C.c_void_p(logits.data_ptr()), st))
         return logits
 
+    def prefill(self, embs, k_bufs, v_bufs):
+        """The native prefill: embs [B, L, hidden] fp16 -> last-position logits [B, vocab] fp32; rows 0 .. L-1 of every layer's K / V
+        buffer filled in place.  The workspace is reserved here, for `max_batch` rows of this prompt length, so that batches of any
+        size share one reservation (outside any capture: a captured call must come after an eager one of the same prompt length,
+        which `_generate_graph`'s warm-up run is).  A longer prompt later grows it; the library keeps the replaced buffers until the
+        handle goes, so graphs captured before keep replaying on valid memory."""
+        C = self._C
+        B, L, hidden = embs.shape
+        assert (embs.dtype == torch.float16 and embs.device == self.device and embs.is_contiguous() and hidden == self.heads * 128
+                and 1 <= B <= self.max_batch and L >= 1)
+        kp, vp, stride = self._cache_tables(k_bufs, v_bufs, B, L)
+        if not torch.cuda.is_current_stream_capturing():
+            self._lib_mod.check(self.L.cgpt_llm_prefill_reserve(self.handle, self.max_batch, L))
+        logits = torch.empty((B, self.vocab), dtype=torch.float32, device=self.device)
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._lib_mod.check(self.L.cgpt_llm_prefill(self.handle, C.c_void_p(embs.data_ptr()), B, int(L), kp, vp, stride,
+                                                    C.c_void_p(logits.data_ptr()), st))
+        return logits
+
     def greedy(self, first_logits, prompt_len, num_new, min_new, eos_ids, pad_id, k_bufs, v_bufs, return_logits=False):
         """The loop of `greedy_tokens` after the prefill: tokens [B, num_new] int64 (and the logits each arg-max saw)."""
         C = self._C
@@ -337,7 +356,7 @@ class MiniGPT4Classifier:
     noise_laws = ("gaussian", "uniform")       # passed through to encoder.encode_img_noisy
 
     def __init__(self, encoder, llama_model, llama_tokenizer, prompt, label_map, max_new_tokens=20, max_batch=None,
-                 generate_kwargs=None, decode="hf", prefill_linear="torch"):
+                 generate_kwargs=None, decode="hf", prefill_linear="torch", prefill="model"):
         self.encoder = encoder
         self.llama_model = llama_model
         self.llama_tokenizer = llama_tokenizer
@@ -366,17 +385,28 @@ class MiniGPT4Classifier:
         #   (csrc/llm.hip: RMSNorm, decode-shape GEMMs, rotary + K/V append + one-query attention, token select) on the K/V the
         #   prefill wrote, captured into the same kind of graph.  Opt-in; a decoder the kernels do not support is a ValueError here,
         #   never another engine.  Parity: tests/test_gpu_llm_decode.py (teacher-forced logit error against HF's own fp16 error).
+        # prefill = "hip" (with decode = "hip" only; anything else is a ValueError, never silently another engine): the prefill too
+        #   runs in this library (csrc/llm_prefill.hip + the large-shape GEMM): no HF forward, no DynamicCache; `prefill_linear` is
+        #   ignored and no linear is routed.  prefill = "model" (default): the model's own forward, as described above.
+        #   Parity: tests/test_gpu_llm_prefill.py (logits and every cache row against HF's own fp16 error).
         assert decode in ("hf", "graph", "hip") and prefill_linear in ("torch", "cgpt")
+        if prefill not in ("model", "hip"):
+            raise ValueError(f'prefill={prefill!r}: expected "model" or "hip"')
+        if prefill == "hip" and decode != "hip":
+            raise ValueError(f'prefill="hip" needs decode="hip" (got decode={decode!r}): the native prefill feeds the native token steps')
         self.decode = decode
+        self.prefill = prefill
         self.prefill_linear = prefill_linear
         self._hip = _HipDecoder(llama_model, self.max_batch) if decode == "hip" else None
-        self.routed_linears = _LinearRoute.install(llama_model) if (decode in ("graph", "hip") and prefill_linear == "cgpt") else 0
+        self.routed_linears = (_LinearRoute.install(llama_model)
+                               if (decode in ("graph", "hip") and prefill_linear == "cgpt" and prefill == "model") else 0)
         import collections
         self._graphs = collections.OrderedDict()            # LRU of captured decode graphs, see _generate_graph
         self.max_graphs = 4
         self._eos_mask = None
         self.decode_stats = {"graph_replays": 0, "graph_captures": 0, "graph_evictions": 0, "hf_calls": 0, "hf_fallback_kwargs": 0,
-                             "hip_steps": 0}                      # token steps enqueued on the native engine (decode = "hip")
+                             "hip_steps": 0,                      # token steps enqueued on the native engine (decode = "hip")
+                             "hip_prefills": 0}                   # native prefills enqueued (prefill = "hip"), counted alike
 
     # ---- nn.Module-shaped surface used by Smooth (smoothing.py:42,71)
     def eval(self):
@@ -548,6 +578,16 @@ class MiniGPT4Classifier:
         pad = getattr(llm.config, "pad_token_id", None) if pad is None else pad
         pad = (eos_ids[0] if eos_ids else 0) if pad is None else pad
         B, L, _ = embs.shape
+        if self.prefill == "hip":                                      # the whole decode in this library: no HF forward, no DynamicCache
+            assert B <= self.max_batch, f"{B} rows > max_batch {self.max_batch} (the native decoder's workspace)"
+            shape = (B, self._hip.heads, L + self.max_new_tokens, 128)    # what PreallocLayer allocates on the other path
+            k_bufs = [embs.new_empty(shape) for _ in range(self._hip.layers)]
+            v_bufs = [embs.new_empty(shape) for _ in range(self._hip.layers)]
+            logits = self._hip.prefill(embs.contiguous(), k_bufs, v_bufs)
+            self.decode_stats["hip_prefills"] += 1
+            self.decode_stats["hip_steps"] += self.max_new_tokens - 1
+            return self._hip.greedy(logits, L, self.max_new_tokens, self.min_new_tokens() if eos_ids else 0, eos_ids, pad,
+                                    k_bufs, v_bufs, return_logits=return_logits)
         cache = DynamicCache(config=llm.config)
         cache.layers = [PreallocLayer(L + self.max_new_tokens) for _ in cache.layers] or cache.layers
         pos = torch.arange(L, device=embs.device).unsqueeze(0)
@@ -586,12 +626,16 @@ class MiniGPT4Classifier:
             return torch.stack(tokens, dim=1), torch.stack(step_logits, dim=1)
         return torch.stack(tokens, dim=1)
 
+    def _graph_key(self, embs):
+        return (embs.shape[0], embs.shape[1], embs.dtype, embs.device.index, self.max_new_tokens, bool(self.routed_linears), self.decode,
+                self.prefill)
+
     def _generate_graph(self, embs):
-        """One captured hipGraph per (batch, prompt length, dtype, device, max_new_tokens, routed prefill, engine), kept in an LRU of
+        """One captured hipGraph per (batch, prompt length, dtype, device, max_new_tokens, routed prefill, engine, prefill engine), kept in an LRU of
         `max_graphs` entries: a graph pins its private pool -- the pre-allocated K / V of every layer plus activations, ~6.7 GB of K / V
         alone at 200 rows x 32 layers x 64 positions -- and ragged last batches or new prompt lengths add entries; the least recently
         used one is dropped (graph and static tensors freed) before a new capture."""
-        key = (embs.shape[0], embs.shape[1], embs.dtype, embs.device.index, self.max_new_tokens, bool(self.routed_linears), self.decode)
+        key = self._graph_key(embs)
         entry = self._graphs.get(key)
         if entry is not None:
             self._graphs.move_to_end(key)
@@ -607,6 +651,7 @@ class MiniGPT4Classifier:
             import contextlib
             route = _LinearRoute.enabled() if self.routed_linears else contextlib.nullcontext()
             hip_steps = self.decode_stats["hip_steps"]                 # counted per replay below, not for warm-up and capture
+            hip_prefills = self.decode_stats["hip_prefills"]
             with route:
                 with torch.cuda.stream(side):                          # warm-up outside the capture (lazy initialisations)
                     self.greedy_tokens(static_in)
@@ -615,6 +660,7 @@ class MiniGPT4Classifier:
                 with torch.cuda.graph(graph):
                     static_out = self.greedy_tokens(static_in)
             self.decode_stats["hip_steps"] = hip_steps
+            self.decode_stats["hip_prefills"] = hip_prefills
             entry = (graph, static_in, static_out)
             self._graphs[key] = entry
             self.decode_stats["graph_captures"] += 1
@@ -624,6 +670,8 @@ class MiniGPT4Classifier:
         self.decode_stats["graph_replays"] += 1
         if self._hip is not None:
             self.decode_stats["hip_steps"] += self.max_new_tokens - 1
+        if self.prefill == "hip":
+            self.decode_stats["hip_prefills"] += 1
         return static_out.clone()
 
     @torch.no_grad()

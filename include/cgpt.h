@@ -310,14 +310,15 @@ cgpt_status cgpt_layernorm(const float* x_dev, int64_t ldx, const float* gamma_d
                            void* y_dev, int64_t ldy, float* y32_dev, int64_t ldy32, int64_t rows, int32_t D,
                            void* stream);
 
-/* ---- LLaMA decode steps (replaces: every forward after the prefill inside `self.llama_model.generate(...)`,
+/* ---- LLaMA decode steps and prefill (replaces: the forwards inside `self.llama_model.generate(...)`,
  *      minigpt_base.py:418-431 -- greedy, one new token per row, K/V cache) ----
  * A decoder is not a cgpt_model: it has its own handle.  Supported architecture (checked by cgpt_llm_create BEFORE any device
  * call): HF LlamaForCausalLM in fp16 -- bias-free linears, RMSNorm, rotate_half rotary with the default (unscaled) rope_theta
  * law, kv_heads == heads (no grouped-query attention), head_dim == 128, hidden == heads * 128, SwiGLU MLP; hidden, mlp and
  * vocab multiples of 64; max_batch <= 256 (one GEMM row tile); max_len <= 8192 (positions the rotary table covers).
- * That is Vicuna-7B / 13B.  The PREFILL stays with the caller (the model's own forward): the step entries work on the caller's
- * K/V buffers in place, layout [B, heads, kv_len_stride, 128] fp16 per layer, rows 0 .. pos-1 filled by the prefill.
+ * That is Vicuna-7B / 13B.  The step entries work on the caller's K/V buffers in place, layout [B, heads, kv_len_stride, 128]
+ * fp16 per layer, rows 0 .. pos-1 filled by the prefill.  The prefill is either the caller's (the model's own forward writes
+ * those rows) or cgpt_llm_prefill: the same layers on B x L token rows in this library's kernels, filling the same buffers.
  * Rounding: where HF's fp16 eager model rounds ("LLaMA decode steps"); split-K partial sums are combined in slice
  * order, so results are bit-identical from launch to launch and a row's result does not depend on the batch around it.
  * All work is enqueued on `stream`; no host sync, no allocation and no host->device copy after create: capturable in a graph
@@ -366,6 +367,25 @@ cgpt_status cgpt_llm_greedy(cgpt_llm_handle h, const float* first_logits_dev, in
                             int32_t min_new, const int64_t* eos_ids_host, int32_t num_eos, int64_t pad_id, void* const* k_ptrs_host,
                             void* const* v_ptrs_host, int64_t kv_len_stride, int64_t* tokens_out_dev, float* step_logits_out_dev,
                             void* stream);
+
+/* Workspace of cgpt_llm_prefill for up to max_rows prompts of up to max_prompt_len positions: max_rows x max_prompt_len token rows,
+ * padded to whole 256-row GEMM tiles and zeroed -- residual stream, normalised rows, fused q/k/v, attention output, projection
+ * output, gate/up product, SwiGLU output: (8 hidden + 3 mlp) x 2 bytes per token row, 1.2 GB at 200 x 44 rows of a 7B decoder.
+ * Synchronises and allocates: call it OUTSIDE any stream capture.  Idempotent; grows only (a smaller request changes nothing).
+ * Growth never invalidates an earlier capture: a graph captured on the smaller workspace keeps replaying on it, because replaced
+ * buffers stay allocated until cgpt_llm_destroy (their bytes are the price: reserve once for the largest shape to avoid it).  A
+ * failed growth (CGPT_ERR_HIP) leaves the workspace the handle had.
+ * CGPT_ERR_INVALID for max_rows outside 1..max_batch or max_prompt_len outside 1..max_len. */
+cgpt_status cgpt_llm_prefill_reserve(cgpt_llm_handle h, int32_t max_rows, int32_t max_prompt_len);
+/* The prefill of B prompts of L positions each (no padding, positions 0 .. L-1, causal): embeds_dev is [B, L, hidden] fp16,
+ * contiguous.  Layer l writes its rotated keys and its values to rows 0 .. L-1 of k_ptrs_host[l] / v_ptrs_host[l] (layout and
+ * tables as cgpt_llm_step; no other cache row is written); logits_dev receives the LAST position's logits, [B, vocab] fp32
+ * (fp16-rounded values).  Rounding as the step entries, except that the attention probabilities are rounded to fp16 as the
+ * matrix-core operand of P.V.  Enqueues only: no host sync, no allocation, no host->device copy -- capturable.
+ * CGPT_ERR_STATE while weights are missing or when B x L exceeds the reserved workspace; CGPT_ERR_INVALID for B outside
+ * 1..max_batch, L < 1, L > kv_len_stride, L > max_len or a null table / buffer; all checked before the first launch. */
+cgpt_status cgpt_llm_prefill(cgpt_llm_handle h, const void* embeds_dev, int32_t B, int32_t L, void* const* k_ptrs_host,
+                             void* const* v_ptrs_host, int64_t kv_len_stride, float* logits_dev, void* stream);
 
 #ifdef __cplusplus
 }

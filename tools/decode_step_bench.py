@@ -1,5 +1,6 @@
-"""Device time of the greedy decode of BASELINE configs[2] on the "graph" engine (PyTorch-ROCm steps, cgpt prefill) and on the
-"hip" engine (this library's token steps), interleaved in one process.
+"""Device time of the greedy decode of BASELINE configs[2] on the "graph" engine (PyTorch-ROCm steps, cgpt prefill), on the "hip"
+engine (this library's token steps after the model's own prefill, its linears routed through this library's GEMM) and on
+"hip_native" (decode="hip", prefill="hip": prefill and steps in this library), interleaved in one process.
 
 Vicuna-7B-shaped random-init decoder (no checkpoint exists here; nothing is downloaded), 200 rows, a prompt of 44 positions, 20 new
 tokens.  Per repetition and engine, by HIP events around graph replays:
@@ -62,7 +63,7 @@ def main():
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--engines", default="graph,hip")
+    ap.add_argument("--engines", default="graph,hip,hip_native")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "this benchmark measures device time: it needs the GPU"
     assert 1 <= args.rows <= 256 and args.new >= 2 and args.prompt >= 1
@@ -72,8 +73,9 @@ def main():
     g = torch.Generator(device="cpu").manual_seed(1)
     embs = llm.get_input_embeddings()(torch.randint(3, 32000, (args.rows, args.prompt), generator=g).to(dev))
     tok, lm = WordHashTokenizer(32000), AnswerLabelMap(4, ())
-    clfs = {(e, n): MiniGPT4Classifier(_Rows(args.rows), llm, tok, "<ImageHere>", lm, max_new_tokens=n, max_batch=args.rows, decode=e,
-                                       prefill_linear="cgpt") for e in engines for n in (args.new, 1)}
+    how = {"graph": dict(decode="graph"), "hip": dict(decode="hip", prefill="model"), "hip_native": dict(decode="hip", prefill="hip")}
+    clfs = {(e, n): MiniGPT4Classifier(_Rows(args.rows), llm, tok, "<ImageHere>", lm, max_new_tokens=n, max_batch=args.rows,
+                                       prefill_linear="cgpt", **how[e]) for e in engines for n in (args.new, 1)}
 
     def timed(clf):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -116,6 +118,12 @@ def main():
             "step": max(res["hip"]["step_ms"]) < min(res["graph"]["step_ms"]),
             "generate": max(res["hip"]["generate_ms"]) < min(res["graph"]["generate_ms"])}
         line["rows_with_identical_tokens"] = int((tokens["hip"] == tokens["graph"]).all(dim=1).sum())
+    if "hip" in res and "hip_native" in res:                           # the native prefill against the model's own, same steps after it
+        line["slowest_native_prefill_beats_fastest_model_prefill"] = {
+            "prefill": max(res["hip_native"]["prefill_ms"]) < min(res["hip"]["prefill_ms"]),
+            "generate": max(res["hip_native"]["generate_ms"]) < min(res["hip"]["generate_ms"])}
+        line["rows_with_identical_tokens_native_vs_model_prefill"] = int((tokens["hip_native"] == tokens["hip"]).all(dim=1).sum())
+    line["native_prefills_enqueued"] = sum(c.decode_stats["hip_prefills"] for c in clfs.values())
     print(json.dumps(line))
 
 
