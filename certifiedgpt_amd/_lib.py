@@ -96,6 +96,9 @@ SIGNATURES = {
     "cgpt_llm_greedy": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _P, _I32, _I64, _P, _P, _I64, _P, _P, _P]),
     "cgpt_llm_prefill_reserve": (_I32, [_P, _I32, _I32]),
     "cgpt_llm_prefill": (_I32, [_P, _P, _I32, _I32, _P, _P, _I64, _P, _P]),
+    "cgpt_llm_prefill_ragged": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _I64, _P, _P]),
+    "cgpt_llm_step_ragged": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _I64, _P, _P]),
+    "cgpt_llm_greedy_ragged": (_I32, [_P, _P, _I32, _I32, _P, _I32, _I32, _P, _I32, _I64, _P, _P, _I64, _P, _P, _P]),
 }
 
 _lib = None

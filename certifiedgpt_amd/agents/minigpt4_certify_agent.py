@@ -14,10 +14,17 @@ Config (a plain dict or any mapping; the reference's YAMLs define no smoothing k
     model: {generate: {llama_model: <LOCAL dir>, prompt | question: ..., answers: [...], max_new_tokens: 20},   # optional: full
             #          MiniGPT-4 `generate` as the base classifier (certifiedgpt_amd/minigpt4.py); classes = the answer vocabulary
             #          also: decode: "hf" | "graph" | "hip", prefill_linear: "torch" | "cgpt", prefill: "model" | "hip" (the native
-            #          prefill; needs decode "hip") -- see build_generating_classifier
+            #          prefill; needs decode "hip"), ragged: "hf" | "hip" (rows with different texts on the native engine; needs decode
+            #          and prefill "hip"), prompt_bucket: null | int (with ragged "hip": prompt lengths rounded up to a multiple of it,
+            #          one captured graph per bucket) -- see build_generating_classifier
             mode: vit_head | encode_img, weights: <path to a torch state_dict saved with torch.save> | null, dims: {...},
             partial_weights: false}   # true: load what the checkpoint has on top of the synthetic initialisation
     data:  {num_images: 10, seed: 1234}      # synthetic CLIP-normalised images unless `dataset` is passed to the agent
+
+A dataset item is (image, label) or, for one question per image (VQA), (image, label, question): the prompt is then built from
+`question` as build_generating_classifier builds it from model.generate.question and assigned to the classifier's `prompt` before
+that image's call (images_per_pass: 1 and shard: samples only).  With ragged: "hip" and a prompt_bucket the questions of one
+bucket share one captured graph.
 """
 import json
 import os
@@ -84,6 +91,7 @@ class CertifyLoop:
             from ..smoothing import _world
             group = max(group, 1) * _world(smooth.process_group)[1]
         pending = []
+        grouped = group > 1 or by_image
 
         def flush():
             if not pending:
@@ -101,8 +109,17 @@ class CertifyLoop:
                 emit(idx, label, pred, radius, dt)
             pending.clear()
 
-        for idx, (x, label) in enumerate(dataset):
-            if group > 1 or by_image:
+        for idx, item in enumerate(dataset):
+            if len(item) == 3:                             # (x, label, question): this image's own question
+                if grouped:
+                    raise ValueError("dataset items (x, label, question) carry one question per image: supported with images_per_pass: 1 "
+                                     f"and shard: samples only (got images_per_pass {sm_cfg.get('images_per_pass', 1)}, shard {shard!r}); "
+                                     "a grouping mode runs several images through one classifier call with one prompt")
+                x, label, question = item
+                smooth.base_classifier.prompt = question_prompt(question)
+            else:
+                x, label = item
+            if grouped:
                 pending.append((idx, x, label))
                 if len(pending) == group:
                     flush()
@@ -127,6 +144,13 @@ class CertifyLoop:
         for r0 in radii:   # certified accuracy at radius r: correct and certified radius >= r (README.md:52-59)
             out[f"certified_acc@{r0}"] = sum(r["correct"] * (r["radius"] >= r0) for r in self.records) / n
         return out
+
+
+def question_prompt(question):
+    """The prompt build_generating_classifier gives a bare `question`: one image placeholder, then the question, in the
+    conversation template of the eval agent (minigpt4.prepare_texts)."""
+    from ..minigpt4 import prepare_texts
+    return prepare_texts(["<Img><ImageHere></Img> " + question])[0]
 
 
 def prepare_state_dict(state, expected_names, allow_partial=False):
@@ -163,9 +187,11 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
     causal LM on PyTorch-ROCm, loaded BY LOCAL PATH only (base_model.py:181-247 loads `llama_model` the same way; nothing is
     ever fetched), + the answer vocabulary that defines the classes.
         gen_cfg: {llama_model: <local dir>, prompt: "... <ImageHere> ...", answers: [...], max_new_tokens: 20,
-                  decode: "hf" | "graph" | "hip", prefill_linear: "torch" | "cgpt", prefill: "model" | "hip"}
-                  (decode / prefill_linear / prefill: see MiniGPT4Classifier; prefill "hip" needs decode "hip")"""
-    from ..minigpt4 import MiniGPT4Classifier, prepare_texts
+                  decode: "hf" | "graph" | "hip", prefill_linear: "torch" | "cgpt", prefill: "model" | "hip",
+                  ragged: "hf" | "hip", prompt_bucket: None | int}
+                  (decode / prefill_linear / prefill / ragged / prompt_bucket: see MiniGPT4Classifier; prefill "hip" needs decode
+                  "hip", ragged "hip" needs both, prompt_bucket needs ragged "hip")"""
+    from ..minigpt4 import MiniGPT4Classifier
     from .label_adapter import AnswerLabelMap
     if llama_model is None:
         from transformers import AutoModelForCausalLM
@@ -177,7 +203,7 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
                                                   use_fast=False)
     for p_ in llama_model.parameters():                      # frozen decoder, base_model.py:236-238
         p_.requires_grad = False
-    prompt = gen_cfg.get("prompt") or prepare_texts(["<Img><ImageHere></Img> " + gen_cfg.get("question", "")])[0]
+    prompt = gen_cfg.get("prompt") or question_prompt(gen_cfg.get("question", ""))
     answers = list(gen_cfg.get("answers", ()) or ())
     from .label_adapter import normalize_answer
     distinct = len({normalize_answer(a) for a in answers})
@@ -192,7 +218,8 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
     return MiniGPT4Classifier(encoder, llama_model, tokenizer, prompt, label_map,
                               max_new_tokens=int(gen_cfg.get("max_new_tokens", 20)), max_batch=encoder.max_batch,
                               decode=gen_cfg.get("decode", "hf"), prefill_linear=gen_cfg.get("prefill_linear", "torch"),
-                              prefill=gen_cfg.get("prefill", "model"))
+                              prefill=gen_cfg.get("prefill", "model"), ragged=gen_cfg.get("ragged", "hf"),
+                              prompt_bucket=gen_cfg.get("prompt_bucket"))
 
 
 def build_classifier(model_cfg, num_classes, max_batch, device_index, tokenizer=None, llama_model=None):

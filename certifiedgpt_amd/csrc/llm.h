@@ -41,11 +41,14 @@ hipError_t launch_decode_gemm(int epilogue, const DecodeGemmParams& p, hipStream
 hipError_t launch_prefill_addnorm(const half_t* x, const half_t* delta, int64_t src_mul, int64_t src_add, const half_t* w, int hidden,
                                   float eps, half_t* x_out, half_t* y, int64_t rows, hipStream_t stream);
 // Rotates q in place in qkv [B L, 3 hidden] and writes rotated k and v to rows 0 .. L-1 of Kc / Vc [B, heads, len_stride, 128].
+// starts (device, [B] int32, or null = no padding): row b is left-padded by start[b] positions (clamped into 0 .. L-1); its real
+// tokens sit at buffer positions start[b] .. L-1 and take rotary rows 0 ..; pad positions are not rotated and not written to the cache.
 hipError_t launch_prefill_rope(half_t* qkv, int B, int L, int hidden, int heads, half_t* Kc, half_t* Vc, int64_t len_stride,
-                               const half_t* rope, hipStream_t stream);
+                               const half_t* rope, const int32_t* starts, hipStream_t stream);
 // out[B L, hidden] = causal softmax(q . K^T / sqrt(128)) . V per head, q from qkv (already rotated), K / V rows 0 .. L-1 of the cache.
+// starts as above: row b attends over cache rows start[b] .. p only, walked from start[b]; pad rows of `out` are written as zeros.
 hipError_t launch_prefill_attention(const half_t* qkv, int B, int L, int hidden, int heads, const half_t* Kc, const half_t* Vc,
-                                    int64_t len_stride, half_t* out, hipStream_t stream);
+                                    int64_t len_stride, half_t* out, const int32_t* starts, hipStream_t stream);
 // act[rows, mlp] = fp16(fp16(silu(gate)) * up) from gu [rows, 2 mlp] with gate / up columns interleaved in blocks of 16.
 hipError_t launch_prefill_swiglu(const half_t* gu, int64_t rows, int mlp, half_t* act, hipStream_t stream);
 

@@ -104,9 +104,13 @@ __global__ __launch_bounds__(64) void llm_rope_table_kernel(const float* __restr
 //   K[b, h, pos, :] = k',  V[b, h, pos, :] = v        (the only cache rows written)
 //   out[b, h * 128 ...] = fp16(softmax(q' . K[0..pos] / sqrt(128)) . V[0..pos]),  scores, probabilities and the sum in fp32
 // HBM-bound: a head reads (pos + 1) x 2 x 256 B; a wave instruction covers 4 keys x 256 B in 16-byte lanes.
+// RAGGED (left-padded rows, cgpt_llm_step_ragged): the token sits at buffer position `bufpos` of a row whose first real position is
+// s = starts[b] (clamped into 0 .. smax; smax = the prompt's last buffer position, so that prefill and steps clamp alike).  The head's cache pointers move by s and `pos` stands for bufpos - s: rotary row
+// bufpos - s, keys s .. bufpos walked in groups of four from s -- the unpadded row's operations in the unpadded row's order.
+template <bool RAGGED>
 __global__ __launch_bounds__(64) void llm_attn_kernel(const half_t* __restrict__ qkv, int hidden, int heads, half_t* Kc, half_t* Vc,
-                                                      int64_t len_stride, const half_t* __restrict__ rope, int pos,
-                                                      half_t* __restrict__ out) {
+                                                      int64_t len_stride, const half_t* __restrict__ rope, int bufpos,
+                                                      half_t* __restrict__ out, const int* __restrict__ starts, int smax) {
     extern __shared__ float asmem[];                   // [128] rotated query, [128 + 128] halfs: the new key and value, [pos + 1] scores
     float* qs = asmem;
     half_t* knew = reinterpret_cast<half_t*>(asmem + HD);
@@ -116,8 +120,10 @@ __global__ __launch_bounds__(64) void llm_attn_kernel(const half_t* __restrict__
     const half_t* q = qkv + (int64_t)b * 3 * hidden + h * HD;
     const half_t* k = q + hidden;
     const half_t* v = k + hidden;
-    half_t* Kh = Kc + (int64_t)(b * heads + h) * len_stride * HD;
-    half_t* Vh = Vc + (int64_t)(b * heads + h) * len_stride * HD;
+    const int s = RAGGED ? min(max(starts[b], 0), min(smax, bufpos)) : 0;
+    const int pos = bufpos - s;
+    half_t* Kh = Kc + ((int64_t)(b * heads + h) * len_stride + s) * HD;
+    half_t* Vh = Vc + ((int64_t)(b * heads + h) * len_stride + s) * HD;
 
     {   // lane i owns the rotary pair (i, i + 64)
         const float c = (float)rope[(int64_t)pos * HD + lane], s = (float)rope[(int64_t)pos * HD + 64 + lane];
@@ -294,20 +300,25 @@ cgpt_status gemm(cgpt_llm* m, int epi, const half_t* A, int K, const half_t* W, 
 }
 
 // One token step on rows 0..B-1: tokens -> logits (fp32, row stride ld_logits).
-cgpt_status run_step(cgpt_llm* m, const long long* tokens, int B, int pos, void* const* kp, void* const* vp, int64_t len_stride,
-                     float* logits, int64_t ld_logits, hipStream_t st) {
+// starts (device, or null): per-row left padding, clamped into 0 .. smax, see llm_attn_kernel.
+cgpt_status run_step(cgpt_llm* m, const long long* tokens, int B, int pos, const int32_t* starts, int smax, void* const* kp, void* const* vp,
+                     int64_t len_stride, float* logits, int64_t ld_logits, hipStream_t st) {
     const cgpt_llm_config& c = m->cfg;
     const int H = c.hidden;
     hipLaunchKernelGGL(llm_embed_kernel, dim3(B), dim3(256), 0, st, tokens, m->embed, c.vocab, H, m->h);
     LAUNCHED();
-    const size_t attn_lds = (size_t)(2 * HD + pos + 1) * sizeof(float);
+    const size_t attn_lds = (size_t)(2 * HD + pos + 1) * sizeof(float);      // scores of the longest row a batch can hold
     for (int l = 0; l < c.layers; ++l) {
         const Layer& L = m->layers[l];
         hipLaunchKernelGGL(llm_rmsnorm_kernel, dim3(B), dim3(256), 0, st, m->h, L.ln1, H, c.rms_eps, m->xn);
         LAUNCHED();
         CGCHK(gemm(m, DEC_F16, m->xn, H, L.wqkv, 3 * H, m->qkv, 3 * H, nullptr, B, st));
-        hipLaunchKernelGGL(llm_attn_kernel, dim3(B * c.heads), dim3(64), attn_lds, st, m->qkv, H, c.heads, (half_t*)kp[l], (half_t*)vp[l],
-                           len_stride, m->rope, pos, m->attn);
+        if (starts)
+            hipLaunchKernelGGL(llm_attn_kernel<true>, dim3(B * c.heads), dim3(64), attn_lds, st, m->qkv, H, c.heads, (half_t*)kp[l],
+                               (half_t*)vp[l], len_stride, m->rope, pos, m->attn, starts, smax);
+        else
+            hipLaunchKernelGGL(llm_attn_kernel<false>, dim3(B * c.heads), dim3(64), attn_lds, st, m->qkv, H, c.heads, (half_t*)kp[l],
+                               (half_t*)vp[l], len_stride, m->rope, pos, m->attn, nullptr, 0);
         LAUNCHED();
         CGCHK(gemm(m, DEC_F16_RESID, m->attn, H, L.wo, H, m->h, H, m->h, B, st));
         hipLaunchKernelGGL(llm_rmsnorm_kernel, dim3(B), dim3(256), 0, st, m->h, L.ln2, H, c.rms_eps, m->xn);
@@ -331,8 +342,10 @@ cgpt_status big_gemm(const half_t* A, int K, const half_t* W, int N, half_t* out
 
 // The prefill of B prompts of L positions: embeds [B, L, hidden] -> cache rows 0 .. L-1 of every layer, last-position logits.
 // The residual stream stays fp16 as in HF; a projection's output is added by the NEXT add + RMSNorm pass (`pending`).
-cgpt_status run_prefill(cgpt_llm* m, const half_t* embeds, int B, int L, void* const* kp, void* const* vp, int64_t len_stride,
-                        float* logits, hipStream_t st) {
+// starts (device, or null): row b is left-padded by start[b] positions.  Only the rotary and attention kernels look at it; pad
+// rows pass through the row-independent kernels and GEMMs like any other row (zero embeds stay zeros).
+cgpt_status run_prefill(cgpt_llm* m, const half_t* embeds, int B, int L, const int32_t* starts, void* const* kp, void* const* vp,
+                        int64_t len_stride, float* logits, hipStream_t st) {
     const cgpt_llm_config& c = m->cfg;
     const int H = c.hidden, F = c.mlp;
     const int64_t M = (int64_t)B * L;
@@ -343,8 +356,9 @@ cgpt_status run_prefill(cgpt_llm* m, const half_t* embeds, int B, int L, void* c
         HIPCHK(launch_prefill_addnorm(x, pending, 1, 0, Lw.ln1, H, c.rms_eps, m->p_h, m->p_xn, M, st));
         x = m->p_h;
         CGCHK(big_gemm(m->p_xn, H, Lw.wqkv, 3 * H, m->p_qkv, M, st));
-        HIPCHK(launch_prefill_rope(m->p_qkv, B, L, H, c.heads, (half_t*)kp[l], (half_t*)vp[l], len_stride, m->rope, st));
-        HIPCHK(launch_prefill_attention(m->p_qkv, B, L, H, c.heads, (const half_t*)kp[l], (const half_t*)vp[l], len_stride, m->p_attn, st));
+        HIPCHK(launch_prefill_rope(m->p_qkv, B, L, H, c.heads, (half_t*)kp[l], (half_t*)vp[l], len_stride, m->rope, starts, st));
+        HIPCHK(launch_prefill_attention(m->p_qkv, B, L, H, c.heads, (const half_t*)kp[l], (const half_t*)vp[l], len_stride, m->p_attn, starts,
+                                          st));
         CGCHK(big_gemm(m->p_attn, H, Lw.wo, H, m->p_proj, M, st));
         HIPCHK(launch_prefill_addnorm(m->p_h, m->p_proj, 1, 0, Lw.ln2, H, c.rms_eps, m->p_h, m->p_xn, M, st));
         CGCHK(big_gemm(m->p_xn, H, Lw.wgu, 2 * F, m->p_gu, M, st));
@@ -483,27 +497,43 @@ cgpt_status cgpt_llm_load_weight_f16(cgpt_llm_handle h, const char* name, const 
     return CGPT_OK;
 }
 
-cgpt_status cgpt_llm_step(cgpt_llm_handle h, const int64_t* tokens_dev, int32_t B, int32_t pos, void* const* k_ptrs_host,
-                          void* const* v_ptrs_host, int64_t kv_len_stride, float* logits_dev, void* stream) {
-    if (!h || !tokens_dev || !logits_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_step: null argument");
-    CGCHK(ready(h, "cgpt_llm_step"));
+// The plain and the _ragged entries share one body each: `who` names the entry in messages, starts == null is the plain one.
+static cgpt_status llm_step_entry(const char* who, cgpt_llm_handle h, const int64_t* tokens_dev, int32_t B, int32_t pos,
+                                  const int32_t* starts_dev, void* const* k_ptrs_host, void* const* v_ptrs_host, int64_t kv_len_stride,
+                                  float* logits_dev, void* stream) {
+    if (!h || !tokens_dev || !logits_dev) return cgpt_fail(CGPT_ERR_INVALID, std::string(who) + ": null argument");
+    CGCHK(ready(h, who));
     HIPCHK(hipSetDevice(h->cfg.device));
-    CGCHK(check_cache(h, "cgpt_llm_step", B, pos, k_ptrs_host, v_ptrs_host, kv_len_stride));
-    return run_step(h, (const long long*)tokens_dev, B, pos, k_ptrs_host, v_ptrs_host, kv_len_stride, logits_dev, h->cfg.vocab,
-                    (hipStream_t)stream);
+    CGCHK(check_cache(h, who, B, pos, k_ptrs_host, v_ptrs_host, kv_len_stride));
+    return run_step(h, (const long long*)tokens_dev, B, pos, starts_dev, pos, k_ptrs_host, v_ptrs_host, kv_len_stride, logits_dev,
+                    h->cfg.vocab, (hipStream_t)stream);
 }
 
-cgpt_status cgpt_llm_greedy(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len, int32_t num_new,
-                            int32_t min_new, const int64_t* eos_ids_host, int32_t num_eos, int64_t pad_id, void* const* k_ptrs_host,
-                            void* const* v_ptrs_host, int64_t kv_len_stride, int64_t* tokens_out_dev, float* step_logits_out_dev,
-                            void* stream) {
-    if (!h || !first_logits_dev || !tokens_out_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_greedy: null argument");
+cgpt_status cgpt_llm_step(cgpt_llm_handle h, const int64_t* tokens_dev, int32_t B, int32_t pos, void* const* k_ptrs_host,
+                          void* const* v_ptrs_host, int64_t kv_len_stride, float* logits_dev, void* stream) {
+    return llm_step_entry("cgpt_llm_step", h, tokens_dev, B, pos, nullptr, k_ptrs_host, v_ptrs_host, kv_len_stride, logits_dev, stream);
+}
+
+cgpt_status cgpt_llm_step_ragged(cgpt_llm_handle h, const int64_t* tokens_dev, int32_t B, int32_t pos, const int32_t* starts_dev,
+                                 void* const* k_ptrs_host, void* const* v_ptrs_host, int64_t kv_len_stride, float* logits_dev,
+                                 void* stream) {
+    if (!starts_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_step_ragged: null starts_dev");
+    return llm_step_entry("cgpt_llm_step_ragged", h, tokens_dev, B, pos, starts_dev, k_ptrs_host, v_ptrs_host, kv_len_stride, logits_dev,
+                          stream);
+}
+
+static cgpt_status llm_greedy_entry(const char* who_c, cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len,
+                                    const int32_t* starts_dev, int32_t num_new, int32_t min_new, const int64_t* eos_ids_host,
+                                    int32_t num_eos, int64_t pad_id, void* const* k_ptrs_host, void* const* v_ptrs_host,
+                                    int64_t kv_len_stride, int64_t* tokens_out_dev, float* step_logits_out_dev, void* stream) {
+    const std::string who(who_c);
+    if (!h || !first_logits_dev || !tokens_out_dev) return cgpt_fail(CGPT_ERR_INVALID, who + ": null argument");
     if (num_new < 1 || prompt_len < 1 || min_new < 0 || num_eos < 0 || num_eos > MAX_EOS || (num_eos > 0 && !eos_ids_host))
-        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_greedy: bad lengths (num_new, prompt_len >= 1; at most 8 EOS ids)");
-    CGCHK(ready(h, "cgpt_llm_greedy"));
+        return cgpt_fail(CGPT_ERR_INVALID, who + ": bad lengths (num_new, prompt_len >= 1; at most 8 EOS ids)");
+    CGCHK(ready(h, who_c));
     HIPCHK(hipSetDevice(h->cfg.device));
     // the last step appends at prompt_len + num_new - 2; with num_new == 1 no step runs but the table must still be sane
-    CGCHK(check_cache(h, "cgpt_llm_greedy", B, num_new > 1 ? prompt_len + num_new - 2 : 0, k_ptrs_host, v_ptrs_host,
+    CGCHK(check_cache(h, who_c, B, num_new > 1 ? prompt_len + num_new - 2 : 0, k_ptrs_host, v_ptrs_host,
                       num_new > 1 ? kv_len_stride : 1));
     hipStream_t st = (hipStream_t)stream;
     EosIds eos{};
@@ -525,10 +555,27 @@ cgpt_status cgpt_llm_greedy(cgpt_llm_handle h, const float* first_logits_dev, in
         LAUNCHED();
         if (i + 1 == num_new) break;
         float* next = step_logits_out_dev ? step_logits_out_dev + (int64_t)(i + 1) * V : h->logits;
-        CGCHK(run_step(h, h->tok, B, prompt_len + i, k_ptrs_host, v_ptrs_host, kv_len_stride, next,
+        CGCHK(run_step(h, h->tok, B, prompt_len + i, starts_dev, prompt_len - 1, k_ptrs_host, v_ptrs_host, kv_len_stride, next,
                        step_logits_out_dev ? ld_out : (int64_t)V, st));
     }
     return CGPT_OK;
+}
+
+cgpt_status cgpt_llm_greedy(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len, int32_t num_new,
+                            int32_t min_new, const int64_t* eos_ids_host, int32_t num_eos, int64_t pad_id, void* const* k_ptrs_host,
+                            void* const* v_ptrs_host, int64_t kv_len_stride, int64_t* tokens_out_dev, float* step_logits_out_dev,
+                            void* stream) {
+    return llm_greedy_entry("cgpt_llm_greedy", h, first_logits_dev, B, prompt_len, nullptr, num_new, min_new, eos_ids_host, num_eos, pad_id,
+                            k_ptrs_host, v_ptrs_host, kv_len_stride, tokens_out_dev, step_logits_out_dev, stream);
+}
+
+cgpt_status cgpt_llm_greedy_ragged(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len,
+                                   const int32_t* starts_dev, int32_t num_new, int32_t min_new, const int64_t* eos_ids_host,
+                                   int32_t num_eos, int64_t pad_id, void* const* k_ptrs_host, void* const* v_ptrs_host,
+                                   int64_t kv_len_stride, int64_t* tokens_out_dev, float* step_logits_out_dev, void* stream) {
+    if (!starts_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_greedy_ragged: null starts_dev");
+    return llm_greedy_entry("cgpt_llm_greedy_ragged", h, first_logits_dev, B, prompt_len, starts_dev, num_new, min_new, eos_ids_host,
+                            num_eos, pad_id, k_ptrs_host, v_ptrs_host, kv_len_stride, tokens_out_dev, step_logits_out_dev, stream);
 }
 
 cgpt_status cgpt_llm_prefill_reserve(cgpt_llm_handle h, int32_t max_rows, int32_t max_prompt_len) {
@@ -563,17 +610,33 @@ cgpt_status cgpt_llm_prefill_reserve(cgpt_llm_handle h, int32_t max_rows, int32_
     return CGPT_OK;
 }
 
-cgpt_status cgpt_llm_prefill(cgpt_llm_handle h, const void* embeds_dev, int32_t B, int32_t L, void* const* k_ptrs_host,
-                             void* const* v_ptrs_host, int64_t kv_len_stride, float* logits_dev, void* stream) {
-    if (!h || !embeds_dev || !logits_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_prefill: null argument");
-    if (L < 1) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_prefill: prompt length must be at least 1");
-    CGCHK(check_cache(h, "cgpt_llm_prefill", B, L - 1, k_ptrs_host, v_ptrs_host, kv_len_stride));
-    CGCHK(ready(h, "cgpt_llm_prefill"));
+static cgpt_status llm_prefill_entry(const char* who_c, cgpt_llm_handle h, const void* embeds_dev, int32_t B, int32_t L,
+                                     const int32_t* starts_dev, void* const* k_ptrs_host, void* const* v_ptrs_host,
+                                     int64_t kv_len_stride, float* logits_dev, void* stream) {
+    const std::string who(who_c);
+    if (!h || !embeds_dev || !logits_dev) return cgpt_fail(CGPT_ERR_INVALID, who + ": null argument");
+    if (L < 1) return cgpt_fail(CGPT_ERR_INVALID, who + ": prompt length must be at least 1");
+    CGCHK(check_cache(h, who_c, B, L - 1, k_ptrs_host, v_ptrs_host, kv_len_stride));
+    CGCHK(ready(h, who_c));
     if ((int64_t)B * L > h->p_rows)
-        return cgpt_fail(CGPT_ERR_STATE, "cgpt_llm_prefill: " + std::to_string((int64_t)B * L) + " token rows, the reserved workspace holds " +
+        return cgpt_fail(CGPT_ERR_STATE, who + ": " + std::to_string((int64_t)B * L) + " token rows, the reserved workspace holds " +
                                              std::to_string(h->p_rows) + " (call cgpt_llm_prefill_reserve outside any capture first)");
     HIPCHK(hipSetDevice(h->cfg.device));
-    return run_prefill(h, (const half_t*)embeds_dev, B, L, k_ptrs_host, v_ptrs_host, kv_len_stride, logits_dev, (hipStream_t)stream);
+    return run_prefill(h, (const half_t*)embeds_dev, B, L, starts_dev, k_ptrs_host, v_ptrs_host, kv_len_stride, logits_dev,
+                       (hipStream_t)stream);
+}
+
+cgpt_status cgpt_llm_prefill(cgpt_llm_handle h, const void* embeds_dev, int32_t B, int32_t L, void* const* k_ptrs_host,
+                             void* const* v_ptrs_host, int64_t kv_len_stride, float* logits_dev, void* stream) {
+    return llm_prefill_entry("cgpt_llm_prefill", h, embeds_dev, B, L, nullptr, k_ptrs_host, v_ptrs_host, kv_len_stride, logits_dev, stream);
+}
+
+cgpt_status cgpt_llm_prefill_ragged(cgpt_llm_handle h, const void* embeds_dev, int32_t B, int32_t L, const int32_t* starts_dev,
+                                    void* const* k_ptrs_host, void* const* v_ptrs_host, int64_t kv_len_stride, float* logits_dev,
+                                    void* stream) {
+    if (!starts_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_prefill_ragged: null starts_dev");
+    return llm_prefill_entry("cgpt_llm_prefill_ragged", h, embeds_dev, B, L, starts_dev, k_ptrs_host, v_ptrs_host, kv_len_stride,
+                             logits_dev, stream);
 }
 
 }  // extern "C"

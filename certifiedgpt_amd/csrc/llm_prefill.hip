@@ -4,6 +4,10 @@
 //
 // Reference call replaced: the first forward inside `self.llama_model.generate(...)` (minigpt_base.py:418-431), HF
 // LlamaForCausalLM on B prompts of L positions each (no padding, positions 0 .. L-1).  Token row r = b * L + p everywhere.
+// Left-padded prompts (cgpt_llm_prefill_ragged): a device array starts[B] gives each row's number of pad positions; the rotary and
+// attention kernels have a RAGGED instantiation that works in row-relative coordinates -- the row's q / k / v, cache and output
+// pointers moved by start[b], the same arithmetic on len[b] = L - start[b] positions -- so a padded row performs the operations of
+// the unpadded run in the same order.  The plain instantiation reads no starts and compiles to the code it was before.
 // Every kernel rounds where HF's fp16 eager model rounds; the one documented difference is the attention
 // probabilities, which are rounded to fp16 as the MFMA operand of P.V.  Plain vector stores, no atomics, fixed summation orders:
 // a row's result does not depend on the rows around it or on the launch.
@@ -71,22 +75,30 @@ __global__ __launch_bounds__(256) void llm_prefill_addnorm_kernel(const half_t* 
 
 // Rotary + cache write, one thread per (token row, head, 8 rotary pairs): q is rotated in place in the fused projection row, the
 // rotated k and the v go to cache row p of (b, head).  The arithmetic is llm_attn_kernel's head: x' = x cos + rotate_half(x) sin,
-// each product and the sum rounded to fp16.
+// each product and the sum rounded to fp16.  RAGGED: the rotary angle of buffer position p is table row p - start[b] (start clamped
+// into 0 .. L-1); pad positions p < start[b] are left alone -- q is not rotated, their cache rows are NOT written.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void llm_prefill_rope_kernel(half_t* __restrict__ qkv, int64_t rows, int L, int hidden, int heads,
                                                                half_t* __restrict__ Kc, half_t* __restrict__ Vc, int64_t len_stride,
-                                                               const half_t* __restrict__ rope) {
+                                                               const half_t* __restrict__ rope, const int* __restrict__ starts) {
     const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (id >= rows * heads * 8) return;
     const int c8 = (int)(id & 7) * 8;
     const int h = (int)((id >> 3) % heads);
     const int64_t r = (id >> 3) / heads;
     const int b = (int)(r / L), p = (int)(r % L);
+    int rp = p;                                              // row of the rotary table
+    if (RAGGED) {
+        const int s = min(max(starts[b], 0), L - 1);
+        if (p < s) return;
+        rp = p - s;
+    }
     half_t* q = qkv + r * 3 * hidden + h * HD + c8;
     half_t* k = q + hidden;
     const half_t* v = k + hidden;
     const int64_t crow = ((int64_t)(b * heads + h) * len_stride + p) * HD + c8;
-    const h16x8 cs = *reinterpret_cast<const h16x8*>(rope + (int64_t)p * HD + c8);
-    const h16x8 sn = *reinterpret_cast<const h16x8*>(rope + (int64_t)p * HD + 64 + c8);
+    const h16x8 cs = *reinterpret_cast<const h16x8*>(rope + (int64_t)rp * HD + c8);
+    const h16x8 sn = *reinterpret_cast<const h16x8*>(rope + (int64_t)rp * HD + 64 + c8);
     const h16x8 q0 = *reinterpret_cast<const h16x8*>(q), q1 = *reinterpret_cast<const h16x8*>(q + 64);
     const h16x8 k0 = *reinterpret_cast<const h16x8*>(k), k1 = *reinterpret_cast<const h16x8*>(k + 64);
     h16x8 qa, qb, ka, kb;
@@ -116,11 +128,18 @@ __global__ __launch_bounds__(256) void llm_prefill_rope_kernel(half_t* __restric
 //   P.V: the lane's 8 probabilities, rounded to fp16, ARE the A fragment of q = lane & 15 with the MFMA's k slot (g, j) standing
 //       for key 4 g + j (j < 4) or 16 + 4 g + j - 4; the B fragment reads V^T[dim][the same keys] from LDS, 8 MFMAs per 32 keys.
 // Queries at or past L (last block) are computed on clamped rows and not stored; keys at or past L or above the query are masked.
+// RAGGED: query and key indices are relative to s = start[b] (clamped into 0 .. L-1) and L stands for len = L - s, so the 64-key
+// chunks and 32-key blocks begin at the row's first real token: fully padded chunks cost nothing and the summation order of a row is
+// the unpadded run's.  Pad queries are never computed (key 0 of the relative walk is visible to every query that is); the block
+// whose grid index covers buffer positions below s writes those rows of the output as zeros, and a block past the row's last real
+// query leaves before the first barrier (block-uniform).
 constexpr int AQ = 64, AKC = 64, AKP = HD + 8, AVP = AKC + 8;
 
-__global__ __launch_bounds__(256) void llm_prefill_attn_kernel(const half_t* __restrict__ qkv, int L, int hidden, int heads,
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void llm_prefill_attn_kernel(const half_t* __restrict__ qkv, int Lbuf, int hidden, int heads,
                                                                const half_t* __restrict__ Kc, const half_t* __restrict__ Vc,
-                                                               int64_t len_stride, half_t* __restrict__ out) {
+                                                               int64_t len_stride, half_t* __restrict__ out,
+                                                               const int* __restrict__ starts) {
     __shared__ __attribute__((aligned(16))) half_t ks[AKC * AKP];
     __shared__ __attribute__((aligned(16))) half_t vt[HD * AVP];
     const int b = blockIdx.x / heads, h = blockIdx.x % heads;
@@ -128,14 +147,26 @@ __global__ __launch_bounds__(256) void llm_prefill_attn_kernel(const half_t* __r
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r15 = lane & 15, g = lane >> 4;
     const int q0 = qbase + wave * 16;                       // wave-uniform
-    const half_t* Kh = Kc + (int64_t)(b * heads + h) * len_stride * HD;
-    const half_t* Vh = Vc + (int64_t)(b * heads + h) * len_stride * HD;
+    int s = 0;
+    if (RAGGED) {
+        s = min(max(starts[b], 0), Lbuf - 1);
+        for (int i = tid; i < AQ * 16; i += 256) {           // pad query rows among buffer positions qbase .. qbase + 63: zeros
+            const int row = qbase + (i >> 4);
+            if (row < s)
+                *reinterpret_cast<h16x8*>(out + ((int64_t)b * Lbuf + row) * hidden + h * HD + (i & 15) * 8) = h16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        }
+        if (qbase >= Lbuf - s) return;
+    }
+    const int L = Lbuf - s;                                  // real positions; everything below is relative to the first of them
+    const int64_t row0 = (int64_t)b * Lbuf + s;
+    const half_t* Kh = Kc + ((int64_t)(b * heads + h) * len_stride + s) * HD;
+    const half_t* Vh = Vc + ((int64_t)(b * heads + h) * len_stride + s) * HD;
 
     // B fragments of the wave's 16 queries: Q[q0 + r15][32 d + 8 g ..]
     h16x8 qf[4];
     {
         const int qrow = min(q0 + r15, L - 1);
-        const half_t* qp = qkv + ((int64_t)b * L + qrow) * 3 * hidden + h * HD + 8 * g;
+        const half_t* qp = qkv + (row0 + qrow) * 3 * hidden + h * HD + 8 * g;
 #pragma unroll
         for (int d = 0; d < 4; ++d) qf[d] = *reinterpret_cast<const h16x8*>(qp + 32 * d);
     }
@@ -186,7 +217,7 @@ __global__ __launch_bounds__(256) void llm_prefill_attn_kernel(const half_t* __r
             }
             bmax = fmaxf(bmax, __shfl_xor(bmax, 16));
             bmax = fmaxf(bmax, __shfl_xor(bmax, 32));
-            // key 0 is visible to every query, so from the first block on the running maximum is finite
+            // (relative) key 0 is visible to every query, so from the first block on the running maximum is finite
             const float mnew = fmaxf(mrun, bmax);
             const float alpha = expf(mrun - mnew);
             float psum = 0.0f;
@@ -225,7 +256,7 @@ __global__ __launch_bounds__(256) void llm_prefill_attn_kernel(const half_t* __r
     for (int r = 0; r < 4; ++r) {
         const int q = q0 + 4 * g + r;
         if (q >= L) continue;
-        half_t* orow = out + ((int64_t)b * L + q) * hidden + h * HD + r15;
+        half_t* orow = out + (row0 + q) * hidden + h * HD + r15;
 #pragma unroll
         for (int t = 0; t < 8; ++t) orow[16 * t] = (half_t)(o[t][r] / lr[r]);
     }
@@ -261,19 +292,28 @@ hipError_t launch_prefill_addnorm(const half_t* x, const half_t* delta, int64_t 
 }
 
 hipError_t launch_prefill_rope(half_t* qkv, int B, int L, int hidden, int heads, half_t* Kc, half_t* Vc, int64_t len_stride,
-                               const half_t* rope, hipStream_t stream) {
+                               const half_t* rope, const int32_t* starts, hipStream_t stream) {
     if (B < 1 || L < 1 || L > len_stride || hidden != heads * HD || !qkv || !Kc || !Vc || !rope) return hipErrorInvalidValue;
     const int64_t rows = (int64_t)B * L, threads = rows * heads * 8;
-    hipLaunchKernelGGL(llm_prefill_rope_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, qkv, rows, L, hidden, heads,
-                       Kc, Vc, len_stride, rope);
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    if (starts)
+        hipLaunchKernelGGL(llm_prefill_rope_kernel<true>, grid, dim3(256), 0, stream, qkv, rows, L, hidden, heads, Kc, Vc, len_stride, rope,
+                           starts);
+    else
+        hipLaunchKernelGGL(llm_prefill_rope_kernel<false>, grid, dim3(256), 0, stream, qkv, rows, L, hidden, heads, Kc, Vc, len_stride, rope,
+                           nullptr);
     return hipGetLastError();
 }
 
 hipError_t launch_prefill_attention(const half_t* qkv, int B, int L, int hidden, int heads, const half_t* Kc, const half_t* Vc,
-                                    int64_t len_stride, half_t* out, hipStream_t stream) {
+                                    int64_t len_stride, half_t* out, const int32_t* starts, hipStream_t stream) {
     if (B < 1 || L < 1 || L > len_stride || hidden != heads * HD || !qkv || !Kc || !Vc || !out) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(llm_prefill_attn_kernel, dim3((unsigned)(B * heads), (unsigned)((L + AQ - 1) / AQ)), dim3(256), 0, stream, qkv, L,
-                       hidden, heads, Kc, Vc, len_stride, out);
+    const dim3 grid((unsigned)(B * heads), (unsigned)((L + AQ - 1) / AQ));
+    if (starts)
+        hipLaunchKernelGGL(llm_prefill_attn_kernel<true>, grid, dim3(256), 0, stream, qkv, L, hidden, heads, Kc, Vc, len_stride, out, starts);
+    else
+        hipLaunchKernelGGL(llm_prefill_attn_kernel<false>, grid, dim3(256), 0, stream, qkv, L, hidden, heads, Kc, Vc, len_stride, out,
+                           nullptr);
     return hipGetLastError();
 }
 

@@ -85,6 +85,37 @@ class WordHashTokenizer:
         return " ".join(out)
 
 
+def left_pad_embeds(batch_embs, bucket=None):
+    """Left padding of prompts of different lengths (minigpt_base.py:407-416): `batch_embs` is a list of tensors [n_i, len_i, hidden]
+    (n_i rows that share one length; the reference's loop has n_i = 1) -> (embeds [B, L, hidden] with zeros on the pad positions,
+    attention mask [B, L] int, starts [B] int32 = pad positions per row), B = sum n_i, L = the longest length, rounded up to a
+    multiple of `bucket` when that is set.  Row b's real tokens sit at positions starts[b] .. L-1.  Pure tensor arithmetic on the
+    inputs' device (CPU tensors work); a row with no real token is a ValueError."""
+    if bucket is not None and (isinstance(bucket, bool) or not isinstance(bucket, int) or bucket < 1):
+        raise ValueError(f"bucket={bucket!r}: expected None or an int >= 1")
+    if not batch_embs:
+        raise ValueError("left_pad_embeds: no rows")
+    lens = [int(e.shape[1]) for e in batch_embs]
+    if min(lens) < 1:
+        raise ValueError(f"left_pad_embeds: row group {lens.index(min(lens))} has no real token (length 0)")
+    L = max(lens)
+    if bucket:
+        L = (L + bucket - 1) // bucket * bucket
+    first = batch_embs[0]
+    B = sum(int(e.shape[0]) for e in batch_embs)
+    embs = torch.zeros([B, L, first.shape[2]], dtype=first.dtype, device=first.device)
+    attn_mask = torch.zeros([B, L], dtype=torch.int, device=first.device)
+    starts = torch.empty([B], dtype=torch.int32, device=first.device)
+    row = 0
+    for emb, n in zip(batch_embs, lens):
+        rows = int(emb.shape[0])
+        embs[row:row + rows, L - n:] = emb
+        attn_mask[row:row + rows, L - n:] = 1
+        starts[row:row + rows] = L - n
+        row += rows
+    return embs, attn_mask, starts
+
+
 def greedy_decode_parity(hf_tokens, hf_scores, tokens, eps):
     """Compare a greedy decode `tokens` [B, n] with HF `generate`'s `hf_tokens` [B, <= n] row by row, given HF's per-step processed
     scores `hf_scores` [B, steps, V] (fp32).  Two greedy decoders of the SAME fp16 model can only part ways at a step where HF's own
@@ -295,24 +326,37 @@ class _HipDecoder:
         vp = (C.c_void_p * self.layers)(*[t.data_ptr() for t in v_bufs])
         return kp, vp, stride
 
-    def step(self, tokens, pos, k_bufs, v_bufs):
-        """One teacher-forced step: tokens [B] int64 at position `pos` -> logits [B, vocab] fp32; K / V row `pos` appended in place."""
+    def _starts_ptr(self, starts, B):
+        """`starts` [B] int32 on the handle's device (pad positions per row of a left-padded batch; the kernels read it when they run,
+        so a captured call sees its contents at every replay) -> the pointer the _ragged entries take."""
+        assert (starts.dtype == torch.int32 and starts.device == self.device and starts.is_contiguous()
+                and tuple(starts.shape) == (B,)), (tuple(starts.shape), starts.dtype, starts.device)
+        return self._C.c_void_p(starts.data_ptr())
+
+    def step(self, tokens, pos, k_bufs, v_bufs, starts=None):
+        """One teacher-forced step: tokens [B] int64 at position `pos` -> logits [B, vocab] fp32; K / V row `pos` appended in place.
+        starts (or None: the plain entry): left-padded rows, `pos` is the position in the padded buffer."""
         C = self._C
         B = int(tokens.shape[0])
         assert tokens.dtype == torch.int64 and tokens.device == self.device and tokens.is_contiguous() and 1 <= B <= self.max_batch
         kp, vp, stride = self._cache_tables(k_bufs, v_bufs, B, int(pos) + 1)
         logits = torch.empty((B, self.vocab), dtype=torch.float32, device=self.device)
         st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._lib_mod.check(self.L.cgpt_llm_step(self.handle, C.c_void_p(tokens.data_ptr()), B, int(pos), kp, vp, stride,
-                                                 C.c_void_p(logits.data_ptr()), st))
+        if starts is None:
+            self._lib_mod.check(self.L.cgpt_llm_step(self.handle, C.c_void_p(tokens.data_ptr()), B, int(pos), kp, vp, stride,
+                                                     C.c_void_p(logits.data_ptr()), st))
+        else:
+            self._lib_mod.check(self.L.cgpt_llm_step_ragged(self.handle, C.c_void_p(tokens.data_ptr()), B, int(pos),
+                                                            self._starts_ptr(starts, B), kp, vp, stride, C.c_void_p(logits.data_ptr()), st))
         return logits
 
-    def prefill(self, embs, k_bufs, v_bufs):
+    def prefill(self, embs, k_bufs, v_bufs, starts=None):
         """The native prefill: embs [B, L, hidden] fp16 -> last-position logits [B, vocab] fp32; rows 0 .. L-1 of every layer's K / V
         buffer filled in place.  The workspace is reserved here, for `max_batch` rows of this prompt length, so that batches of any
         size share one reservation (outside any capture: a captured call must come after an eager one of the same prompt length,
         which `_generate_graph`'s warm-up run is).  A longer prompt later grows it; the library keeps the replaced buffers until the
-        handle goes, so graphs captured before keep replaying on valid memory."""
+        handle goes, so graphs captured before keep replaying on valid memory.
+        starts (or None: the plain entry): row b is left-padded by starts[b] positions; cache rows starts[b] .. L-1 are filled."""
         C = self._C
         B, L, hidden = embs.shape
         assert (embs.dtype == torch.float16 and embs.device == self.device and embs.is_contiguous() and hidden == self.heads * 128
@@ -322,12 +366,18 @@ class _HipDecoder:
             self._lib_mod.check(self.L.cgpt_llm_prefill_reserve(self.handle, self.max_batch, L))
         logits = torch.empty((B, self.vocab), dtype=torch.float32, device=self.device)
         st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._lib_mod.check(self.L.cgpt_llm_prefill(self.handle, C.c_void_p(embs.data_ptr()), B, int(L), kp, vp, stride,
-                                                    C.c_void_p(logits.data_ptr()), st))
+        if starts is None:
+            self._lib_mod.check(self.L.cgpt_llm_prefill(self.handle, C.c_void_p(embs.data_ptr()), B, int(L), kp, vp, stride,
+                                                        C.c_void_p(logits.data_ptr()), st))
+        else:
+            self._lib_mod.check(self.L.cgpt_llm_prefill_ragged(self.handle, C.c_void_p(embs.data_ptr()), B, int(L),
+                                                               self._starts_ptr(starts, B), kp, vp, stride,
+                                                               C.c_void_p(logits.data_ptr()), st))
         return logits
 
-    def greedy(self, first_logits, prompt_len, num_new, min_new, eos_ids, pad_id, k_bufs, v_bufs, return_logits=False):
-        """The loop of `greedy_tokens` after the prefill: tokens [B, num_new] int64 (and the logits each arg-max saw)."""
+    def greedy(self, first_logits, prompt_len, num_new, min_new, eos_ids, pad_id, k_bufs, v_bufs, return_logits=False, starts=None):
+        """The loop of `greedy_tokens` after the prefill: tokens [B, num_new] int64 (and the logits each arg-max saw).
+        starts (or None: the plain entry): the prefill's left padding; `prompt_len` is then the padded length."""
         C = self._C
         B, V = first_logits.shape
         assert (first_logits.dtype == torch.float32 and first_logits.device == self.device and first_logits.is_contiguous()
@@ -337,9 +387,13 @@ class _HipDecoder:
         steps = torch.empty((B, num_new, V), dtype=torch.float32, device=self.device) if return_logits else None
         eos = (C.c_int64 * max(1, len(eos_ids)))(*[int(e) for e in eos_ids])
         st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._lib_mod.check(self.L.cgpt_llm_greedy(
-            self.handle, C.c_void_p(first_logits.data_ptr()), B, int(prompt_len), int(num_new), int(min_new), eos, len(eos_ids),
-            int(pad_id), kp, vp, stride, C.c_void_p(tokens.data_ptr()), C.c_void_p(steps.data_ptr()) if return_logits else None, st))
+        tail = (int(num_new), int(min_new), eos, len(eos_ids), int(pad_id), kp, vp, stride, C.c_void_p(tokens.data_ptr()),
+                C.c_void_p(steps.data_ptr()) if return_logits else None, st)
+        if starts is None:
+            self._lib_mod.check(self.L.cgpt_llm_greedy(self.handle, C.c_void_p(first_logits.data_ptr()), B, int(prompt_len), *tail))
+        else:
+            self._lib_mod.check(self.L.cgpt_llm_greedy_ragged(self.handle, C.c_void_p(first_logits.data_ptr()), B, int(prompt_len),
+                                                              self._starts_ptr(starts, B), *tail))
         return (tokens, steps) if return_logits else tokens
 
 
@@ -351,12 +405,18 @@ class MiniGPT4Classifier:
        :param llama_tokenizer: its tokenizer (`__call__(text, return_tensors="pt", add_special_tokens=...)`, `decode`)
        :param prompt: the text every noisy copy is asked, containing one `<ImageHere>`
        :param label_map: `AnswerLabelMap` -- frozen when torch.distributed is initialised (see label_adapter.py)
+       :param ragged: "hf" (default) | "hip" -- who decodes a call whose rows carry DIFFERENT texts (left padding + mask); see __init__
+       :param prompt_bucket: None | int >= 1 (with ragged="hip") -- padded prompt lengths are rounded up to a multiple of it
+
+    `prompt` is a plain attribute: assigning a new prompt between two images (`clf.prompt = ...`) is the supported way to ask a
+    per-image question (VQA: one question per image).  Under decode="graph" / "hip" every new prompt LENGTH captures a graph of its
+    own; with ragged="hip", prompt_bucket=k all prompts whose length rounds up to the same multiple of k replay one graph.
     """
 
     noise_laws = ("gaussian", "uniform")       # passed through to encoder.encode_img_noisy
 
     def __init__(self, encoder, llama_model, llama_tokenizer, prompt, label_map, max_new_tokens=20, max_batch=None,
-                 generate_kwargs=None, decode="hf", prefill_linear="torch", prefill="model"):
+                 generate_kwargs=None, decode="hf", prefill_linear="torch", prefill="model", ragged="hf", prompt_bucket=None):
         self.encoder = encoder
         self.llama_model = llama_model
         self.llama_tokenizer = llama_tokenizer
@@ -389,13 +449,34 @@ class MiniGPT4Classifier:
         #   runs in this library (csrc/llm_prefill.hip + the large-shape GEMM): no HF forward, no DynamicCache; `prefill_linear` is
         #   ignored and no linear is routed.  prefill = "model" (default): the model's own forward, as described above.
         #   Parity: tests/test_gpu_llm_prefill.py (logits and every cache row against HF's own fp16 error).
+        # ragged = "hip" (with decode = "hip" AND prefill = "hip" only; anything else is a ValueError): rows with different texts are
+        #   left-padded as the reference pads them (minigpt_base.py:407-416) and run through the native engine's _ragged entries with
+        #   a per-row start offset held in device memory (include/cgpt.h), from one captured graph per (batch, padded length): no HF
+        #   call.  A padded row's tokens are bit for bit those of the row run alone without padding (tests/test_gpu_llm_ragged.py).
+        #   ragged = "hf" (default): such calls take HF `generate` with the attention mask, as before.
+        # prompt_bucket = k (with ragged = "hip" only): padded lengths are rounded up to a multiple of k, and a SHARED prompt is padded
+        #   the same way (one common start), so prompts of different lengths replay one graph per bucket.  None: shared prompts take
+        #   the unpadded path, unchanged.
         assert decode in ("hf", "graph", "hip") and prefill_linear in ("torch", "cgpt")
         if prefill not in ("model", "hip"):
             raise ValueError(f'prefill={prefill!r}: expected "model" or "hip"')
         if prefill == "hip" and decode != "hip":
             raise ValueError(f'prefill="hip" needs decode="hip" (got decode={decode!r}): the native prefill feeds the native token steps')
+        if ragged not in ("hf", "hip"):
+            raise ValueError(f'ragged={ragged!r}: expected "hf" or "hip"')
+        if ragged == "hip" and (decode != "hip" or prefill != "hip"):
+            raise ValueError(f'ragged="hip" needs decode="hip" and prefill="hip" (got decode={decode!r}, prefill={prefill!r}): '
+                             "left-padded rows run on the native prefill and the native token steps")
+        if prompt_bucket is not None:
+            if isinstance(prompt_bucket, bool) or not isinstance(prompt_bucket, int) or prompt_bucket < 1:
+                raise ValueError(f"prompt_bucket={prompt_bucket!r}: expected None or an int >= 1")
+            if ragged != "hip":
+                raise ValueError(f'prompt_bucket={prompt_bucket} needs ragged="hip" (got ragged={ragged!r}): only the native engine pads '
+                                 "a prompt up to a bucket length")
         self.decode = decode
         self.prefill = prefill
+        self.ragged = ragged
+        self.prompt_bucket = prompt_bucket
         self.prefill_linear = prefill_linear
         self._hip = _HipDecoder(llama_model, self.max_batch) if decode == "hip" else None
         self.routed_linears = (_LinearRoute.install(llama_model)
@@ -442,28 +523,31 @@ class MiniGPT4Classifier:
         dtype = self.embed_tokens(torch.zeros(1, 1, dtype=torch.long, device=img_embeds.device)).dtype
         img_embeds = img_embeds.to(dtype)
         B = img_embeds.shape[0]
-        if isinstance(texts, str) or len(set(texts)) == 1:
+        shared = isinstance(texts, str) or len(set(texts)) == 1
+        # the native engine takes left-padded rows only where it would take a shared prompt: on the device, greedy arguments
+        native_pad = self.ragged == "hip" and img_embeds.is_cuda and self._greedy_defaults()
+        starts = None
+        if shared:
             # shared prompt: segments embedded once and broadcast; equal lengths -> no padding, all-ones mask
             prompt = texts if isinstance(texts, str) else texts[0]
             segs = self._segment_embeddings(prompt, img_embeds.device)
             assert len(segs) == 2, "Unmatched numbers of image placeholders and images."
             embs = torch.cat([segs[0].expand(B, -1, -1), img_embeds, segs[1].expand(B, -1, -1)], dim=1)
-            attn_mask = torch.ones(embs.shape[:2], dtype=torch.int, device=embs.device)
+            if native_pad and self.prompt_bucket:                      # padded up to the bucket: one graph for every length in it
+                embs, attn_mask, starts = left_pad_embeds([embs], self.prompt_bucket)
+            else:
+                attn_mask = torch.ones(embs.shape[:2], dtype=torch.int, device=embs.device)
         else:
             assert len(texts) == B
             batch_embs = [self.get_context_emb(t, [img_embeds[i][None]]) for i, t in enumerate(texts)]
-            max_len = max(e.shape[1] for e in batch_embs)
-            embs = torch.zeros([B, max_len, batch_embs[0].shape[2]], dtype=dtype, device=img_embeds.device)
-            attn_mask = torch.zeros([B, max_len], dtype=torch.int, device=img_embeds.device)
-            for i, emb in enumerate(batch_embs):                       # left padding, minigpt_base.py:413-416
-                embs[i, -emb.shape[1]:] = emb[0]
-                attn_mask[i, -emb.shape[1]:] = 1
-        shared = isinstance(texts, str) or len(set(texts)) == 1
-        if self.decode in ("graph", "hip") and shared and embs.is_cuda and self._greedy_defaults():
-            outputs = self._generate_graph(embs)
+            embs, attn_mask, starts = left_pad_embeds(batch_embs, self.prompt_bucket if native_pad else None)     # minigpt_base.py:407-416
+            if not native_pad:
+                starts = None
+        if self.decode in ("graph", "hip") and (shared or native_pad) and embs.is_cuda and self._greedy_defaults():
+            outputs = self._generate_graph(embs, starts)
         else:
             self.decode_stats["hf_calls"] += 1
-            if self.decode in ("graph", "hip") and shared and embs.is_cuda:
+            if self.decode in ("graph", "hip") and (shared or self.ragged == "hip") and embs.is_cuda:
                 self.decode_stats["hf_fallback_kwargs"] += 1            # generation arguments outside the greedy whitelist
             outputs = self.llama_model.generate(inputs_embeds=embs, attention_mask=attn_mask, max_new_tokens=self.max_new_tokens,
                                                 **self.hf_generate_kwargs())
@@ -539,11 +623,13 @@ class MiniGPT4Classifier:
         kw["min_length"] = 0
         return kw
 
-    def greedy_tokens(self, embs, return_logits=False):
+    def greedy_tokens(self, embs, return_logits=False, starts=None):
         """What `generate(inputs_embeds=embs, attention_mask=ones, max_new_tokens=n, do_sample=False, min_length=1, ...)` returns for
         prompts without padding, as a straight loop of the model's own forward calls: [B, n] token ids, pad_token_id after a row's
         EOS.  (HF additionally stops, and truncates, at the step where every row has finished; the extra columns here are pad ids,
-        which decode to nothing.)  No data-dependent control flow: capturable as one graph."""
+        which decode to nothing.)  No data-dependent control flow: capturable as one graph.
+        starts ([B] int32 on the device, prefill = "hip" only): row b of `embs` is left-padded by starts[b] positions (zeros); the
+        result is what each row gives without its padding."""
         from transformers import DynamicCache
         from transformers.cache_utils import DynamicLayer
 
@@ -578,16 +664,17 @@ class MiniGPT4Classifier:
         pad = getattr(llm.config, "pad_token_id", None) if pad is None else pad
         pad = (eos_ids[0] if eos_ids else 0) if pad is None else pad
         B, L, _ = embs.shape
+        assert starts is None or self.prefill == "hip", 'left-padded rows need prefill="hip"'
         if self.prefill == "hip":                                      # the whole decode in this library: no HF forward, no DynamicCache
             assert B <= self.max_batch, f"{B} rows > max_batch {self.max_batch} (the native decoder's workspace)"
             shape = (B, self._hip.heads, L + self.max_new_tokens, 128)    # what PreallocLayer allocates on the other path
             k_bufs = [embs.new_empty(shape) for _ in range(self._hip.layers)]
             v_bufs = [embs.new_empty(shape) for _ in range(self._hip.layers)]
-            logits = self._hip.prefill(embs.contiguous(), k_bufs, v_bufs)
+            logits = self._hip.prefill(embs.contiguous(), k_bufs, v_bufs, starts=starts)
             self.decode_stats["hip_prefills"] += 1
             self.decode_stats["hip_steps"] += self.max_new_tokens - 1
             return self._hip.greedy(logits, L, self.max_new_tokens, self.min_new_tokens() if eos_ids else 0, eos_ids, pad,
-                                    k_bufs, v_bufs, return_logits=return_logits)
+                                    k_bufs, v_bufs, return_logits=return_logits, starts=starts)
         cache = DynamicCache(config=llm.config)
         cache.layers = [PreallocLayer(L + self.max_new_tokens) for _ in cache.layers] or cache.layers
         pos = torch.arange(L, device=embs.device).unsqueeze(0)
@@ -626,16 +713,19 @@ class MiniGPT4Classifier:
             return torch.stack(tokens, dim=1), torch.stack(step_logits, dim=1)
         return torch.stack(tokens, dim=1)
 
-    def _graph_key(self, embs):
-        return (embs.shape[0], embs.shape[1], embs.dtype, embs.device.index, self.max_new_tokens, bool(self.routed_linears), self.decode,
-                self.prefill)
+    def _graph_key(self, embs, ragged=False):
+        key = (embs.shape[0], embs.shape[1], embs.dtype, embs.device.index, self.max_new_tokens, bool(self.routed_linears), self.decode,
+               self.prefill)
+        return key + ("ragged",) if ragged else key                   # a graph of the _ragged entries is never an unpadded one's
 
-    def _generate_graph(self, embs):
+    def _generate_graph(self, embs, starts=None):
         """One captured hipGraph per (batch, prompt length, dtype, device, max_new_tokens, routed prefill, engine, prefill engine), kept in an LRU of
         `max_graphs` entries: a graph pins its private pool -- the pre-allocated K / V of every layer plus activations, ~6.7 GB of K / V
         alone at 200 rows x 32 layers x 64 positions -- and ragged last batches or new prompt lengths add entries; the least recently
-        used one is dropped (graph and static tensors freed) before a new capture."""
-        key = self._graph_key(embs)
+        used one is dropped (graph and static tensors freed) before a new capture.
+        starts (left-padded rows, see greedy_tokens): the graph is captured on a static copy that is refreshed before every replay, like
+        the embeds -- the kernels read it when they run, so one graph per (batch, PADDED length) serves every mix of prompt lengths."""
+        key = self._graph_key(embs, ragged=starts is not None)
         entry = self._graphs.get(key)
         if entry is not None:
             self._graphs.move_to_end(key)
@@ -646,6 +736,7 @@ class MiniGPT4Classifier:
                 self.decode_stats["graph_evictions"] += 1
                 torch.cuda.empty_cache()                                # return the evicted graph's pool before capturing again
             static_in = embs.clone()
+            static_starts = None if starts is None else starts.clone()
             side = torch.cuda.Stream(device=embs.device)
             side.wait_stream(torch.cuda.current_stream())
             import contextlib
@@ -654,18 +745,20 @@ class MiniGPT4Classifier:
             hip_prefills = self.decode_stats["hip_prefills"]
             with route:
                 with torch.cuda.stream(side):                          # warm-up outside the capture (lazy initialisations)
-                    self.greedy_tokens(static_in)
+                    self.greedy_tokens(static_in, starts=static_starts)
                 torch.cuda.current_stream().wait_stream(side)
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
-                    static_out = self.greedy_tokens(static_in)
+                    static_out = self.greedy_tokens(static_in, starts=static_starts)
             self.decode_stats["hip_steps"] = hip_steps
             self.decode_stats["hip_prefills"] = hip_prefills
-            entry = (graph, static_in, static_out)
+            entry = (graph, static_in, static_out, static_starts)
             self._graphs[key] = entry
             self.decode_stats["graph_captures"] += 1
-        graph, static_in, static_out = entry
+        graph, static_in, static_out, static_starts = entry
         static_in.copy_(embs)
+        if static_starts is not None:
+            static_starts.copy_(starts)
         graph.replay()
         self.decode_stats["graph_replays"] += 1
         if self._hip is not None:

@@ -387,6 +387,32 @@ cgpt_status cgpt_llm_prefill_reserve(cgpt_llm_handle h, int32_t max_rows, int32_
 cgpt_status cgpt_llm_prefill(cgpt_llm_handle h, const void* embeds_dev, int32_t B, int32_t L, void* const* k_ptrs_host,
                              void* const* v_ptrs_host, int64_t kv_len_stride, float* logits_dev, void* stream);
 
+/* ---- Left-padded prompts: the three entries above with a per-row start offset ----
+ * starts_dev is a DEVICE array of B int32.  Row b of a batch padded to L positions has start[b] pad positions at buffer positions
+ * 0 .. start[b]-1 and its len[b] = L - start[b] >= 1 real tokens at start[b] .. L-1 (HF's left padding: the first real token sits at
+ * rotary position 0).  The kernels clamp start[b] into 0 .. L-1 (cgpt_llm_step_ragged, which is not told L: 0 .. pos): the host cannot check device
+ * contents without a sync.  They work in row-relative coordinates -- the row's q / k / v, cache and output pointers moved by
+ * start[b], the plain entries' arithmetic on len[b] positions -- so a padded row's logits, tokens and cache rows
+ * start[b] .. are bit for bit those of the same row run unpadded through the plain entries (cache rows 0 ..).
+ * Cache rows written: the prefill writes rows start[b] .. L-1 of row b, a step at `pos` writes row `pos`; rows below start[b] are
+ * NEVER written or read.  embeds_dev holds all B x L rows; pad rows go through the row-independent kernels and GEMMs like any other
+ * row (the price of left padding), so their embeds must be finite (zeros stay zeros); pad rows of the attention output are zeros.
+ * starts_dev is read when the kernels RUN, not when the call enqueues: a captured graph sees the array's current contents at each
+ * replay, so one graph per (B, L) serves every mix of prompt lengths.  All three calls of one decode must see the same contents.
+ * Same contracts as the plain entries (enqueue only, capturable, CGPT_ERR_STATE / CGPT_ERR_INVALID rules, all checks before the
+ * first launch; the workspace is cgpt_llm_prefill_reserve's, for B x L rows), plus CGPT_ERR_INVALID for a null starts_dev.
+ * cgpt_llm_greedy_ragged: prompt_len is the PADDED length L; its steps run at buffer positions L, L + 1, ... */
+cgpt_status cgpt_llm_prefill_ragged(cgpt_llm_handle h, const void* embeds_dev, int32_t B, int32_t L, const int32_t* starts_dev,
+                                    void* const* k_ptrs_host, void* const* v_ptrs_host, int64_t kv_len_stride, float* logits_dev,
+                                    void* stream);
+cgpt_status cgpt_llm_step_ragged(cgpt_llm_handle h, const int64_t* tokens_dev, int32_t B, int32_t pos, const int32_t* starts_dev,
+                                 void* const* k_ptrs_host, void* const* v_ptrs_host, int64_t kv_len_stride, float* logits_dev,
+                                 void* stream);
+cgpt_status cgpt_llm_greedy_ragged(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len,
+                                   const int32_t* starts_dev, int32_t num_new, int32_t min_new, const int64_t* eos_ids_host,
+                                   int32_t num_eos, int64_t pad_id, void* const* k_ptrs_host, void* const* v_ptrs_host,
+                                   int64_t kv_len_stride, int64_t* tokens_out_dev, float* step_logits_out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,16 @@ tokens.  Per repetition and engine, by HIP events around graph replays:
     prefill_ms   = the same classifier with max_new_tokens = 1 (prefill + 1 select, no step)
     steps_ms     = generate_ms - prefill_ms  (the 19 steps and their selects), step_ms = steps_ms / 19
 Prints ONE JSON line.  The floor quoted beside it is bytes / copy rate: the decoder's weight bytes plus the mean K / V bytes a step
-reads, over 6.3 TB/s (the copy rate the box reaches)."""
+reads, over 6.3 TB/s (the copy rate the box reaches).
+
+--ragged runs the left-padding leg instead (ragged="hip"), same protocol, every engine decode="hip", prefill="hip":
+    plain       the shared prompt of --prompt positions on the plain entries (today's path)
+    bucketed    the same prompt left-padded to --bucket-len positions (one common start): the cost of the pad rows
+    ragged      rows of lengths --ragged-min .. --bucket-len (fixed seed), left-padded to --bucket-len -- the SAME captured graph as
+                `bucketed`, other contents of the starts tensor
+    hf_ragged   today's fallback for those rows: eager HF `generate` with the attention mask (generate_ms only)
+    parent      `plain` on another build of the library (--parent-lib PATH, e.g. the parent commit's libcgpt.so), loaded beside
+                the product in this process: the claim to check is that the plain path's time is unchanged"""
 import argparse
 import json
 import os
@@ -55,6 +64,107 @@ def _clock():
         return f"unavailable ({type(e).__name__})"
 
 
+def _other_library(path):
+    """Context: `_lib.lib()` answers with the build at `path` (entries it lacks stay unbound), so a decoder created inside binds it."""
+    import contextlib
+    import ctypes as C
+    from certifiedgpt_amd import _lib
+
+    @contextlib.contextmanager
+    def ctx():
+        _lib.lib()
+        other = C.CDLL(path)
+        for name, (res, argtypes) in _lib.SIGNATURES.items():
+            if hasattr(other, name):
+                fn = getattr(other, name)
+                fn.restype, fn.argtypes = res, argtypes
+        saved, _lib._lib = _lib._lib, other
+        try:
+            yield
+        finally:
+            _lib._lib = saved
+    return ctx()
+
+
+def ragged_leg(args, llm, embs, tok, lm):
+    from certifiedgpt_amd.minigpt4 import left_pad_embeds
+    dev, Lb, rows = embs.device, args.bucket_len, args.rows
+    assert args.prompt <= Lb and 1 <= args.ragged_min <= Lb
+
+    def build(n, **kw):
+        return MiniGPT4Classifier(_Rows(rows), llm, tok, "<ImageHere>", lm, max_new_tokens=n, max_batch=rows, decode="hip", prefill="hip", **kw)
+
+    clfs = {("plain", n): build(n) for n in (args.new, 1)}
+    clfs.update({("padded", n): build(n, ragged="hip", prompt_bucket=Lb) for n in (args.new, 1)})
+    legs = ["plain", "bucketed", "ragged", "hf_ragged"]
+    if args.parent_lib:
+        with _other_library(args.parent_lib):
+            clfs.update({("parent", n): build(n) for n in (args.new, 1)})
+        legs.append("parent")
+    g = torch.Generator(device="cpu").manual_seed(2)
+    lens = torch.randint(args.ragged_min, Lb + 1, (rows,), generator=g).tolist()
+    wide = llm.get_input_embeddings()(torch.randint(3, 32000, (rows, Lb), generator=g).to(dev))
+    b_embs, _, b_starts = left_pad_embeds([embs], Lb)
+    r_embs, r_mask, r_starts = left_pad_embeds([wide[i:i + 1, Lb - n:] for i, n in enumerate(lens)], Lb)
+    hf_kw = clfs[("plain", args.new)].hf_generate_kwargs()
+    inputs = {"plain": (embs, None), "parent": (embs, None), "bucketed": (b_embs, b_starts), "ragged": (r_embs, r_starts)}
+    which = {"plain": "plain", "parent": "parent", "bucketed": "padded", "ragged": "padded"}
+
+    def timed(leg, n):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        if leg == "hf_ragged":
+            out = llm.generate(inputs_embeds=r_embs, attention_mask=r_mask, max_new_tokens=n, **hf_kw)
+        else:
+            out = clfs[(which[leg], n)]._generate_graph(*inputs[leg])
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b), out
+
+    clock_before = _clock()
+    res = {e: {"generate_ms": [], "prefill_ms": []} for e in legs}
+    tokens = {}
+    with torch.no_grad():
+        for rep_i in range(args.warmup + args.reps):                   # interleaved: leg by leg inside every repetition
+            for e in legs:
+                t, out = timed(e, args.new)
+                tp = timed(e, 1)[0]
+                print(f"decode_step_bench: repetition {rep_i} {e} generate {t:.1f} ms prefill {tp:.1f} ms", file=sys.stderr, flush=True)
+                if rep_i >= args.warmup:
+                    res[e]["generate_ms"].append(t)
+                    res[e]["prefill_ms"].append(tp)
+                    tokens[e] = out
+    clock_after = _clock()
+    steps = args.new - 1
+    for r in res.values():
+        r["step_ms"] = [(gm - pm) / steps for gm, pm in zip(r["generate_ms"], r["prefill_ms"])]
+        for k in ("generate_ms", "prefill_ms", "step_ms"):
+            r[k + "_min_max"] = [min(r[k]), max(r[k])]
+    padded = clfs[("padded", args.new)].decode_stats
+
+    def overlap(a, b, k):
+        (a0, a1), (b0, b1) = res[a][k + "_min_max"], res[b][k + "_min_max"]
+        return a0 <= b1 and b0 <= a1
+
+    def med(e, k):
+        return sorted(res[e][k])[len(res[e][k]) // 2]
+
+    line = {"tool": "decode_step_bench", "leg": "ragged", "rows": rows, "prompt": args.prompt, "bucket_len": Lb,
+            "ragged_lengths_min_max_mean": [min(lens), max(lens), sum(lens) / len(lens)], "new_tokens": args.new, "layers": args.layers,
+            "reps": args.reps, "warmup": args.warmup, "engines": res,
+            "bucketed_over_plain_median": {k: med("bucketed", k) / med("plain", k) for k in ("prefill_ms", "step_ms", "generate_ms")},
+            "token_rows_ratio": Lb / args.prompt,
+            "ragged_over_hf_ragged_generate_median": med("ragged", "generate_ms") / med("hf_ragged", "generate_ms"),
+            "padded_graph_captures_replays": [padded["graph_captures"], padded["graph_replays"]],      # bucketed and ragged share ONE graph
+            "bucketed_rows_with_plain_tokens": int((tokens["bucketed"] == tokens["plain"]).all(dim=1).sum()),
+            "shader_clock_mhz_before_after": [clock_before, clock_after], "device": torch.cuda.get_device_name(0)}
+    if "parent" in res:
+        line["parent_lib"] = os.path.basename(args.parent_lib)
+        line["plain_and_parent_ranges_overlap"] = {k: overlap("plain", "parent", k) for k in ("prefill_ms", "step_ms", "generate_ms")}
+        line["plain_rows_with_parent_tokens"] = int((tokens["plain"] == tokens["parent"]).all(dim=1).sum())
+    print(json.dumps(line))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=200)
@@ -64,6 +174,10 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--engines", default="graph,hip,hip_native")
+    ap.add_argument("--ragged", action="store_true", help="the left-padding leg (see the module docstring)")
+    ap.add_argument("--bucket-len", type=int, default=48)
+    ap.add_argument("--ragged-min", type=int, default=38)
+    ap.add_argument("--parent-lib", default=None, help="another build of libcgpt.so for the plain-path A/B of --ragged")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "this benchmark measures device time: it needs the GPU"
     assert 1 <= args.rows <= 256 and args.new >= 2 and args.prompt >= 1
@@ -73,6 +187,8 @@ def main():
     g = torch.Generator(device="cpu").manual_seed(1)
     embs = llm.get_input_embeddings()(torch.randint(3, 32000, (args.rows, args.prompt), generator=g).to(dev))
     tok, lm = WordHashTokenizer(32000), AnswerLabelMap(4, ())
+    if args.ragged:
+        return ragged_leg(args, llm, embs, tok, lm)
     how = {"graph": dict(decode="graph"), "hip": dict(decode="hip", prefill="model"), "hip_native": dict(decode="hip", prefill="hip")}
     clfs = {(e, n): MiniGPT4Classifier(_Rows(args.rows), llm, tok, "<ImageHere>", lm, max_new_tokens=n, max_batch=args.rows,
                                        prefill_linear="cgpt", **how[e]) for e in engines for n in (args.new, 1)}
