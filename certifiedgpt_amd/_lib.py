@@ -38,8 +38,13 @@ class LlmConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32), ("device", C.c_int32), ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32),
         ("kv_heads", C.c_int32), ("head_dim", C.c_int32), ("mlp", C.c_int32), ("vocab", C.c_int32), ("rms_eps", C.c_float),
-        ("rope_theta", C.c_float), ("max_batch", C.c_int32), ("max_len", C.c_int32),
+        ("rope_theta", C.c_float), ("max_batch", C.c_int32), ("max_len", C.c_int32), ("weight_format", C.c_int32),
     ]
+
+
+LLM_WEIGHT_FORMATS = {"fp16": 0, "int8": 1}   # CGPT_LLM_W_F16, CGPT_LLM_W_INT8
+# sizeof(cgpt_llm_config) before weight_format existed: still accepted by cgpt_llm_create (fp16), and what older builds expect
+LLM_CONFIG_SIZE_F16 = LlmConfig.weight_format.offset
 
 
 # (name, restype, argtypes) of every symbol include/cgpt.h declares
@@ -92,6 +97,7 @@ SIGNATURES = {
     "cgpt_llm_create": (_I32, [C.POINTER(LlmConfig), C.POINTER(_P)]),
     "cgpt_llm_destroy": (_I32, [_P]),
     "cgpt_llm_load_weight_f16": (_I32, [_P, C.c_char_p, _P, _I64, _P]),
+    "cgpt_llm_weight_bytes": (_I32, [_P, C.POINTER(_I64)]),
     "cgpt_llm_step": (_I32, [_P, _P, _I32, _I32, _P, _P, _I64, _P, _P]),
     "cgpt_llm_greedy": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _P, _I32, _I64, _P, _P, _I64, _P, _P, _P]),
     "cgpt_llm_prefill_reserve": (_I32, [_P, _I32, _I32]),

@@ -190,7 +190,9 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
                   decode: "hf" | "graph" | "hip", prefill_linear: "torch" | "cgpt", prefill: "model" | "hip",
                   ragged: "hf" | "hip", prompt_bucket: None | int}
                   (decode / prefill_linear / prefill / ragged / prompt_bucket: see MiniGPT4Classifier; prefill "hip" needs decode
-                  "hip", ragged "hip" needs both, prompt_bucket needs ragged "hip")"""
+                  "hip", ragged "hip" needs both, prompt_bucket needs ragged "hip"); weights: "fp16" | "int8" (the native engine's
+                  layer linears as row-wise absmax int8, the weight law of the reference's low_resource: true; needs decode and
+                  prefill "hip")"""
     from ..minigpt4 import MiniGPT4Classifier
     from .label_adapter import AnswerLabelMap
     if llama_model is None:
@@ -219,7 +221,7 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
                               max_new_tokens=int(gen_cfg.get("max_new_tokens", 20)), max_batch=encoder.max_batch,
                               decode=gen_cfg.get("decode", "hf"), prefill_linear=gen_cfg.get("prefill_linear", "torch"),
                               prefill=gen_cfg.get("prefill", "model"), ragged=gen_cfg.get("ragged", "hf"),
-                              prompt_bucket=gen_cfg.get("prompt_bucket"))
+                              prompt_bucket=gen_cfg.get("prompt_bucket"), weights=gen_cfg.get("weights", "fp16"))
 
 
 def build_classifier(model_cfg, num_classes, max_batch, device_index, tokenizer=None, llama_model=None):

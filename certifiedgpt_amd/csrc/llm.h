@@ -32,7 +32,9 @@ size_t decode_gemm_slab_bytes(int N, int K);                // workspace the sha
 // Allows the kernels their 80 KiB of dynamic LDS on the CURRENT device.  Call once per device before the first launch, outside any
 // stream capture (cgpt_llm_create does): launch_decode_gemm itself then only launches.
 hipError_t decode_gemm_prepare();
-hipError_t launch_decode_gemm(int epilogue, const DecodeGemmParams& p, hipStream_t stream);
+// wscale != null: W points at the row-wise absmax int8 matrix q[N, K] (ldw in int8 elements) and wscale at its N fp16 row scales;
+// the product is bit for bit that of the fp16 call on W'[n, k] = fp16(q[n, k]) * wscale[n] (one fp16 multiply).  Not with DEC_F32.
+hipError_t launch_decode_gemm(int epilogue, const DecodeGemmParams& p, hipStream_t stream, const half_t* wscale = nullptr);
 
 // ------------------------------------------------------------------------------------- prefill (llm_prefill.hip)
 // Token row r = b * L + p of B prompts of L positions.  All fp16, rows `hidden` (or 3 hidden / 2 mlp / mlp) elements apart.

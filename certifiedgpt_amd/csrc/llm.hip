@@ -10,7 +10,14 @@
 // llm_gemm.hip; the rest is here.  Every kernel rounds where HF's fp16 eager model rounds: what is left between
 // the two is summation order.  Nothing here synchronises, allocates or copies from the host after cgpt_llm_create, so a whole
 // greedy loop can be captured into one graph.
+//
+// int8 handles (cgpt_llm_config.weight_format = CGPT_LLM_W_INT8): the seven layer linears are held as row-wise
+// absmax int8 with one fp16 scale per row (llm_quant_rows_kernel, at load).  The token step reads them through the int8-weight
+// instantiation of the decode GEMM; the prefill expands each matrix into ONE fp16 scratch matrix right before its GEMM
+// (llm_dequant_kernel, same stream).  Both form W' = fp16(q) * s with one fp16 multiply, so every result is bit for bit that of
+// an fp16 handle loaded with W'.
 #include <math.h>
+#include <stddef.h>
 #include <string.h>
 
 #include <set>
@@ -193,6 +200,70 @@ __global__ __launch_bounds__(64) void llm_attn_kernel(const half_t* __restrict__
     }
 }
 
+typedef signed char i8x16 __attribute__((ext_vector_type(16)));
+
+// The weight law of an int8 handle, one workgroup per source row of an HF nn.Linear.weight [rows, K] in fp16:
+//   s = fp16(absmax / 127)           the maximum is exact in any order; the division is fp32, correctly rounded
+//   q = clamp(rint(w / s), -127, 127)   fp32 division, round to nearest even; s == 0 (a zero row, or an underflow): q = 0
+// Row r goes to row r of the destination (interleave < 0) or to row 32 (r / 16) + 16 interleave + r % 16 (gate / up fusion):
+// a row keeps its scale.  16 values per thread and pass: 16-byte stores.
+__global__ __launch_bounds__(256) void llm_quant_rows_kernel(const half_t* __restrict__ w, int K, int interleave,
+                                                             signed char* __restrict__ q, half_t* __restrict__ scales) {
+    __shared__ float wmax[4];
+    const int r = blockIdx.x;
+    const int dr = interleave < 0 ? r : 32 * (r / 16) + 16 * interleave + (r % 16);
+    const h16x8* src = reinterpret_cast<const h16x8*>(w + (int64_t)r * K);
+    float amax = 0.0f;
+    for (int i = threadIdx.x; i < K / 8; i += 256) {
+        const h16x8 v = src[i];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf((float)v[e]));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = amax;
+    __syncthreads();
+    amax = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    const half_t sh = (half_t)__fdiv_rn(amax, 127.0f);
+    const float sf = (float)sh;
+    if (threadIdx.x == 0) scales[dr] = sh;
+    i8x16* dst = reinterpret_cast<i8x16*>(q + (int64_t)dr * K);
+    for (int i = threadIdx.x; i < K / 16; i += 256) {
+        const h16x8 lo = src[2 * i], hi = src[2 * i + 1];
+        i8x16 o;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const float x = (float)(e < 8 ? lo[e] : hi[e - 8]);
+            const float t = fminf(fmaxf(rintf(__fdiv_rn(x, sf)), -127.0f), 127.0f);
+            o[e] = sf == 0.0f ? (signed char)0 : (signed char)(int)t;
+        }
+        dst[i] = o;
+    }
+}
+
+// out[n, k] = fp16(q[n, k]) * s[n] (ONE fp16 multiply; the conversion is exact) for the rows_padded x K int8 matrix of an int8
+// handle: the prefill's expansion into the handle's fp16 scratch.  Pad rows hold q = 0 and s = 0 and come out as zeros.
+// One thread per 16 values: a 16-byte load, two 16-byte stores.
+__global__ __launch_bounds__(256) void llm_dequant_kernel(const signed char* __restrict__ q, const half_t* __restrict__ scales, int K,
+                                                          int64_t chunks, half_t* __restrict__ out) {
+    const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (id >= chunks) return;
+    const int per_row = K / 16;
+    const half_t s = scales[id / per_row];
+    const i8x16 v = reinterpret_cast<const i8x16*>(q)[id];
+    h16x8 lo, hi;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        lo[e] = (half_t)(short)v[e];
+        hi[e] = (half_t)(short)v[e + 8];
+    }
+    lo = lo * s;
+    hi = hi * s;
+    asm volatile("" : "+v"(lo), "+v"(hi));                 // the products stay values of their own
+    reinterpret_cast<h16x8*>(out)[2 * id] = lo;
+    reinterpret_cast<h16x8*>(out)[2 * id + 1] = hi;
+}
+
 struct EosIds { long long id[MAX_EOS]; int n; };
 
 // Greedy bookkeeping of one step, one workgroup per row (greedy_tokens in minigpt4.py): EOS columns read as -inf while
@@ -239,8 +310,15 @@ __global__ __launch_bounds__(256) void llm_select_kernel(const float* src, int64
     }
 }
 
+// One fused layer matrix [up256(N)][K]: fp16 (`w`) on an fp16 handle; int8 `q` with one fp16 scale per row (`s`) on an int8 handle.
+struct Mat {
+    half_t* w = nullptr;
+    signed char* q = nullptr;
+    half_t* s = nullptr;
+};
 struct Layer {
-    half_t *wqkv = nullptr, *wo = nullptr, *wgu = nullptr, *wdown = nullptr, *ln1 = nullptr, *ln2 = nullptr;
+    Mat wqkv, wo, wgu, wdown;
+    half_t *ln1 = nullptr, *ln2 = nullptr;
 };
 
 }  // namespace
@@ -260,6 +338,9 @@ struct cgpt_llm {
     // stays allocated (in `allocs`) until destroy: a graph captured earlier still holds its addresses.
     int64_t p_rows = 0;
     half_t *p_h = nullptr, *p_xn = nullptr, *p_qkv = nullptr, *p_attn = nullptr, *p_proj = nullptr, *p_gu = nullptr, *p_act = nullptr;
+    // int8 handles: the prefill's ONE fp16 expansion of the layer matrix its next GEMM reads (stream order makes one enough)
+    half_t* scratch = nullptr;
+    int64_t weight_bytes = 0;              // matrices, scales and scratch, as allocated (cgpt_llm_weight_bytes)
 };
 
 namespace {
@@ -290,12 +371,13 @@ cgpt_status check_cache(cgpt_llm* m, const char* who, int B, int last_pos, void*
 
 #define LAUNCHED() HIPCHK(hipGetLastError())
 
-cgpt_status gemm(cgpt_llm* m, int epi, const half_t* A, int K, const half_t* W, int N, void* out, int64_t ldo, const half_t* resid,
+cgpt_status gemm(cgpt_llm* m, int epi, const half_t* A, int K, const Mat& W, int N, void* out, int64_t ldo, const half_t* resid,
                  int B, hipStream_t st) {
     DecodeGemmParams p{};
-    p.A = A; p.lda = K; p.W = W; p.ldw = K; p.out = out; p.ldo = ldo; p.resid = resid; p.ldr = ldo; p.slabs = m->slabs;
+    p.A = A; p.lda = K; p.W = W.q ? reinterpret_cast<const half_t*>(W.q) : W.w; p.ldw = K; p.out = out; p.ldo = ldo; p.resid = resid;
+    p.ldr = ldo; p.slabs = m->slabs;
     p.M = B; p.N = N; p.K = K;
-    HIPCHK(launch_decode_gemm(epi, p, st));
+    HIPCHK(launch_decode_gemm(epi, p, st, W.q ? W.s : nullptr));
     return CGPT_OK;
 }
 
@@ -328,11 +410,20 @@ cgpt_status run_step(cgpt_llm* m, const long long* tokens, int B, int pos, const
     }
     hipLaunchKernelGGL(llm_rmsnorm_kernel, dim3(B), dim3(256), 0, st, m->h, m->norm, H, c.rms_eps, m->xn);
     LAUNCHED();
-    return gemm(m, DEC_F32, m->xn, H, m->lm_head, c.vocab, logits, ld_logits, nullptr, B, st);
+    return gemm(m, DEC_F32, m->xn, H, Mat{m->lm_head}, c.vocab, logits, ld_logits, nullptr, B, st);
 }
 
 // C[M, N] = A[M, K] * W[N, K]^T, fp16 result of the fp32 sum, through the large-shape GEMM of the ViT (gemm.hip / gemm9.hip).
-cgpt_status big_gemm(const half_t* A, int K, const half_t* W, int N, half_t* out, int64_t M, hipStream_t st) {
+// On an int8 handle the matrix is first expanded into the handle's scratch (all up256(N) rows, pad rows zeros), on the same stream:
+// the expansion of the next matrix is ordered behind this GEMM, so one scratch serves every layer.
+cgpt_status big_gemm(cgpt_llm* m, const half_t* A, int K, const Mat& Wm, int N, half_t* out, int64_t M, hipStream_t st) {
+    const half_t* W = Wm.w;
+    if (Wm.q) {
+        const int64_t chunks = (int64_t)((N + 255) / 256 * 256) * (K / 16);
+        hipLaunchKernelGGL(llm_dequant_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st, Wm.q, Wm.s, K, chunks, m->scratch);
+        HIPCHK(hipGetLastError());
+        W = m->scratch;
+    }
     GemmParams p{};
     p.A = A; p.lda = K; p.W = W; p.ldw = K; p.bias = nullptr; p.out = out; p.ldo = N; p.aux = nullptr; p.ldaux = 0;
     p.M = (int)M; p.N = N; p.K = K; p.patches = 0;
@@ -355,20 +446,20 @@ cgpt_status run_prefill(cgpt_llm* m, const half_t* embeds, int B, int L, const i
         const Layer& Lw = m->layers[l];
         HIPCHK(launch_prefill_addnorm(x, pending, 1, 0, Lw.ln1, H, c.rms_eps, m->p_h, m->p_xn, M, st));
         x = m->p_h;
-        CGCHK(big_gemm(m->p_xn, H, Lw.wqkv, 3 * H, m->p_qkv, M, st));
+        CGCHK(big_gemm(m, m->p_xn, H, Lw.wqkv, 3 * H, m->p_qkv, M, st));
         HIPCHK(launch_prefill_rope(m->p_qkv, B, L, H, c.heads, (half_t*)kp[l], (half_t*)vp[l], len_stride, m->rope, starts, st));
         HIPCHK(launch_prefill_attention(m->p_qkv, B, L, H, c.heads, (const half_t*)kp[l], (const half_t*)vp[l], len_stride, m->p_attn, starts,
                                           st));
-        CGCHK(big_gemm(m->p_attn, H, Lw.wo, H, m->p_proj, M, st));
+        CGCHK(big_gemm(m, m->p_attn, H, Lw.wo, H, m->p_proj, M, st));
         HIPCHK(launch_prefill_addnorm(m->p_h, m->p_proj, 1, 0, Lw.ln2, H, c.rms_eps, m->p_h, m->p_xn, M, st));
-        CGCHK(big_gemm(m->p_xn, H, Lw.wgu, 2 * F, m->p_gu, M, st));
+        CGCHK(big_gemm(m, m->p_xn, H, Lw.wgu, 2 * F, m->p_gu, M, st));
         HIPCHK(launch_prefill_swiglu(m->p_gu, M, F, m->p_act, st));
-        CGCHK(big_gemm(m->p_act, F, Lw.wdown, H, m->p_proj, M, st));
+        CGCHK(big_gemm(m, m->p_act, F, Lw.wdown, H, m->p_proj, M, st));
         pending = m->p_proj;
     }
     // tail, as run_step ends: the last position's row of every prompt (with its pending update) into the step workspace
     HIPCHK(launch_prefill_addnorm(m->p_h, pending, L, L - 1, m->norm, H, c.rms_eps, m->h, m->xn, B, st));
-    return gemm(m, DEC_F32, m->xn, H, m->lm_head, c.vocab, logits, c.vocab, nullptr, B, st);
+    return gemm(m, DEC_F32, m->xn, H, Mat{m->lm_head}, c.vocab, logits, c.vocab, nullptr, B, st);
 }
 
 }  // namespace
@@ -377,9 +468,16 @@ extern "C" {
 
 cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
     if (!cfg || !out) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: null argument");
-    if (cfg->struct_size != (int32_t)sizeof(cgpt_llm_config))
+    // two sizes are valid: the struct up to max_len (callers built before weight_format existed: fp16) and the whole struct
+    constexpr int32_t kOldSize = (int32_t)offsetof(cgpt_llm_config, weight_format);
+    if (cfg->struct_size != (int32_t)sizeof(cgpt_llm_config) && cfg->struct_size != kOldSize)
         return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: cgpt_llm_config.struct_size mismatch (header/library drift)");
-    const cgpt_llm_config& c = *cfg;
+    cgpt_llm_config c{};
+    memcpy(&c, cfg, (size_t)cfg->struct_size);
+    if (cfg->struct_size == kOldSize) c.weight_format = CGPT_LLM_W_F16;
+    c.struct_size = (int32_t)sizeof(cgpt_llm_config);
+    if (c.weight_format != CGPT_LLM_W_F16 && c.weight_format != CGPT_LLM_W_INT8)
+        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: weight_format must be CGPT_LLM_W_F16 (0) or CGPT_LLM_W_INT8 (1)");
     if (c.head_dim != HD) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: head_dim must be 128");
     if (c.heads < 1 || c.kv_heads != c.heads)
         return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: kv_heads must equal heads (no grouped-query attention)");
@@ -405,17 +503,26 @@ cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
     auto fail = [&](cgpt_status s) { cgpt_llm_destroy(m); return s; };
     cgpt_status s = CGPT_OK;
     auto za = [&](size_t bytes, void* out_ptr) { if (s == CGPT_OK) s = dev_zalloc(m, bytes, (void**)out_ptr); };
-    za(V * H * hs, &m->embed);
+    const bool int8 = c.weight_format == CGPT_LLM_W_INT8;
+    auto counted = [&](size_t bytes, void* out_ptr) { za(bytes, out_ptr); m->weight_bytes += (int64_t)bytes; };
+    // a layer matrix [up256(N)][K]: fp16, or int8 with up256(N) fp16 row scales (pad rows: q = 0, s = 0)
+    auto mat = [&](Mat& W, size_t N, size_t K) {
+        if (int8) { counted(up256(N) * K, &W.q); counted(up256(N) * hs, &W.s); }
+        else counted(up256(N) * K * hs, &W.w);
+    };
+    counted(V * H * hs, &m->embed);
     za(H * hs, &m->norm);
-    za(V * H * hs, &m->lm_head);
+    counted(V * H * hs, &m->lm_head);
     for (Layer& L : m->layers) {
-        za(up256(3 * H) * H * hs, &L.wqkv);
-        za(up256(H) * H * hs, &L.wo);
-        za(up256(2 * F) * H * hs, &L.wgu);
-        za(up256(H) * F * hs, &L.wdown);
+        mat(L.wqkv, 3 * H, H);
+        mat(L.wo, H, H);
+        mat(L.wgu, 2 * F, H);
+        mat(L.wdown, H, F);
         za(H * hs, &L.ln1);
         za(H * hs, &L.ln2);
     }
+    if (int8)                                             // the largest fused layer matrix, up256(2 mlp) x hidden at LLaMA's shapes
+        counted(std::max(std::max(up256(3 * H) * H, up256(2 * F) * H), up256(H) * std::max(H, F)) * hs, &m->scratch);
     // activations: whole 256-row tiles (the GEMM stages every row of its tile; rows past the batch hold zeros)
     za(MAX_ROWS * H * hs, &m->h);
     za(MAX_ROWS * H * hs, &m->xn);
@@ -453,6 +560,12 @@ cgpt_status cgpt_llm_destroy(cgpt_llm_handle h) {
     return CGPT_OK;
 }
 
+cgpt_status cgpt_llm_weight_bytes(cgpt_llm_handle h, int64_t* out) {
+    if (!h || !out) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_weight_bytes: null argument");
+    *out = h->weight_bytes;
+    return CGPT_OK;
+}
+
 cgpt_status cgpt_llm_load_weight_f16(cgpt_llm_handle h, const char* name, const void* data_dev, int64_t numel, void* stream) {
     if (!h || !name || !data_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_load_weight_f16: null argument");
     const cgpt_llm_config& c = h->cfg;
@@ -460,7 +573,8 @@ cgpt_status cgpt_llm_load_weight_f16(cgpt_llm_handle h, const char* name, const 
     hipStream_t st = (hipStream_t)stream;
     const std::string n(name);
     half_t* dst = nullptr;
-    int64_t want = 0;
+    const Mat* mat = nullptr;                              // a layer linear: `row0` = its first row in the fused matrix, K = its columns
+    int64_t want = 0, row0 = 0, K = 0;
     int interleave = -1;                                   // 0 = gate, 1 = up: rows go to alternate blocks of 16
     if (n == "model.embed_tokens.weight") { dst = h->embed; want = V * H; }
     else if (n == "model.norm.weight") { dst = h->norm; want = H; }
@@ -471,13 +585,13 @@ cgpt_status cgpt_llm_load_weight_f16(cgpt_llm_handle h, const char* name, const 
             return cgpt_fail(CGPT_ERR_NOT_FOUND, "cgpt_llm_load_weight_f16: unknown weight '" + n + "'");
         const std::string rest(name + used);
         Layer& L = h->layers[li];
-        if (rest == "self_attn.q_proj.weight") { dst = L.wqkv; want = H * H; }
-        else if (rest == "self_attn.k_proj.weight") { dst = L.wqkv + H * H; want = H * H; }
-        else if (rest == "self_attn.v_proj.weight") { dst = L.wqkv + 2 * H * H; want = H * H; }
-        else if (rest == "self_attn.o_proj.weight") { dst = L.wo; want = H * H; }
-        else if (rest == "mlp.gate_proj.weight") { dst = L.wgu; want = F * H; interleave = 0; }
-        else if (rest == "mlp.up_proj.weight") { dst = L.wgu; want = F * H; interleave = 1; }
-        else if (rest == "mlp.down_proj.weight") { dst = L.wdown; want = H * F; }
+        if (rest == "self_attn.q_proj.weight") { mat = &L.wqkv; want = H * H; K = H; }
+        else if (rest == "self_attn.k_proj.weight") { mat = &L.wqkv; row0 = H; want = H * H; K = H; }
+        else if (rest == "self_attn.v_proj.weight") { mat = &L.wqkv; row0 = 2 * H; want = H * H; K = H; }
+        else if (rest == "self_attn.o_proj.weight") { mat = &L.wo; want = H * H; K = H; }
+        else if (rest == "mlp.gate_proj.weight") { mat = &L.wgu; want = F * H; K = H; interleave = 0; }
+        else if (rest == "mlp.up_proj.weight") { mat = &L.wgu; want = F * H; K = H; interleave = 1; }
+        else if (rest == "mlp.down_proj.weight") { mat = &L.wdown; want = H * F; K = F; }
         else if (rest == "input_layernorm.weight") { dst = L.ln1; want = H; }
         else if (rest == "post_attention_layernorm.weight") { dst = L.ln2; want = H; }
         else return cgpt_fail(CGPT_ERR_NOT_FOUND, "cgpt_llm_load_weight_f16: unknown weight '" + n + "'");
@@ -486,6 +600,14 @@ cgpt_status cgpt_llm_load_weight_f16(cgpt_llm_handle h, const char* name, const 
         return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_load_weight_f16: '" + n + "' expects " + std::to_string(want) + " elements, got " +
                                                std::to_string(numel));
     HIPCHK(hipSetDevice(c.device));
+    if (mat && mat->q) {                                   // int8 handle: quantise the caller's rows straight into the fused matrix
+        hipLaunchKernelGGL(llm_quant_rows_kernel, dim3((unsigned)(want / K)), dim3(256), 0, st, (const half_t*)data_dev, (int)K, interleave,
+                           mat->q + row0 * K, mat->s + row0);
+        LAUNCHED();
+        h->loaded.insert(n);
+        return CGPT_OK;
+    }
+    if (mat) dst = mat->w + row0 * K;
     if (interleave < 0) {
         HIPCHK(hipMemcpyAsync(dst, data_dev, (size_t)want * sizeof(half_t), hipMemcpyDeviceToDevice, st));
     } else {                                               // 16 source rows -> rows 32 t + 16 * interleave .. of the fused matrix

@@ -15,6 +15,11 @@
 // stores, and decode_combine_kernel (a second launch: the kernel boundary is the release / acquire) adds slabs 0, 1, 2, ... in
 // that order and applies the epilogue.  The number of slices depends on (N, K) only, so a row's result does not depend on M,
 // on its neighbours, or on the launch.
+//
+// W8 (the second template parameter, int8 handles of llm.hip): W is the row-wise absmax int8 matrix q[N, K] with one fp16 scale per
+// row.  Only the W staging differs: a thread loads the 8 bytes of its chunk, converts them to fp16 exactly (|q| <= 127) and forms
+// W'[n, k] = fp16(q) * s_n with ONE packed fp16 multiply per pair -- the thread's row never changes, so s_n is one register loaded
+// once -- and writes the same swizzled LDS image.  From there on the kernel is the fp16 kernel on W' (DESIGN.md 4.4.3).
 #include "gemm_common.h"
 #include "llm.h"
 
@@ -50,8 +55,21 @@ __device__ __forceinline__ void decode_store_swiglu(const DecodeGemmParams& p, i
     reinterpret_cast<half_t*>(p.out)[(int64_t)m * p.ldo + c] = (half_t)(s * round_f16(up));
 }
 
-template <int EPI>
-__global__ __launch_bounds__(512) void decode_gemm_kernel(DecodeGemmParams p, int tiles_n, int splitk) {
+typedef signed char i8x8 __attribute__((ext_vector_type(8)));
+
+// W'[n, k .. k+7] = fp16(q) * s_n: the conversion is exact, the product is rounded once.  The barrier keeps the product a value of
+// its own (nothing may be contracted or reassociated into it).
+__device__ __forceinline__ f16x8 dequant8(i8x8 q, half_t s) {
+    f16x8 v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (half_t)(short)q[e];
+    v = v * s;
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
+template <int EPI, bool W8>
+__global__ __launch_bounds__(512) void decode_gemm_kernel(DecodeGemmParams p, int tiles_n, int splitk, const half_t* __restrict__ wscale) {
     extern __shared__ __attribute__((aligned(16))) half_t dsmem[];   // [2 stages][A 256x64 | W 64x64]
 
     const int tid = threadIdx.x;
@@ -67,6 +85,10 @@ __global__ __launch_bounds__(512) void decode_gemm_kernel(DecodeGemmParams p, in
     const int ld_row = tid >> 3, ld_chunk = tid & 7;
     const half_t* a_src = p.A + (int64_t)ld_row * p.lda + ld_chunk * 8;
     const half_t* w_src = p.W + (int64_t)(tn * DBN + ld_row) * p.ldw + ld_chunk * 8;
+    // W8: p.W points at int8 elements (ldw counts them); the row's scale is loaded once
+    const signed char* q_src = reinterpret_cast<const signed char*>(p.W) + (int64_t)(tn * DBN + ld_row) * p.ldw + ld_chunk * 8;
+    half_t wsc = (half_t)0.0f;
+    if constexpr (W8) wsc = wscale[tn * DBN + ld_row];
     const int64_t a_step = 64 * p.lda;
     const int wr_off = ld_row * DBK + ((ld_chunk ^ ((ld_row >> 1) & 7)) << 3);   // +64 rows keeps the swizzle term
 
@@ -82,12 +104,15 @@ __global__ __launch_bounds__(512) void decode_gemm_kernel(DecodeGemmParams p, in
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     f16x8 ra[4], rb;
+    i8x8 rq;
     if (kt0 < kt1) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) ra[i] = *reinterpret_cast<const f16x8*>(a_src + i * a_step + (int64_t)kt0 * DBK);
-        rb = *reinterpret_cast<const f16x8*>(w_src + (int64_t)kt0 * DBK);
+        if constexpr (W8) rq = *reinterpret_cast<const i8x8*>(q_src + (int64_t)kt0 * DBK);
+        else rb = *reinterpret_cast<const f16x8*>(w_src + (int64_t)kt0 * DBK);
 #pragma unroll
         for (int i = 0; i < 4; ++i) *reinterpret_cast<f16x8*>(dsmem + wr_off + i * 64 * DBK) = ra[i];
+        if constexpr (W8) rb = dequant8(rq, wsc);
         *reinterpret_cast<f16x8*>(dsmem + DBM * DBK + wr_off) = rb;
     }
     __syncthreads();
@@ -98,7 +123,8 @@ __global__ __launch_bounds__(512) void decode_gemm_kernel(DecodeGemmParams p, in
         if (more) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) ra[i] = *reinterpret_cast<const f16x8*>(a_src + i * a_step + (int64_t)(kt + 1) * DBK);
-            rb = *reinterpret_cast<const f16x8*>(w_src + (int64_t)(kt + 1) * DBK);
+            if constexpr (W8) rq = *reinterpret_cast<const i8x8*>(q_src + (int64_t)(kt + 1) * DBK);
+            else rb = *reinterpret_cast<const f16x8*>(w_src + (int64_t)(kt + 1) * DBK);
         }
         if (active) {
 #pragma unroll
@@ -120,6 +146,7 @@ __global__ __launch_bounds__(512) void decode_gemm_kernel(DecodeGemmParams p, in
             half_t* dn = dsmem + ((kt + 1 - kt0) & 1) * DSTAGE;
 #pragma unroll
             for (int i = 0; i < 4; ++i) *reinterpret_cast<f16x8*>(dn + wr_off + i * 64 * DBK) = ra[i];
+            if constexpr (W8) rb = dequant8(rq, wsc);
             *reinterpret_cast<f16x8*>(dn + DBM * DBK + wr_off) = rb;
         }
         __syncthreads();
@@ -187,10 +214,10 @@ __global__ __launch_bounds__(256) void decode_combine_kernel(DecodeGemmParams p,
     }
 }
 
-template <int EPI>
-hipError_t launch_epi(const DecodeGemmParams& p, int splitk, hipStream_t stream) {
+template <int EPI, bool W8>
+hipError_t launch_epi(const DecodeGemmParams& p, int splitk, const half_t* wscale, hipStream_t stream) {
     const int tiles_n = p.N / DBN;
-    hipLaunchKernelGGL(decode_gemm_kernel<EPI>, dim3(tiles_n * splitk), dim3(512), DLDS_BYTES, stream, p, tiles_n, splitk);
+    hipLaunchKernelGGL((decode_gemm_kernel<EPI, W8>), dim3(tiles_n * splitk), dim3(512), DLDS_BYTES, stream, p, tiles_n, splitk, wscale);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || splitk == 1) return e;
     const int ncols = (EPI == DEC_SWIGLU) ? p.N / 2 : p.N;
@@ -202,8 +229,13 @@ hipError_t launch_epi(const DecodeGemmParams& p, int splitk, hipStream_t stream)
 }  // namespace
 
 hipError_t decode_gemm_prepare() {
-    const void* kernels[4] = {reinterpret_cast<const void*>(decode_gemm_kernel<DEC_F16>), reinterpret_cast<const void*>(decode_gemm_kernel<DEC_F16_RESID>),
-                              reinterpret_cast<const void*>(decode_gemm_kernel<DEC_SWIGLU>), reinterpret_cast<const void*>(decode_gemm_kernel<DEC_F32>)};
+    const void* kernels[7] = {reinterpret_cast<const void*>(decode_gemm_kernel<DEC_F16, false>),
+                              reinterpret_cast<const void*>(decode_gemm_kernel<DEC_F16_RESID, false>),
+                              reinterpret_cast<const void*>(decode_gemm_kernel<DEC_SWIGLU, false>),
+                              reinterpret_cast<const void*>(decode_gemm_kernel<DEC_F32, false>),
+                              reinterpret_cast<const void*>(decode_gemm_kernel<DEC_F16, true>),
+                              reinterpret_cast<const void*>(decode_gemm_kernel<DEC_F16_RESID, true>),
+                              reinterpret_cast<const void*>(decode_gemm_kernel<DEC_SWIGLU, true>)};
     for (const void* k : kernels) {
         const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, DLDS_BYTES);
         if (e != hipSuccess) return e;
@@ -223,17 +255,25 @@ size_t decode_gemm_slab_bytes(int N, int K) {
     return s > 1 ? (size_t)s * DBM * (size_t)N * sizeof(float) : 0;
 }
 
-hipError_t launch_decode_gemm(int epilogue, const DecodeGemmParams& p, hipStream_t stream) {
+hipError_t launch_decode_gemm(int epilogue, const DecodeGemmParams& p, hipStream_t stream, const half_t* wscale) {
     if (p.M < 1 || p.M > DBM || p.N < DBN || p.N % DBN || p.K < DBK || p.K % DBK || !p.A || !p.W || !p.out)
         return hipErrorInvalidValue;
     if (epilogue == DEC_F16_RESID && !p.resid) return hipErrorInvalidValue;
     const int splitk = decode_gemm_splitk(p.N, p.K);
     if (splitk > 1 && !p.slabs) return hipErrorInvalidValue;
+    if (wscale) {                                          // int8 weights: the three layer epilogues (lm_head stays fp16)
+        switch (epilogue) {
+            case DEC_F16: return launch_epi<DEC_F16, true>(p, splitk, wscale, stream);
+            case DEC_F16_RESID: return launch_epi<DEC_F16_RESID, true>(p, splitk, wscale, stream);
+            case DEC_SWIGLU: return launch_epi<DEC_SWIGLU, true>(p, splitk, wscale, stream);
+            default: return hipErrorInvalidValue;
+        }
+    }
     switch (epilogue) {
-        case DEC_F16: return launch_epi<DEC_F16>(p, splitk, stream);
-        case DEC_F16_RESID: return launch_epi<DEC_F16_RESID>(p, splitk, stream);
-        case DEC_SWIGLU: return launch_epi<DEC_SWIGLU>(p, splitk, stream);
-        case DEC_F32: return launch_epi<DEC_F32>(p, splitk, stream);
+        case DEC_F16: return launch_epi<DEC_F16, false>(p, splitk, nullptr, stream);
+        case DEC_F16_RESID: return launch_epi<DEC_F16_RESID, false>(p, splitk, nullptr, stream);
+        case DEC_SWIGLU: return launch_epi<DEC_SWIGLU, false>(p, splitk, nullptr, stream);
+        case DEC_F32: return launch_epi<DEC_F32, false>(p, splitk, nullptr, stream);
         default: return hipErrorInvalidValue;
     }
 }

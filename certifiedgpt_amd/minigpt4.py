@@ -144,6 +144,48 @@ def fp16_ulp(x):
     return 2.0 ** (math.floor(math.log2(max(float(x), 6.2e-5))) - 10)
 
 
+# ---- the weight law of weights="int8" (csrc/llm.hip: llm_quant_rows_kernel; include/cgpt.h: CGPT_LLM_W_INT8), in plain torch
+LAYER_LINEARS = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj",
+                 "mlp.down_proj")
+
+
+def quantize_rows_int8(w):
+    """Row-wise absmax int8 of an fp16 `nn.Linear.weight` [N, K] -> (q int8 [N, K], s fp16 [N]):
+        s_n  = fp16(absmax_k |w_nk| / 127)                     the division in fp32, then one rounding to fp16
+        q_nk = clamp(rint(fp32(w_nk) / fp32(s_n)), -127, 127)  fp32 division, round to nearest even; q = 0 where s_n = 0
+    (a zero row, or an absmax so small that absmax / 127 underflows fp16).  Works on CPU tensors."""
+    if w.dtype != torch.float16 or w.dim() != 2:
+        raise ValueError(f"quantize_rows_int8: expected an fp16 matrix [N, K], got {w.dtype} {tuple(w.shape)}")
+    s = (w.abs().amax(dim=1).float() / 127.0).to(torch.float16)
+    sf = s.float()[:, None]
+    live = sf != 0
+    q = torch.round(w.float() / torch.where(live, sf, torch.ones_like(sf))).clamp_(-127, 127)
+    return torch.where(live, q, torch.zeros_like(q)).to(torch.int8), s
+
+
+def dequantize_rows_int8(q, s):
+    """W'_nk = fp16(q_nk) * s_n as ONE fp16 multiply (q is exact in fp16): what an int8 handle multiplies by."""
+    if q.dtype != torch.int8 or s.dtype != torch.float16 or q.dim() != 2 or tuple(s.shape) != (q.shape[0],):
+        raise ValueError("dequantize_rows_int8: expected q int8 [N, K] and s fp16 [N]")
+    return q.to(torch.float16) * s[:, None]
+
+
+def int8_state_dict(llama_model, device=None):
+    """The state dict of `llama_model` with the seven linears of every layer replaced by W' = dequantize(quantize(W)); everything else
+    (embed_tokens, lm_head, the RMSNorm weights) as it is.  Loadable into an HF twin of the model: by the definition of
+    weights="int8" the native engine on `llama_model` computes, bit for bit, what the fp16 native engine computes on that twin.
+    device: where the law is evaluated (default: where each weight lives; "cpu" for the reference evaluation); the results go back to
+    the weight's own device."""
+    out = {}
+    for name, w in llama_model.state_dict().items():
+        if name.startswith("model.layers.") and name.endswith(".weight") and name.split(".", 3)[3][:-len(".weight")] in LAYER_LINEARS:
+            src = w.detach().to(device or w.device)
+            out[name] = dequantize_rows_int8(*quantize_rows_int8(src)).to(w.device)
+        else:
+            out[name] = w.detach().clone()
+    return out
+
+
 class _LinearRoute:
     """Routes the bias-free fp16 `nn.Linear` layers of a frozen decoder through libcgpt's MFMA GEMM (`cgpt_linear_f16`, the kernel
     of the ViT's qkv / proj / MLP) for calls with at least `min_rows` rows, i.e. the PREFILL of a Monte-Carlo batch (200 rows x 44
@@ -266,13 +308,17 @@ def _rope_theta(cfg):
 class _HipDecoder:
     """The native token step of a frozen LlamaForCausalLM (`cgpt_llm_*`, include/cgpt.h): validates the model, creates the handle
     and hands it the module's own fp16 parameters ONCE (the library keeps fused copies: 2 bytes per parameter more HBM, 13.5 GB at
-    7B; a later change of the module's weights is not seen).  `greedy` enqueues the whole loop after the prefill on the current
+    7B; a later change of the module's weights is not seen; with weights="int8" the seven linears of every layer are held as row-wise
+    absmax int8 instead, quantised on the device at load, 7.2 GB at 7B -- see `quantize_rows_int8`).  `greedy` enqueues the whole loop after the prefill on the current
     stream -- no host sync, capturable -- on the K/V buffers the prefill filled, in place."""
     MAX_LEN = 4096                                                     # positions the rotary table covers (prompt + new tokens)
 
-    def __init__(self, llama_model, max_batch):
+    def __init__(self, llama_model, max_batch, weights="fp16"):
         import ctypes as C
         from . import _lib
+        if weights not in _lib.LLM_WEIGHT_FORMATS:
+            raise ValueError(f'weights={weights!r}: expected "fp16" or "int8"')
+        self.weights = weights
         bad = hip_decode_unsupported(llama_model, max_batch)
         if bad:
             raise ValueError('decode="hip" does not support this decoder -- ' + "; ".join(bad))
@@ -281,7 +327,10 @@ class _HipDecoder:
         self.device = next(llama_model.parameters()).device
         self.layers, self.heads, self.vocab = int(cfg.num_hidden_layers), int(cfg.num_attention_heads), int(cfg.vocab_size)
         self.max_batch = int(max_batch)
-        c = _lib.LlmConfig(struct_size=C.sizeof(_lib.LlmConfig), device=self.device.index or 0, hidden=int(cfg.hidden_size),
+        # fp16 handles pass the config up to max_len, which every build of the library accepts (an A/B against an older build loads it
+        # through CGPT_LIB_PATH); weight_format travels only when it says something
+        size = C.sizeof(_lib.LlmConfig) if weights != "fp16" else _lib.LLM_CONFIG_SIZE_F16
+        c = _lib.LlmConfig(struct_size=size, weight_format=_lib.LLM_WEIGHT_FORMATS[weights], device=self.device.index or 0, hidden=int(cfg.hidden_size),
                            layers=self.layers, heads=self.heads, kv_heads=self.heads, head_dim=128, mlp=int(cfg.intermediate_size),
                            vocab=self.vocab, rms_eps=float(cfg.rms_norm_eps), rope_theta=_rope_theta(cfg),
                            max_batch=self.max_batch, max_len=self.MAX_LEN)
@@ -300,6 +349,17 @@ class _HipDecoder:
             w = w.contiguous()
             _lib.check(self.L.cgpt_llm_load_weight_f16(self.handle, name.encode(), C.c_void_p(w.data_ptr()), w.numel(), st))
         torch.cuda.current_stream(self.device).synchronize()           # contiguous() temporaries may go once the copies have run
+
+    @property
+    def weight_bytes(self):
+        """Bytes the handle holds for weight matrices, row scales and the dequantisation scratch (cgpt_llm_weight_bytes: the
+        library's own accounting).  None on a build of the library that predates the entry (CGPT_LIB_PATH A/B runs)."""
+        C = self._C
+        if not hasattr(self.L, "cgpt_llm_weight_bytes"):
+            return None
+        n = C.c_int64()
+        self._lib_mod.check(self.L.cgpt_llm_weight_bytes(self.handle, C.byref(n)))
+        return int(n.value)
 
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
@@ -407,6 +467,7 @@ class MiniGPT4Classifier:
        :param label_map: `AnswerLabelMap` -- frozen when torch.distributed is initialised (see label_adapter.py)
        :param ragged: "hf" (default) | "hip" -- who decodes a call whose rows carry DIFFERENT texts (left padding + mask); see __init__
        :param prompt_bucket: None | int >= 1 (with ragged="hip") -- padded prompt lengths are rounded up to a multiple of it
+       :param weights: "fp16" (default) | "int8" (with decode="hip" and prefill="hip") -- how the native engine holds the layer linears
 
     `prompt` is a plain attribute: assigning a new prompt between two images (`clf.prompt = ...`) is the supported way to ask a
     per-image question (VQA: one question per image).  Under decode="graph" / "hip" every new prompt LENGTH captures a graph of its
@@ -416,7 +477,8 @@ class MiniGPT4Classifier:
     noise_laws = ("gaussian", "uniform")       # passed through to encoder.encode_img_noisy
 
     def __init__(self, encoder, llama_model, llama_tokenizer, prompt, label_map, max_new_tokens=20, max_batch=None,
-                 generate_kwargs=None, decode="hf", prefill_linear="torch", prefill="model", ragged="hf", prompt_bucket=None):
+                 generate_kwargs=None, decode="hf", prefill_linear="torch", prefill="model", ragged="hf", prompt_bucket=None,
+                 weights="fp16"):
         self.encoder = encoder
         self.llama_model = llama_model
         self.llama_tokenizer = llama_tokenizer
@@ -457,6 +519,13 @@ class MiniGPT4Classifier:
         # prompt_bucket = k (with ragged = "hip" only): padded lengths are rounded up to a multiple of k, and a SHARED prompt is padded
         #   the same way (one common start), so prompts of different lengths replay one graph per bucket.  None: shared prompts take
         #   the unpadded path, unchanged.
+        # weights = "int8" (with decode = "hip" AND prefill = "hip" only; anything else is a ValueError): the native engine holds the
+        #   seven linears of every layer as row-wise absmax int8 with one fp16 scale per row (`quantize_rows_int8`; the weight law of the
+        #   reference's `low_resource: true` -> load_in_8bit), quantised on the device at load; activations stay fp16.  Half the
+        #   engine's weight bytes (decode_stats["weight_bytes"]).  Every token is, bit for bit, what the fp16 native engine gives on
+        #   the model whose layer linears are `int8_state_dict(llama_model)` (tests/test_gpu_llm_int8.py).  With the model's own
+        #   prefill the prompt would run on W and the steps on W': a mixed model, hence the ValueError.  Works with ragged = "hip" and
+        #   prompt_bucket.  weights = "fp16" (default): the engine's own fp16 copies, as before.
         assert decode in ("hf", "graph", "hip") and prefill_linear in ("torch", "cgpt")
         if prefill not in ("model", "hip"):
             raise ValueError(f'prefill={prefill!r}: expected "model" or "hip"')
@@ -467,6 +536,11 @@ class MiniGPT4Classifier:
         if ragged == "hip" and (decode != "hip" or prefill != "hip"):
             raise ValueError(f'ragged="hip" needs decode="hip" and prefill="hip" (got decode={decode!r}, prefill={prefill!r}): '
                              "left-padded rows run on the native prefill and the native token steps")
+        if weights not in ("fp16", "int8"):
+            raise ValueError(f'weights={weights!r}: expected "fp16" or "int8"')
+        if weights == "int8" and (decode != "hip" or prefill != "hip"):
+            raise ValueError(f'weights="int8" needs decode="hip" and prefill="hip" (got decode={decode!r}, prefill={prefill!r}): '
+                             "int8 weights exist on the native engine only, and prompt and steps must run on the same weights")
         if prompt_bucket is not None:
             if isinstance(prompt_bucket, bool) or not isinstance(prompt_bucket, int) or prompt_bucket < 1:
                 raise ValueError(f"prompt_bucket={prompt_bucket!r}: expected None or an int >= 1")
@@ -478,7 +552,8 @@ class MiniGPT4Classifier:
         self.ragged = ragged
         self.prompt_bucket = prompt_bucket
         self.prefill_linear = prefill_linear
-        self._hip = _HipDecoder(llama_model, self.max_batch) if decode == "hip" else None
+        self.weights = weights
+        self._hip = _HipDecoder(llama_model, self.max_batch, weights=weights) if decode == "hip" else None
         self.routed_linears = (_LinearRoute.install(llama_model)
                                if (decode in ("graph", "hip") and prefill_linear == "cgpt" and prefill == "model") else 0)
         import collections
@@ -487,7 +562,9 @@ class MiniGPT4Classifier:
         self._eos_mask = None
         self.decode_stats = {"graph_replays": 0, "graph_captures": 0, "graph_evictions": 0, "hf_calls": 0, "hf_fallback_kwargs": 0,
                              "hip_steps": 0,                      # token steps enqueued on the native engine (decode = "hip")
-                             "hip_prefills": 0}                   # native prefills enqueued (prefill = "hip"), counted alike
+                             "hip_prefills": 0,                   # native prefills enqueued (prefill = "hip"), counted alike
+                             # bytes the native engine holds for weights, scales and scratch (None without one)
+                             "weight_bytes": self._hip.weight_bytes if self._hip is not None else None}
 
     # ---- nn.Module-shaped surface used by Smooth (smoothing.py:42,71)
     def eval(self):

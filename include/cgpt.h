@@ -338,12 +338,26 @@ typedef struct cgpt_llm_config {
     float   rope_theta;       /* 10000                                                             */
     int32_t max_batch;        /* rows of a step, <= 256                                            */
     int32_t max_len;          /* positions (prompt + new tokens) the rotary table covers           */
+    int32_t weight_format;    /* CGPT_LLM_W_F16 (0) | CGPT_LLM_W_INT8 (1): how the layer linears are held; read only when
+                                 struct_size covers it -- a caller that passes the size up to max_len gets fp16 */
 } cgpt_llm_config;
+
+/* cgpt_llm_config.weight_format.
+ * CGPT_LLM_W_INT8 (W8A16): the seven linears of every layer are held as row-wise absmax int8, one fp16 scale per output row
+ * (the weight law of bitsandbytes' load_in_8bit; activations stay fp16, no outlier decomposition -- parity with LLM.int8()'s
+ * forward is NOT pinned).  For row n of an nn.Linear.weight [N, K]:  s_n = fp16(absmax_k |w_nk| / 127), the division in fp32;
+ * q_nk = clamp(rint(fp32(w_nk) / fp32(s_n)), -127, 127), round to nearest even, q = 0 where s_n = 0;  W'_nk = fp16(q_nk) * s_n,
+ * ONE fp16 multiply.  Every result of an int8 handle is bit for bit the result of an fp16 handle whose layer linears were loaded
+ * with W'.  lm_head, embed_tokens and the RMSNorm weights stay fp16. */
+#define CGPT_LLM_W_F16 0
+#define CGPT_LLM_W_INT8 1
 
 typedef struct cgpt_llm* cgpt_llm_handle;
 
 /* Allocates the library's own weight copies (fused q/k/v and gate/up, 2 bytes per parameter: 13.5 GB MORE HBM at 7B, beside the
- * HF module's) and the step workspace.  CGPT_ERR_INVALID for an unsupported config, CGPT_ERR_NO_DEVICE without a GPU. */
+ * HF module's; CGPT_LLM_W_INT8: 1 byte per layer-linear parameter, the row scales and ONE fp16 scratch matrix of the largest fused
+ * layer matrix for the prefill, 7.2 GB at 7B) and the step workspace.  CGPT_ERR_INVALID for an unsupported config, a struct_size
+ * that is neither the whole struct nor the struct up to max_len, or an unknown weight_format; CGPT_ERR_NO_DEVICE without a GPU. */
 cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out);
 cgpt_status cgpt_llm_destroy(cgpt_llm_handle h);
 /* Device-to-device copy of one fp16 parameter of the HF module under its state_dict name: "model.embed_tokens.weight",
@@ -351,6 +365,13 @@ cgpt_status cgpt_llm_destroy(cgpt_llm_handle h);
  * "model.layers.<i>.{input,post_attention}_layernorm.weight", "model.norm.weight", "lm_head.weight" (contiguous, PyTorch shape;
  * numel must match).  Enqueued on `stream`.  The step entries return CGPT_ERR_STATE until every name has been loaded. */
 cgpt_status cgpt_llm_load_weight_f16(cgpt_llm_handle h, const char* name, const void* data_dev, int64_t numel, void* stream);
+/* On a CGPT_LLM_W_INT8 handle cgpt_llm_load_weight_f16 of a layer linear is a quantising kernel instead of a copy: it reads the
+ * caller's fp16 rows and writes int8 rows and their scales into the fused matrix (rows keep their scales through the q/k/v fusion
+ * and the gate/up interleave); no fp16 copy of the layer survives the call.  The other names are copied as above.
+ * cgpt_llm_weight_bytes: *out = the bytes this handle holds for weight matrices (embed_tokens, lm_head and the layer linears with
+ * their padding to 256-row tiles), row scales and the dequantisation scratch, as allocated -- the library's own accounting.  The
+ * RMSNorm vectors, the rotary table and the step / prefill workspaces are not counted. */
+cgpt_status cgpt_llm_weight_bytes(cgpt_llm_handle h, int64_t* out);
 /* One token step: row b feeds token tokens_dev[b] (int64) at position `pos`; layer l appends its rotated key and its value to
  * row `pos` of k_ptrs_host[l] / v_ptrs_host[l] (device buffers [B, heads, kv_len_stride, 128] fp16; the two tables are HOST
  * arrays of `layers` device pointers, read when the call enqueues) and attends over rows 0 .. pos.  No other cache row is

@@ -17,7 +17,13 @@ reads, over 6.3 TB/s (the copy rate the box reaches).
                 `bucketed`, other contents of the starts tensor
     hf_ragged   today's fallback for those rows: eager HF `generate` with the attention mask (generate_ms only)
     parent      `plain` on another build of the library (--parent-lib PATH, e.g. the parent commit's libcgpt.so), loaded beside
-                the product in this process: the claim to check is that the plain path's time is unchanged"""
+                the product in this process: the claim to check is that the plain path's time is unchanged
+
+--int8 runs the weight-format leg instead (weights="int8"), same protocol, every engine decode="hip", prefill="hip":
+    fp16        the engine's own fp16 copies (today's path)
+    int8        row-wise absmax int8 layer linears: the int8-weight decode GEMM in the steps, a dequant pass before each prefill GEMM
+    parent      `fp16` on another build of the library (--parent-lib PATH), as under --ragged
+and reports the handles' weight_bytes beside the times."""
 import argparse
 import json
 import os
@@ -165,6 +171,78 @@ def ragged_leg(args, llm, embs, tok, lm):
     print(json.dumps(line))
 
 
+def int8_leg(args, llm, embs, tok, lm):
+    rows = args.rows
+
+    def build(n, **kw):
+        return MiniGPT4Classifier(_Rows(rows), llm, tok, "<ImageHere>", lm, max_new_tokens=n, max_batch=rows, decode="hip", prefill="hip", **kw)
+
+    legs = ["fp16", "int8"]
+    clfs = {("fp16", n): build(n) for n in (args.new, 1)}
+    clfs.update({("int8", n): build(n, weights="int8") for n in (args.new, 1)})
+    if args.parent_lib:
+        with _other_library(args.parent_lib):
+            clfs.update({("parent", n): build(n) for n in (args.new, 1)})
+        legs.append("parent")
+
+    def timed(leg, n):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = clfs[(leg, n)]._generate_graph(embs)
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b), out
+
+    clock_before = _clock()
+    res = {e: {"generate_ms": [], "prefill_ms": []} for e in legs}
+    tokens = {}
+    with torch.no_grad():
+        for rep_i in range(args.warmup + args.reps):                   # interleaved: leg by leg inside every repetition
+            for e in legs:
+                t, out = timed(e, args.new)
+                tp = timed(e, 1)[0]
+                print(f"decode_step_bench: repetition {rep_i} {e} generate {t:.1f} ms prefill {tp:.1f} ms", file=sys.stderr, flush=True)
+                if rep_i >= args.warmup:
+                    res[e]["generate_ms"].append(t)
+                    res[e]["prefill_ms"].append(tp)
+                    tokens[e] = out
+    clock_after = _clock()
+    steps = args.new - 1
+    for r in res.values():
+        r["step_ms"] = [(gm - pm) / steps for gm, pm in zip(r["generate_ms"], r["prefill_ms"])]
+        for k in ("generate_ms", "prefill_ms", "step_ms"):
+            r[k + "_min_max"] = [min(r[k]), max(r[k])]
+
+    def overlap(a, b, k):
+        (a0, a1), (b0, b1) = res[a][k + "_min_max"], res[b][k + "_min_max"]
+        return a0 <= b1 and b0 <= a1
+
+    def med(e, k):
+        return sorted(res[e][k])[len(res[e][k]) // 2]
+
+    keys = ("prefill_ms", "step_ms", "generate_ms")
+    wb = {e: clfs[(e, args.new)].decode_stats["weight_bytes"] for e in legs}
+    layer_bytes = sum(p.numel() for n, p in llm.named_parameters() if "_proj." in n)
+    kv_mean = 2 * 2 * rows * args.layers * 4096 * (args.prompt + (steps + 1) / 2.0)
+    lm_head = 2 * 32000 * 4096
+    line = {"tool": "decode_step_bench", "leg": "int8", "rows": rows, "prompt": args.prompt, "new_tokens": args.new, "layers": args.layers,
+            "reps": args.reps, "warmup": args.warmup, "engines": res, "weight_bytes": wb,
+            "int8_over_fp16_weight_bytes": wb["int8"] / wb["fp16"],
+            "int8_over_fp16_median": {k: med("int8", k) / med("fp16", k) for k in keys},
+            "int8_and_fp16_ranges_overlap": {k: overlap("int8", "fp16", k) for k in keys},
+            "floor_ms_per_step": {"fp16": (2 * layer_bytes + lm_head + kv_mean) / COPY_RATE * 1e3,
+                                  "int8": (layer_bytes + lm_head + kv_mean) / COPY_RATE * 1e3},
+            "copy_rate_bytes_per_s": COPY_RATE,
+            "int8_rows_with_fp16_tokens": int((tokens["int8"] == tokens["fp16"]).all(dim=1).sum()),
+            "shader_clock_mhz_before_after": [clock_before, clock_after], "device": torch.cuda.get_device_name(0)}
+    if "parent" in res:
+        line["parent_lib"] = os.path.basename(args.parent_lib)
+        line["fp16_and_parent_ranges_overlap"] = {k: overlap("fp16", "parent", k) for k in keys}
+        line["fp16_over_parent_median"] = {k: med("fp16", k) / med("parent", k) for k in keys}
+        line["fp16_rows_with_parent_tokens"] = int((tokens["fp16"] == tokens["parent"]).all(dim=1).sum())
+    print(json.dumps(line))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=200)
@@ -177,7 +255,8 @@ def main():
     ap.add_argument("--ragged", action="store_true", help="the left-padding leg (see the module docstring)")
     ap.add_argument("--bucket-len", type=int, default=48)
     ap.add_argument("--ragged-min", type=int, default=38)
-    ap.add_argument("--parent-lib", default=None, help="another build of libcgpt.so for the plain-path A/B of --ragged")
+    ap.add_argument("--int8", action="store_true", help="the weight-format leg (see the module docstring)")
+    ap.add_argument("--parent-lib", default=None, help="another build of libcgpt.so for the plain-path A/B of --ragged / --int8")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "this benchmark measures device time: it needs the GPU"
     assert 1 <= args.rows <= 256 and args.new >= 2 and args.prompt >= 1
@@ -189,6 +268,8 @@ def main():
     tok, lm = WordHashTokenizer(32000), AnswerLabelMap(4, ())
     if args.ragged:
         return ragged_leg(args, llm, embs, tok, lm)
+    if args.int8:
+        return int8_leg(args, llm, embs, tok, lm)
     how = {"graph": dict(decode="graph"), "hip": dict(decode="hip", prefill="model"), "hip_native": dict(decode="hip", prefill="hip")}
     clfs = {(e, n): MiniGPT4Classifier(_Rows(args.rows), llm, tok, "<ImageHere>", lm, max_new_tokens=n, max_batch=args.rows,
                                        prefill_linear="cgpt", **how[e]) for e in engines for n in (args.new, 1)}
