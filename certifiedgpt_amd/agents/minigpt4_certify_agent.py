@@ -17,6 +17,9 @@ Config (a plain dict or any mapping; the reference's YAMLs define no smoothing k
             #          prefill; needs decode "hip"), ragged: "hf" | "hip" (rows with different texts on the native engine; needs decode
             #          and prefill "hip"), prompt_bucket: null | int (with ragged "hip": prompt lengths rounded up to a multiple of it,
             #          one captured graph per bucket) -- see build_generating_classifier
+            #          also: classify: "generate" | "multi_select" (rank the answers by their teacher-forced loss instead of generating:
+            #          every noisy copy votes for one of `answers`, never for "other"), score: "hf" | "hip" (who computes those losses;
+            #          "hip" needs decode and prefill "hip"), end_sym: "\\n" (appended to every answer; the reference's VQA configs: "###")
             mode: vit_head | encode_img, weights: <path to a torch state_dict saved with torch.save> | null, dims: {...},
             partial_weights: false}   # true: load what the checkpoint has on top of the synthetic initialisation
     data:  {num_images: 10, seed: 1234}      # synthetic CLIP-normalised images unless `dataset` is passed to the agent
@@ -192,7 +195,9 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
                   (decode / prefill_linear / prefill / ragged / prompt_bucket: see MiniGPT4Classifier; prefill "hip" needs decode
                   "hip", ragged "hip" needs both, prompt_bucket needs ragged "hip"); weights: "fp16" | "int8" (the native engine's
                   layer linears as row-wise absmax int8, the weight law of the reference's low_resource: true; needs decode and
-                  prefill "hip")"""
+                  prefill "hip"); classify: "generate" | "multi_select" (the base classifier ranks `answers` by their answer loss,
+                  MiniGPTBase.multi_select, instead of generating), score: "hf" | "hip" (the model's own forward per candidate | one
+                  native prefill + the native scoring pass; needs decode and prefill "hip"), end_sym: "\\n" (appended to every answer)"""
     from ..minigpt4 import MiniGPT4Classifier
     from .label_adapter import AnswerLabelMap
     if llama_model is None:
@@ -221,7 +226,9 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
                               max_new_tokens=int(gen_cfg.get("max_new_tokens", 20)), max_batch=encoder.max_batch,
                               decode=gen_cfg.get("decode", "hf"), prefill_linear=gen_cfg.get("prefill_linear", "torch"),
                               prefill=gen_cfg.get("prefill", "model"), ragged=gen_cfg.get("ragged", "hf"),
-                              prompt_bucket=gen_cfg.get("prompt_bucket"), weights=gen_cfg.get("weights", "fp16"))
+                              prompt_bucket=gen_cfg.get("prompt_bucket"), weights=gen_cfg.get("weights", "fp16"),
+                              classify=gen_cfg.get("classify", "generate"), score=gen_cfg.get("score", "hf"),
+                              end_sym=gen_cfg.get("end_sym", "\n"))
 
 
 def build_classifier(model_cfg, num_classes, max_batch, device_index, tokenizer=None, llama_model=None):

@@ -54,4 +54,34 @@ hipError_t launch_prefill_attention(const half_t* qkv, int B, int L, int hidden,
 // act[rows, mlp] = fp16(fp16(silu(gate)) * up) from gu [rows, 2 mlp] with gate / up columns interleaved in blocks of 16.
 hipError_t launch_prefill_swiglu(const half_t* gu, int64_t rows, int mlp, half_t* act, hipStream_t stream);
 
+// ------------------------------------------------------------------------------------- answer scoring (llm_score.hip)
+// C candidate answers of T_c tokens each are scored on ONE prefilled prompt of L positions per row.  Token 0 of a candidate is
+// predicted by the prompt's last position; token j >= 1 by "tail row" j - 1: input token j - 1 of the candidate at rotary position
+// L + j - 1.  A prompt row b has S = sum_c (T_c - 1) tail rows, tail row r = b * S + off[c] + j everywhere below.
+constexpr int SCORE_MAX_CANDS = 64;      // candidates of one call
+constexpr int SCORE_MAX_TAIL = 64;       // tail rows per prompt row (the attention kernel keeps their state in LDS)
+struct ScoreCands {                      // passed by value: nothing is copied to the device by the host
+    int n;                               // C
+    int tmax;                            // row length of the token table [C, tmax]
+    int off[SCORE_MAX_CANDS + 1];        // off[c] = sum of (T_c' - 1) over c' < c; off[n] = S.  T_c = off[c + 1] - off[c] + 1
+};
+// Sets the attention kernel's dynamic-LDS limit on the CURRENT device (once per device, outside any capture).
+hipError_t score_prepare();
+// h[r, :] = embed[token of tail row r, :]; a token outside the table reads row 0.
+hipError_t launch_score_embed(const long long* cand_tokens, const ScoreCands& t, int B, const half_t* table, int vocab, int hidden,
+                              half_t* h, hipStream_t stream);
+// Rotary + attention of the tail rows: out[r, head] = softmax(q_r . [K_prompt(b, 0..L-1); k_tail(b, c, 0..j)] / sqrt(128)) . V alike,
+// q / k / v from qkv [B S, 3 hidden] (not modified).  Kc / Vc are read (rows 0 .. L-1) and NEVER written.
+hipError_t launch_score_attention(const half_t* qkv, const ScoreCands& t, int B, int L, int hidden, int heads, const half_t* Kc,
+                                  const half_t* Vc, int64_t len_stride, const half_t* rope, half_t* out, hipStream_t stream);
+// ce[b, tok(c) + j] = label-smoothed cross-entropy of one logits row against token j of candidate c, tok(c) = off[c] + c, a row of
+// ce holding S + C values.  first: token 0 of every candidate on the fp32 rows first_logits[b] (B x C workgroups).  tail: `rows`
+// fp16 logits rows, the tail rows row0 .. row0 + rows - 1 (row r predicts token j + 1 of its candidate).
+hipError_t launch_score_ce_first(const float* first_logits, int vocab, const long long* cand_tokens, const ScoreCands& t, int B,
+                                 float smoothing, float* ce, hipStream_t stream);
+hipError_t launch_score_ce_tail(const half_t* logits, int vocab, const long long* cand_tokens, const ScoreCands& t, int64_t row0,
+                                int64_t rows, float smoothing, float* ce, hipStream_t stream);
+// out[b, c] = ce[b, tok(c)] + ... + ce[b, tok(c) + T_c - 1], added in token order.
+hipError_t launch_score_sum(const float* ce, const ScoreCands& t, int B, float* out, hipStream_t stream);
+
 }  // namespace cgpt

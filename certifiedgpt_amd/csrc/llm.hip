@@ -4,6 +4,8 @@
 // (graphs/models/minigpt4/models/minigpt_base.py:418-431, greedy: do_sample=False, num_beams=1), i.e. HF LlamaForCausalLM
 // on one new token per row with a K/V cache.  The prefill is the caller's (the model's own forward; its K/V are used in place) or
 // cgpt_llm_prefill below: the same layer sequence on B x L token rows, large-shape GEMMs (gemm.hip) and llm_prefill.hip's kernels.
+// cgpt_llm_score (`MiniGPTBase.multi_select`, minigpt_base.py:451-467) runs that sequence once more on the answer tokens of all
+// candidates, on the prompt cache the prefill left and without writing to it (llm_score.hip).
 //
 // One step = embedding lookup, layers x (RMSNorm, fused q/k/v GEMM, rotary + K/V append + one-query attention, o_proj GEMM +
 // residual, RMSNorm, fused gate/up GEMM + SwiGLU, down GEMM + residual), final RMSNorm, lm_head GEMM.  The GEMMs are
@@ -341,6 +343,11 @@ struct cgpt_llm {
     // int8 handles: the prefill's ONE fp16 expansion of the layer matrix its next GEMM reads (stream order makes one enough)
     half_t* scratch = nullptr;
     int64_t weight_bytes = 0;              // matrices, scales and scratch, as allocated (cgpt_llm_weight_bytes)
+    // scoring workspace (cgpt_llm_score_reserve) beside the prefill workspace, which holds the tail rows: fp16 logits of `s_rows`
+    // tail rows (a multiple of 256; more rows run in chunks) and `s_ce` per-token cross-entropies.  Replaced buffers stay in `allocs`.
+    int64_t s_rows = 0, s_ce = 0;
+    half_t* s_logits = nullptr;
+    float* s_ce_buf = nullptr;
 };
 
 namespace {
@@ -462,6 +469,45 @@ cgpt_status run_prefill(cgpt_llm* m, const half_t* embeds, int B, int L, const i
     return gemm(m, DEC_F32, m->xn, H, Mat{m->lm_head}, c.vocab, logits, c.vocab, nullptr, B, st);
 }
 
+
+constexpr int64_t SCORE_LOGIT_ROWS = 4096;                 // tail rows whose fp16 logits are held at once (262 MB at 32 000 columns)
+
+// All candidates of `t` on the prompt cache rows 0 .. L-1 of B prompt rows: out[b, c] = summed label-smoothed cross-entropy.
+// run_prefill's layer sequence on the R = B S tail rows with the tail attention in place of rotary + cache write + causal
+// attention; then lm_head and the cross-entropy in chunks of the reserved logits rows.  No cache row is written.
+cgpt_status run_score(cgpt_llm* m, const float* first_logits, int B, int L, const long long* cand_tokens, const ScoreCands& t, float eps,
+                      void* const* kp, void* const* vp, int64_t len_stride, float* out, hipStream_t st) {
+    const cgpt_llm_config& c = m->cfg;
+    const int H = c.hidden, F = c.mlp, S = t.off[t.n];
+    const int64_t R = (int64_t)B * S;
+    HIPCHK(launch_score_ce_first(first_logits, c.vocab, cand_tokens, t, B, eps, m->s_ce_buf, st));
+    if (S > 0) {
+        HIPCHK(launch_score_embed(cand_tokens, t, B, m->embed, c.vocab, H, m->p_h, st));
+        const half_t* pending = nullptr;
+        for (int l = 0; l < c.layers; ++l) {
+            const Layer& Lw = m->layers[l];
+            HIPCHK(launch_prefill_addnorm(m->p_h, pending, 1, 0, Lw.ln1, H, c.rms_eps, m->p_h, m->p_xn, R, st));
+            CGCHK(big_gemm(m, m->p_xn, H, Lw.wqkv, 3 * H, m->p_qkv, R, st));
+            HIPCHK(launch_score_attention(m->p_qkv, t, B, L, H, c.heads, (const half_t*)kp[l], (const half_t*)vp[l], len_stride, m->rope,
+                                          m->p_attn, st));
+            CGCHK(big_gemm(m, m->p_attn, H, Lw.wo, H, m->p_proj, R, st));
+            HIPCHK(launch_prefill_addnorm(m->p_h, m->p_proj, 1, 0, Lw.ln2, H, c.rms_eps, m->p_h, m->p_xn, R, st));
+            CGCHK(big_gemm(m, m->p_xn, H, Lw.wgu, 2 * F, m->p_gu, R, st));
+            HIPCHK(launch_prefill_swiglu(m->p_gu, R, F, m->p_act, st));
+            CGCHK(big_gemm(m, m->p_act, F, Lw.wdown, H, m->p_proj, R, st));
+            pending = m->p_proj;
+        }
+        HIPCHK(launch_prefill_addnorm(m->p_h, pending, 1, 0, m->norm, H, c.rms_eps, m->p_h, m->p_xn, R, st));
+        for (int64_t r0 = 0; r0 < R; r0 += m->s_rows) {        // chunks begin at multiples of 256 rows: whole GEMM row tiles
+            const int64_t n = std::min(m->s_rows, R - r0);
+            CGCHK(big_gemm(m, m->p_xn + r0 * H, H, Mat{m->lm_head}, c.vocab, m->s_logits, n, st));
+            HIPCHK(launch_score_ce_tail(m->s_logits, c.vocab, cand_tokens, t, r0, n, eps, m->s_ce_buf, st));
+        }
+    }
+    HIPCHK(launch_score_sum(m->s_ce_buf, t, B, out, st));
+    return CGPT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -494,6 +540,7 @@ cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
     if (c.device < 0 || c.device >= ndev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: bad device ordinal");
     HIPCHK(hipSetDevice(c.device));
     HIPCHK(decode_gemm_prepare());                        // kernel attributes now: nothing but launches is left for a captured stream
+    HIPCHK(score_prepare());
     cgpt_llm* m = new cgpt_llm();
     m->cfg = c;
     m->layers.resize(c.layers);
@@ -512,7 +559,9 @@ cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
     };
     counted(V * H * hs, &m->embed);
     za(H * hs, &m->norm);
-    counted(V * H * hs, &m->lm_head);
+    // lm_head is read by the large-shape GEMM too (cgpt_llm_score): whole 256-row tiles, pad rows zeros.  Counted without them.
+    za(up256(V) * H * hs, &m->lm_head);
+    m->weight_bytes += (int64_t)(V * H * hs);
     for (Layer& L : m->layers) {
         mat(L.wqkv, 3 * H, H);
         mat(L.wo, H, H);
@@ -700,11 +749,8 @@ cgpt_status cgpt_llm_greedy_ragged(cgpt_llm_handle h, const float* first_logits_
                             num_eos, pad_id, k_ptrs_host, v_ptrs_host, kv_len_stride, tokens_out_dev, step_logits_out_dev, stream);
 }
 
-cgpt_status cgpt_llm_prefill_reserve(cgpt_llm_handle h, int32_t max_rows, int32_t max_prompt_len) {
-    if (!h) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_prefill_reserve: null handle");
-    if (max_rows < 1 || max_rows > h->cfg.max_batch || max_prompt_len < 1 || max_prompt_len > h->cfg.max_len)
-        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_prefill_reserve: rows outside 1..max_batch or prompt length outside 1..max_len");
-    const int64_t rows = ((int64_t)max_rows * max_prompt_len + 255) / 256 * 256;
+// Grows the prefill workspace to `rows` token rows (a multiple of 256); `who` names the entry in messages.
+static cgpt_status grow_workspace(cgpt_llm_handle h, int64_t rows, const std::string& who) {
     if (rows <= h->p_rows) return CGPT_OK;                 // grows only; a second call with the same sizes does nothing
     HIPCHK(hipSetDevice(h->cfg.device));
     const size_t H = h->cfg.hidden, F = h->cfg.mlp, hs = sizeof(half_t);
@@ -721,7 +767,7 @@ cgpt_status cgpt_llm_prefill_reserve(cgpt_llm_handle h, int32_t max_rows, int32_
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         for (half_t* p : fresh) (void)hipFree(p);
-        return cgpt_fail(CGPT_ERR_HIP, std::string("cgpt_llm_prefill_reserve: workspace allocation failed -> ") + hipGetErrorString(e));
+        return cgpt_fail(CGPT_ERR_HIP, who + ": workspace allocation failed -> " + hipGetErrorString(e));
     }
     half_t** bufs[7] = {&h->p_h, &h->p_xn, &h->p_qkv, &h->p_attn, &h->p_proj, &h->p_gu, &h->p_act};
     for (int i = 0; i < 7; ++i) {
@@ -730,6 +776,13 @@ cgpt_status cgpt_llm_prefill_reserve(cgpt_llm_handle h, int32_t max_rows, int32_
     }
     h->p_rows = rows;
     return CGPT_OK;
+}
+
+cgpt_status cgpt_llm_prefill_reserve(cgpt_llm_handle h, int32_t max_rows, int32_t max_prompt_len) {
+    if (!h) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_prefill_reserve: null handle");
+    if (max_rows < 1 || max_rows > h->cfg.max_batch || max_prompt_len < 1 || max_prompt_len > h->cfg.max_len)
+        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_prefill_reserve: rows outside 1..max_batch or prompt length outside 1..max_len");
+    return grow_workspace(h, ((int64_t)max_rows * max_prompt_len + 255) / 256 * 256, "cgpt_llm_prefill_reserve");
 }
 
 static cgpt_status llm_prefill_entry(const char* who_c, cgpt_llm_handle h, const void* embeds_dev, int32_t B, int32_t L,
@@ -759,6 +812,69 @@ cgpt_status cgpt_llm_prefill_ragged(cgpt_llm_handle h, const void* embeds_dev, i
     if (!starts_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_prefill_ragged: null starts_dev");
     return llm_prefill_entry("cgpt_llm_prefill_ragged", h, embeds_dev, B, L, starts_dev, k_ptrs_host, v_ptrs_host, kv_len_stride,
                              logits_dev, stream);
+}
+
+cgpt_status cgpt_llm_score_reserve(cgpt_llm_handle h, int32_t max_rows, int32_t max_tail_rows) {
+    if (!h) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_score_reserve: null handle");
+    if (max_rows < 1 || max_rows > h->cfg.max_batch || max_tail_rows < 1 || max_tail_rows > SCORE_MAX_TAIL)
+        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_score_reserve: rows outside 1..max_batch or tail rows outside 1.." +
+                                               std::to_string(SCORE_MAX_TAIL));
+    const int64_t rows = ((int64_t)max_rows * max_tail_rows + 255) / 256 * 256;
+    CGCHK(grow_workspace(h, rows, "cgpt_llm_score_reserve"));      // the tail rows run on the prefill workspace
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const int64_t lrows = std::min(rows, SCORE_LOGIT_ROWS), nce = (int64_t)max_rows * (max_tail_rows + SCORE_MAX_CANDS);
+    // as the prefill workspace: built beside the buffers in use, which stay allocated until destroy
+    half_t* logits = nullptr;
+    float* ce = nullptr;
+    hipError_t e = hipSuccess;
+    if (lrows > h->s_rows) {
+        e = hipMalloc((void**)&logits, (size_t)lrows * h->cfg.vocab * sizeof(half_t));
+        if (e == hipSuccess) e = hipMemset(logits, 0, (size_t)lrows * h->cfg.vocab * sizeof(half_t));
+    }
+    if (e == hipSuccess && nce > h->s_ce) {
+        e = hipMalloc((void**)&ce, (size_t)nce * sizeof(float));
+        if (e == hipSuccess) e = hipMemset(ce, 0, (size_t)nce * sizeof(float));
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipFree(logits);
+        (void)hipFree(ce);
+        return cgpt_fail(CGPT_ERR_HIP, std::string("cgpt_llm_score_reserve: workspace allocation failed -> ") + hipGetErrorString(e));
+    }
+    if (logits) { h->s_logits = logits; h->s_rows = lrows; h->allocs.push_back(logits); }
+    if (ce) { h->s_ce_buf = ce; h->s_ce = nce; h->allocs.push_back(ce); }
+    return CGPT_OK;
+}
+
+cgpt_status cgpt_llm_score(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len, const int64_t* cand_tokens_dev,
+                           const int32_t* cand_lens_host, int32_t C, int32_t Tmax, float label_smoothing, void* const* k_ptrs_host,
+                           void* const* v_ptrs_host, int64_t kv_len_stride, float* out_dev, void* stream) {
+    const std::string who("cgpt_llm_score");
+    if (!h || !first_logits_dev || !cand_tokens_dev || !cand_lens_host || !out_dev) return cgpt_fail(CGPT_ERR_INVALID, who + ": null argument");
+    if (C < 1 || C > SCORE_MAX_CANDS || Tmax < 1)
+        return cgpt_fail(CGPT_ERR_INVALID, who + ": candidates outside 1.." + std::to_string(SCORE_MAX_CANDS) + " or Tmax < 1");
+    if (!(label_smoothing >= 0.0f && label_smoothing < 1.0f)) return cgpt_fail(CGPT_ERR_INVALID, who + ": label_smoothing outside [0, 1)");
+    ScoreCands t{};
+    t.n = C;
+    t.tmax = Tmax;
+    for (int c = 0; c < C; ++c) {
+        if (cand_lens_host[c] < 1 || cand_lens_host[c] > Tmax)
+            return cgpt_fail(CGPT_ERR_INVALID, who + ": candidate " + std::to_string(c) + " has a length outside 1..Tmax");
+        t.off[c + 1] = t.off[c] + cand_lens_host[c] - 1;
+        if (t.off[c + 1] > SCORE_MAX_TAIL)
+            return cgpt_fail(CGPT_ERR_INVALID, who + ": more than " + std::to_string(SCORE_MAX_TAIL) + " tail rows (sum of lengths - 1) per prompt row");
+    }
+    if (prompt_len < 1 || (int64_t)prompt_len + Tmax - 1 > h->cfg.max_len)
+        return cgpt_fail(CGPT_ERR_INVALID, who + ": prompt_len < 1 or prompt_len + Tmax - 1 > max_len (the rotary table)");
+    CGCHK(check_cache(h, "cgpt_llm_score", B, prompt_len - 1, k_ptrs_host, v_ptrs_host, kv_len_stride));
+    CGCHK(ready(h, "cgpt_llm_score"));
+    const int64_t R = (int64_t)B * t.off[C];
+    if (R > h->p_rows || (R > 0 && h->s_rows < 1) || (int64_t)B * (t.off[C] + C) > h->s_ce)
+        return cgpt_fail(CGPT_ERR_STATE, who + ": " + std::to_string(R) + " tail rows of " + std::to_string(C) +
+                                             " candidates exceed the reserved workspace (call cgpt_llm_score_reserve outside any capture first)");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    return run_score(h, first_logits_dev, B, prompt_len, (const long long*)cand_tokens_dev, t, label_smoothing, k_ptrs_host, v_ptrs_host,
+                     kv_len_stride, out_dev, (hipStream_t)stream);
 }
 
 }  // extern "C"

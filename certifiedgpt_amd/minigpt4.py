@@ -456,6 +456,31 @@ class _HipDecoder:
                                                               self._starts_ptr(starts, B), *tail))
         return (tokens, steps) if return_logits else tokens
 
+    MAX_CANDS, MAX_TAIL = 64, 64                                       # SCORE_MAX_CANDS, SCORE_MAX_TAIL (csrc/llm.h)
+
+    def score(self, first_logits, prompt_len, cand_tokens, cand_lens, label_smoothing, k_bufs, v_bufs):
+        """Every candidate on the prompt cache a prefill left (cgpt_llm_score): first_logits [B, vocab] fp32 = that prefill's result,
+        cand_tokens [C, Tmax] int64 on the device, cand_lens = the C token counts (host) -> [B, C] fp32, the SUM over each
+        candidate's tokens of the label-smoothed cross-entropy.  Reads cache rows 0 .. prompt_len-1 and writes none.  The workspace is
+        reserved here (outside any capture), for `max_batch` rows of this call's tail rows."""
+        C = self._C
+        B, V = first_logits.shape
+        n, tmax = cand_tokens.shape
+        lens = [int(t) for t in cand_lens]
+        assert (first_logits.dtype == torch.float32 and first_logits.device == self.device and first_logits.is_contiguous()
+                and V == self.vocab and 1 <= B <= self.max_batch)
+        assert (cand_tokens.dtype == torch.int64 and cand_tokens.device == self.device and cand_tokens.is_contiguous()
+                and len(lens) == n)
+        kp, vp, stride = self._cache_tables(k_bufs, v_bufs, B, int(prompt_len))
+        if not torch.cuda.is_current_stream_capturing():
+            self._lib_mod.check(self.L.cgpt_llm_score_reserve(self.handle, self.max_batch, max(1, sum(t - 1 for t in lens))))
+        out = torch.empty((B, n), dtype=torch.float32, device=self.device)
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._lib_mod.check(self.L.cgpt_llm_score(self.handle, C.c_void_p(first_logits.data_ptr()), B, int(prompt_len),
+                                                  C.c_void_p(cand_tokens.data_ptr()), (C.c_int32 * n)(*lens), n, int(tmax),
+                                                  float(label_smoothing), kp, vp, stride, C.c_void_p(out.data_ptr()), st))
+        return out
+
 
 class MiniGPT4Classifier:
     """:param encoder: a `HipClassifier(mode="encode_img")` (or any object with `encode_img(images) -> (emb, atts)` and
@@ -468,6 +493,11 @@ class MiniGPT4Classifier:
        :param ragged: "hf" (default) | "hip" -- who decodes a call whose rows carry DIFFERENT texts (left padding + mask); see __init__
        :param prompt_bucket: None | int >= 1 (with ragged="hip") -- padded prompt lengths are rounded up to a multiple of it
        :param weights: "fp16" (default) | "int8" (with decode="hip" and prefill="hip") -- how the native engine holds the layer linears
+       :param end_sym: text appended to every candidate answer of `multi_select` ("\n": the reference's default; its VQA configs: "###")
+       :param label_smoothing: of the answer loss (0.1: modeling_llama.py:105)
+       :param score: "hf" (default) | "hip" -- who computes the answer losses of `multi_select`; see __init__
+       :param classify: "generate" (default) | "multi_select" -- what the base classifier of `Smooth` does with a batch; see __init__
+       :param candidates: the answers `classify="multi_select"` ranks (default: `label_map.answers`, in class-id order)
 
     `prompt` is a plain attribute: assigning a new prompt between two images (`clf.prompt = ...`) is the supported way to ask a
     per-image question (VQA: one question per image).  Under decode="graph" / "hip" every new prompt LENGTH captures a graph of its
@@ -478,7 +508,7 @@ class MiniGPT4Classifier:
 
     def __init__(self, encoder, llama_model, llama_tokenizer, prompt, label_map, max_new_tokens=20, max_batch=None,
                  generate_kwargs=None, decode="hf", prefill_linear="torch", prefill="model", ragged="hf", prompt_bucket=None,
-                 weights="fp16"):
+                 weights="fp16", end_sym="\n", label_smoothing=0.1, score="hf", classify="generate", candidates=None):
         self.encoder = encoder
         self.llama_model = llama_model
         self.llama_tokenizer = llama_tokenizer
@@ -526,6 +556,18 @@ class MiniGPT4Classifier:
         #   the model whose layer linears are `int8_state_dict(llama_model)` (tests/test_gpu_llm_int8.py).  With the model's own
         #   prefill the prompt would run on W and the steps on W': a mixed model, hence the ValueError.  Works with ragged = "hip" and
         #   prompt_bucket.  weights = "fp16" (default): the engine's own fp16 copies, as before.
+        # score = "hf" (default): `multi_select` / `answer_losses_from_embeds` run the model's own forward once per candidate over the
+        #   concatenated prompt + answer embeds, as the reference does (works on the CPU); counted in decode_stats["hf_score_forwards"].
+        # score = "hip" (with decode = "hip" AND prefill = "hip" only; anything else is a ValueError, never another engine): ONE native
+        #   prefill of the prompt, then every candidate on its cache (cgpt_llm_score, csrc/llm_score.hip: tail attention over the shared
+        #   prompt keys + fused label-smoothed cross-entropy); counted in decode_stats["hip_scores"].  Taken when the call is on the
+        #   device, every row shares one text and every row gets the same candidate list (the smoothing case); any other call takes the
+        #   "hf" path and is counted in decode_stats["hf_score_fallbacks"] -- the policy ragged = "hf" has for `generate`.  Works with
+        #   weights = "int8"; prompt_bucket does not apply (left-padded scoring does not exist).  Parity: tests/test_gpu_llm_score.py.
+        # classify = "multi_select": `__call__`, `sample_counts` and `sample_counts_pair` score `candidates` (default: the label map's
+        #   answers, in class-id order; at least 2, at most num_classes - 1) instead of generating: logits [B, num_classes] hold -loss in
+        #   column i for candidate i and -inf in column `other_id`, so every row votes for a known class.  classify = "generate"
+        #   (default): as before.
         assert decode in ("hf", "graph", "hip") and prefill_linear in ("torch", "cgpt")
         if prefill not in ("model", "hip"):
             raise ValueError(f'prefill={prefill!r}: expected "model" or "hip"')
@@ -547,6 +589,27 @@ class MiniGPT4Classifier:
             if ragged != "hip":
                 raise ValueError(f'prompt_bucket={prompt_bucket} needs ragged="hip" (got ragged={ragged!r}): only the native engine pads '
                                  "a prompt up to a bucket length")
+        if score not in ("hf", "hip"):
+            raise ValueError(f'score={score!r}: expected "hf" or "hip"')
+        if score == "hip" and (decode != "hip" or prefill != "hip"):
+            raise ValueError(f'score="hip" needs decode="hip" and prefill="hip" (got decode={decode!r}, prefill={prefill!r}): '
+                             "the candidates are scored on the cache the native prefill fills")
+        if classify not in ("generate", "multi_select"):
+            raise ValueError(f'classify={classify!r}: expected "generate" or "multi_select"')
+        if not 0.0 <= float(label_smoothing) < 1.0:
+            raise ValueError(f"label_smoothing={label_smoothing!r}: expected a value in [0, 1)")
+        if candidates is not None and classify != "multi_select":
+            raise ValueError('candidates need classify="multi_select" (classify="generate" maps free text through label_map)')
+        if classify == "multi_select":
+            candidates = list(label_map.answers if candidates is None else candidates)
+            if not 2 <= len(candidates) <= self.num_classes - 1:
+                raise ValueError(f'classify="multi_select" needs at least 2 and at most num_classes - 1 = {self.num_classes - 1} '
+                                 f"candidates (got {len(candidates)}): class id num_classes - 1 stays \"other\"")
+        self.end_sym = end_sym
+        self.label_smoothing = float(label_smoothing)
+        self.score = score
+        self.classify = classify
+        self.candidates = candidates
         self.decode = decode
         self.prefill = prefill
         self.ragged = ragged
@@ -563,6 +626,9 @@ class MiniGPT4Classifier:
         self.decode_stats = {"graph_replays": 0, "graph_captures": 0, "graph_evictions": 0, "hf_calls": 0, "hf_fallback_kwargs": 0,
                              "hip_steps": 0,                      # token steps enqueued on the native engine (decode = "hip")
                              "hip_prefills": 0,                   # native prefills enqueued (prefill = "hip"), counted alike
+                             "hf_score_forwards": 0,              # model forwards of score = "hf": one per candidate and call
+                             "hip_scores": 0,                     # native scoring passes (score = "hip"): one per call
+                             "hf_score_fallbacks": 0,             # score = "hip" calls that took the "hf" path (see __init__)
                              # bytes the native engine holds for weights, scales and scratch (None without one)
                              "weight_bytes": self._hip.weight_bytes if self._hip is not None else None}
 
@@ -850,15 +916,155 @@ class MiniGPT4Classifier:
         img_embeds, _ = self.encoder.encode_img(images)
         return self.generate_from_embeds(img_embeds, texts)
 
+    # ---- minigpt_base.py:451-467 with encode_img's output given
+    def _answer_tokens(self, text):
+        ids = self.llama_tokenizer(text + self.end_sym, return_tensors="pt", add_special_tokens=False).input_ids[0]
+        if ids.numel() < 1:
+            raise ValueError(f"candidate answer {text!r} + end_sym {self.end_sym!r} has no token")
+        return ids
+
+    def _prompt_embeds(self, prompt, img_embeds):
+        """bos + the prompt's segments around the rows' image embeds, [rows, L, hidden]: the bos is added explicitly
+        (minigpt_base.py:332-338) and every segment is tokenised with add_special_tokens=False (prompt_wrap, :118-129)."""
+        dev = img_embeds.device
+        segs = [self.embed_tokens(self.llama_tokenizer(seg, return_tensors="pt", add_special_tokens=False).input_ids.to(dev))
+                for seg in prompt.split(IMAGE_PLACEHOLDER)]
+        assert len(segs) == 2, "Unmatched numbers of image placeholders and images."
+        bos = self.embed_tokens(torch.full((1, 1), int(self.llama_tokenizer.bos_token_id), dtype=torch.long, device=dev))
+        rows = img_embeds.shape[0]
+        return torch.cat([bos.expand(rows, -1, -1), segs[0].expand(rows, -1, -1), img_embeds, segs[1].expand(rows, -1, -1)], dim=1)
+
+    @torch.no_grad()
+    def answer_losses_from_embeds(self, img_embeds, texts, answers):
+        """img_embeds [B, queries, hidden] + one prompt per row (or ONE str shared by all rows) + `answers[c][b]` = candidate c for
+        row b (answers[c] may be ONE str for all rows) -> losses [B, C] fp32: `multi_select`'s `all_losses`.
+
+        The loss law is the reference's, quirks included (`forward(..., reduction='none')`, minigpt_base.py:320-363 with
+        preparing_embedding :254-318 -- for the loss: :295-350 -- and modeling_llama.py:101-123):
+          * the sequence is bos + prompt segments around the image embeds + the tokens of `answer + end_sym`; prompt and answer are
+            tokenised with add_special_tokens=False, the bos is added explicitly (minigpt_base.py:298-305, :332-338);
+          * targets are the answer tokens only (-100 elsewhere, :343-350); an answer token equal to the tokenizer's pad id is masked
+            out too (:312-314);
+          * each token's loss is CrossEntropyLoss(reduction="none", label_smoothing=0.1) on `logits.float()` (modeling_llama.py:84,105);
+          * the per-row loss is `.view(B, -1).mean(1)` (modeling_llama.py:122-123): the SUM over the answer tokens divided by
+            (sequence length - 1), not by the number of answer tokens.  With L = prompt length including the bos and T_c = answer
+            tokens the divisor is L + T_c - 1, per candidate (one forward each); if candidate c's answers (or the prompts) differ in
+            length over the rows, T_c (L) is the longest, because `preparing_embedding` / `prompt_wrap` pad on the right (minigpt_base.py:132-143, :298-305).
+        score="hf": one forward of the model per candidate over the concatenated embeds (CPU tensors work).  score="hip": see __init__."""
+        dtype = self.embed_tokens(torch.zeros(1, 1, dtype=torch.long, device=img_embeds.device)).dtype
+        img_embeds = img_embeds.to(dtype)
+        B = img_embeds.shape[0]
+        prompts = [texts] * B if isinstance(texts, str) else list(texts)
+        assert len(prompts) == B
+        answers = [[a] * B if isinstance(a, str) else list(a) for a in answers]
+        assert answers and all(len(a) == B for a in answers), "answers[c][b]: one answer per candidate and row"
+        if self.score == "hip":
+            native = self._native_losses(img_embeds, prompts, answers)
+            if native is not None:
+                return native
+            self.decode_stats["hf_score_fallbacks"] += 1
+        dev = img_embeds.device
+        if len(set(prompts)) == 1:
+            cond = [self._prompt_embeds(prompts[0], img_embeds)]
+            cond_rows = [(0, i) for i in range(B)]                     # (group, row within the group)
+        else:
+            cond = [self._prompt_embeds(t, img_embeds[i:i + 1]) for i, t in enumerate(prompts)]
+            cond_rows = [(i, 0) for i in range(B)]
+        lens = [int(cond[g].shape[1]) for g, _ in cond_rows]
+        Lmax = max(lens)
+        pad_id = getattr(self.llama_tokenizer, "pad_token_id", None)
+        pad_emb = self.embed_tokens(torch.tensor([[0 if pad_id is None else int(pad_id)]], device=dev))[0, 0]
+        loss_fct = torch.nn.CrossEntropyLoss(reduction="none", label_smoothing=self.label_smoothing)
+        losses = []
+        for cand in answers:
+            toks = {a: self._answer_tokens(a).to(dev) for a in set(cand)}
+            Tmax = max(int(t.numel()) for t in toks.values())
+            total = Lmax + Tmax
+            embs = pad_emb.expand(B, total, -1).clone()
+            mask = torch.zeros((B, total), dtype=torch.int, device=dev)
+            targets = torch.full((B, total), -100, dtype=torch.long, device=dev)
+            for b, (g, r) in enumerate(cond_rows):                     # prompt, then the answer right behind it, then padding
+                ids = toks[cand[b]]
+                n, T = lens[b], int(ids.numel())
+                embs[b, :n] = cond[g][r]
+                embs[b, n:n + T] = self.embed_tokens(ids[None])[0]
+                mask[b, :n + T] = 1
+                targets[b, n:n + T] = ids if pad_id is None else ids.masked_fill(ids == pad_id, -100)
+            logits = self.llama_model(inputs_embeds=embs, attention_mask=mask).logits.float()
+            self.decode_stats["hf_score_forwards"] += 1
+            V = logits.shape[-1]
+            tok_loss = loss_fct(logits[:, :-1].reshape(-1, V), targets[:, 1:].reshape(-1))
+            losses.append(tok_loss.view(B, -1).mean(1))
+        return torch.stack(losses, dim=1)
+
+    def _native_losses(self, img_embeds, prompts, answers):
+        """score="hip": [B, C] losses from one native prefill and one native scoring pass, or None where the call is not the native
+        path's (off the device, per-row texts or candidates, more rows / candidates / tokens than the engine takes, an answer token
+        equal to the pad id, which the reference masks out)."""
+        B = img_embeds.shape[0]
+        hip = self._hip
+        if not img_embeds.is_cuda or len(set(prompts)) != 1 or any(len(set(a)) != 1 for a in answers):
+            return None
+        toks = [self._answer_tokens(a[0]) for a in answers]
+        lens = [int(t.numel()) for t in toks]
+        pad_id = getattr(self.llama_tokenizer, "pad_token_id", None)
+        embs = self._prompt_embeds(prompts[0], img_embeds).contiguous()
+        L, Tmax = int(embs.shape[1]), max(lens)
+        if (B > self.max_batch or len(toks) > hip.MAX_CANDS or sum(t - 1 for t in lens) > hip.MAX_TAIL or L + Tmax - 1 > hip.MAX_LEN
+                or (pad_id is not None and any(bool((t == pad_id).any()) for t in toks))):
+            return None
+        table = torch.zeros((len(toks), Tmax), dtype=torch.long)
+        for c, t in enumerate(toks):
+            table[c, :lens[c]] = t
+        shape = (B, hip.heads, L, 128)                                 # the prompt's rows only: scoring appends nothing
+        k_bufs = [embs.new_empty(shape) for _ in range(hip.layers)]
+        v_bufs = [embs.new_empty(shape) for _ in range(hip.layers)]
+        first = hip.prefill(embs, k_bufs, v_bufs)
+        sums = hip.score(first, L, table.to(embs.device), lens, self.label_smoothing, k_bufs, v_bufs)
+        self.decode_stats["hip_prefills"] += 1
+        self.decode_stats["hip_scores"] += 1
+        # the reference runs one forward per candidate, so each candidate's divisor is its own sequence length - 1
+        return sums / torch.tensor([float(L + t - 1) for t in lens], device=sums.device)
+
+    @torch.no_grad()
+    def multi_select(self, images, texts, answers, num_cand=None):
+        """`MiniGPTBase.multi_select(images, texts, answers, num_cand=None)` (minigpt_base.py:451-467): candidate ranks per row, best
+        first -- `argsort` of the [B, C] answer losses (see `answer_losses_from_embeds` for the loss law), entries at or after
+        `num_cand[i]` set to 9999 first."""
+        img_embeds, _ = self.encoder.encode_img(images)
+        losses = self.answer_losses_from_embeds(img_embeds, texts, answers)
+        if num_cand is not None:
+            for i in range(losses.shape[0]):
+                losses[i, int(num_cand[i]):] = 9999
+        return torch.argsort(losses, dim=-1).tolist()
+
     # ---- base classifier: [B,3,H,W] -> [B,num_classes] one-hot logits (smoothing.py:21,97)
     def _logits(self, answers, device):
         self.last_answers = answers
         return self.label_map.one_hot_logits(answers, device)
 
+    def _classify_embeds(self, emb, device):
+        """One classifier batch from encode_img's output -> (logits [B, num_classes] on `device`, the rows' answer texts).
+        classify="generate": one-hot of the generated answer's class.  classify="multi_select": -loss of candidate i in column i,
+        -inf in column `other_id` (and in unused columns), so the top class is always a candidate."""
+        if self.classify == "generate":
+            answers = self.generate_from_embeds(emb, self.prompt)
+            return self.label_map.one_hot_logits(answers, device), answers
+        losses = self.answer_losses_from_embeds(emb, self.prompt, self.candidates)
+        logits = torch.full((losses.shape[0], self.num_classes), float("-inf"), dtype=torch.float32, device=losses.device)
+        logits[:, :losses.shape[1]] = -losses
+        answers = [self.candidates[i] for i in losses.argmin(dim=1).tolist()]
+        return logits.to(device), answers
+
     def __call__(self, images):
         out = []
         for lo in range(0, images.shape[0], self.max_batch):
-            out.append(self._logits(self.generate(images[lo:lo + self.max_batch], self.prompt), images.device))
+            if self.classify == "generate":
+                out.append(self._logits(self.generate(images[lo:lo + self.max_batch], self.prompt), images.device))
+                continue
+            emb, _ = self.encoder.encode_img(images[lo:lo + self.max_batch])
+            logits, self.last_answers = self._classify_embeds(emb, images.device)
+            out.append(logits)
         return torch.cat(out)
 
     def sample_counts_pair(self, x, first_a, num_a, first_b, num_b, batch_size, sigma, seed, law="gaussian"):
@@ -874,8 +1080,7 @@ class MiniGPT4Classifier:
         while done < total:
             nb = min(bs, total - done)
             emb = self._encode_noisy(x, first_a + done, nb, sigma, seed, law)
-            batch_answers = self.generate_from_embeds(emb, self.prompt)
-            logits = self.label_map.one_hot_logits(batch_answers, x.device)
+            logits, batch_answers = self._classify_embeds(emb, x.device)
             na = max(0, min(nb, num_a - done))                         # rows of this batch that belong to the selection range
             if na > 0:
                 vote(logits[:na], counts[0])
@@ -900,6 +1105,7 @@ class MiniGPT4Classifier:
         while done < num:
             nb = min(bs, num - done)
             emb = self._encode_noisy(x, first_sample + done, nb, sigma, seed, law)
-            vote(self._logits(self.generate_from_embeds(emb, self.prompt), x.device), counts)
+            logits, self.last_answers = self._classify_embeds(emb, x.device)
+            vote(logits, counts)
             done += nb
         return counts

@@ -434,6 +434,40 @@ cgpt_status cgpt_llm_greedy_ragged(cgpt_llm_handle h, const float* first_logits_
                                    int32_t num_eos, int64_t pad_id, void* const* k_ptrs_host, void* const* v_ptrs_host,
                                    int64_t kv_len_stride, int64_t* tokens_out_dev, float* step_logits_out_dev, void* stream);
 
+/* ---- Answer scoring: all candidates of a multiple-choice question on ONE prefilled prompt ----
+ * Replaces: `MiniGPTBase.multi_select` (minigpt_base.py:451-467), i.e. `forward(..., reduction='none')` (minigpt_base.py:320-363;
+ * modeling_llama.py:101-123) once per candidate: a whole forward over prompt + answer and
+ * CrossEntropyLoss(label_smoothing) on `logits.float()`.  Here cgpt_llm_prefill runs once and every candidate is scored on the
+ * cache rows it left: candidate c of T_c tokens adds T_c - 1 "tail rows" per prompt row (its tokens 0 .. T_c - 2 at rotary
+ * positions prompt_len ..), which run the layers like prefill rows but attend over the prompt's cache rows 0 .. prompt_len-1 and
+ * over the rotated keys / values of their own candidate's earlier tail rows.  Those exist in the workspace and on chip only.
+ *
+ * cgpt_llm_score_reserve: workspace for max_rows prompt rows with up to max_tail_rows tail rows each (sum over the candidates of
+ * T_c - 1; at most 64): the prefill workspace grown to max_rows x max_tail_rows token rows where it is smaller, fp16 logits of up
+ * to 4096 tail rows (more rows run lm_head and the cross-entropy in chunks) and the per-token losses.  Same rules as
+ * cgpt_llm_prefill_reserve: synchronises and allocates, so call it OUTSIDE any capture; idempotent; grows only; replaced buffers
+ * stay allocated until cgpt_llm_destroy; a failed growth leaves the handle as it was.  CGPT_ERR_INVALID for max_rows outside
+ * 1..max_batch or max_tail_rows outside 1..64. */
+cgpt_status cgpt_llm_score_reserve(cgpt_llm_handle h, int32_t max_rows, int32_t max_tail_rows);
+/* first_logits_dev: [B, vocab] fp32, the prefill's last-position logits (not modified).  cand_tokens_dev: DEVICE int64 [C, Tmax],
+ * row c holding the T_c = cand_lens_host[c] tokens of candidate c (the rest of the row is not read); cand_lens_host: HOST int32 [C],
+ * read when the call enqueues.  out_dev[b, c] (fp32 [B, C]) receives the SUM over candidate c's tokens of
+ *     ce = lse(z) - (1 - label_smoothing) z[token] - label_smoothing mean(z)
+ * with z the fp16 logits widened to fp32 (HF's `logits.float()`), all statistics in fp32: token 0 on first_logits_dev, token j >= 1
+ * on the logits of tail row j - 1.  The caller divides (the reference's `.view(B, -1).mean(1)` divides by sequence length - 1).
+ * A token id outside 0 .. vocab-1 reads as 0 (the host cannot check device contents without a sync).
+ * Reads cache rows 0 .. prompt_len-1 of k_ptrs_host[l] / v_ptrs_host[l] (layout and tables as cgpt_llm_step) and WRITES NO CACHE ROW:
+ * after the call the same cache serves cgpt_llm_greedy or another cgpt_llm_score.  A (row, candidate) result depends on that row's
+ * cache and that candidate's tokens only -- not on B, C, the other candidates or their order; fixed summation orders, no atomics.
+ * Enqueues only: no host sync, no allocation, no host->device copy (the lengths travel as kernel arguments).
+ * CGPT_ERR_INVALID, before any device call: a null handle or pointer, C outside 1..64, Tmax < 1, a length outside 1..Tmax, more than
+ * 64 tail rows per prompt row, label_smoothing outside [0, 1), prompt_len < 1, prompt_len + Tmax - 1 > max_len, prompt_len >
+ * kv_len_stride, B outside 1..max_batch, a null table / buffer.  CGPT_ERR_STATE while weights are missing or when the call exceeds
+ * what cgpt_llm_score_reserve reserved. */
+cgpt_status cgpt_llm_score(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len,
+                           const int64_t* cand_tokens_dev, const int32_t* cand_lens_host, int32_t C, int32_t Tmax, float label_smoothing,
+                           void* const* k_ptrs_host, void* const* v_ptrs_host, int64_t kv_len_stride, float* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
