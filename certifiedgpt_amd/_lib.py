@@ -105,6 +105,8 @@ SIGNATURES = {
     "cgpt_llm_prefill_ragged": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _I64, _P, _P]),
     "cgpt_llm_step_ragged": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _I64, _P, _P]),
     "cgpt_llm_greedy_ragged": (_I32, [_P, _P, _I32, _I32, _P, _I32, _I32, _P, _I32, _I64, _P, _P, _I64, _P, _P, _P]),
+    "cgpt_llm_set_early_stop": (_I32, [_P, _I32]),
+    "cgpt_llm_live_steps": (_I32, [_P, C.POINTER(_I32), _P]),
     "cgpt_llm_score_reserve": (_I32, [_P, _I32, _I32]),
     "cgpt_llm_score": (_I32, [_P, _P, _I32, _I32, _P, _P, _I32, _I32, _F, _P, _P, _I64, _P, _P]),
 }

@@ -60,9 +60,17 @@ __device__ __forceinline__ float mul_f16(float a, float b) {
     return r;
 }
 
+// Early stop (cgpt_llm_set_early_stop): every kernel of a token step exists twice.  GUARD = true reads *live -- one
+// int, uniform over the grid, written by llm_live_kernel earlier on the same stream -- before any load, LDS write or barrier and
+// returns when it is 0.  GUARD = false never looks at `live` (null) and is the kernel as it was: cgpt_llm_step, the prefill's tail,
+// the scoring pass and a greedy call with early stop off take it.
+
 // h[b, :] = embed[token[b], :].  A token outside the table reads row 0 (never out of bounds).
+template <bool GUARD>
 __global__ __launch_bounds__(256) void llm_embed_kernel(const long long* __restrict__ tokens, const half_t* __restrict__ table,
-                                                        int vocab, int hidden, half_t* __restrict__ h) {
+                                                        int vocab, int hidden, half_t* __restrict__ h, const int* __restrict__ live) {
+    if constexpr (GUARD)
+        if (*live == 0) return;
     long long t = tokens[blockIdx.x];
     if (t < 0 || t >= vocab) t = 0;
     const h16x8* src = reinterpret_cast<const h16x8*>(table + (int64_t)t * hidden);
@@ -72,9 +80,12 @@ __global__ __launch_bounds__(256) void llm_embed_kernel(const long long* __restr
 
 // LlamaRMSNorm: y = weight * fp16(x * rsqrt(mean(x^2) + eps)), statistics in fp32, both products rounded to fp16.
 // One workgroup per row; the sum runs in a fixed order (per-thread strided, wave butterfly, 4 wave sums in order).
+template <bool GUARD>
 __global__ __launch_bounds__(256) void llm_rmsnorm_kernel(const half_t* __restrict__ x, const half_t* __restrict__ w, int hidden,
-                                                          float eps, half_t* __restrict__ y) {
+                                                          float eps, half_t* __restrict__ y, const int* __restrict__ live) {
     __shared__ float wsum[4];
+    if constexpr (GUARD)
+        if (*live == 0) return;
     const half_t* xr = x + (int64_t)blockIdx.x * hidden;
     half_t* yr = y + (int64_t)blockIdx.x * hidden;
     float ss = 0.0f;
@@ -116,11 +127,14 @@ __global__ __launch_bounds__(64) void llm_rope_table_kernel(const float* __restr
 // RAGGED (left-padded rows, cgpt_llm_step_ragged): the token sits at buffer position `bufpos` of a row whose first real position is
 // s = starts[b] (clamped into 0 .. smax; smax = the prompt's last buffer position, so that prefill and steps clamp alike).  The head's cache pointers move by s and `pos` stands for bufpos - s: rotary row
 // bufpos - s, keys s .. bufpos walked in groups of four from s -- the unpadded row's operations in the unpadded row's order.
-template <bool RAGGED>
+template <bool RAGGED, bool GUARD>
 __global__ __launch_bounds__(64) void llm_attn_kernel(const half_t* __restrict__ qkv, int hidden, int heads, half_t* Kc, half_t* Vc,
                                                       int64_t len_stride, const half_t* __restrict__ rope, int bufpos,
-                                                      half_t* __restrict__ out, const int* __restrict__ starts, int smax) {
+                                                      half_t* __restrict__ out, const int* __restrict__ starts, int smax,
+                                                      const int* __restrict__ live) {
     extern __shared__ float asmem[];                   // [128] rotated query, [128 + 128] halfs: the new key and value, [pos + 1] scores
+    if constexpr (GUARD)
+        if (*live == 0) return;
     float* qs = asmem;
     half_t* knew = reinterpret_cast<half_t*>(asmem + HD);
     half_t* vnew = knew + HD;
@@ -272,13 +286,26 @@ struct EosIds { long long id[MAX_EOS]; int n; };
 // `mask_eos` (the first min_new_tokens steps), first-max arg-max, pad once the row has produced an EOS.
 //   dst != null: the (masked) logits are also written there (row stride ldd); dst may be src.
 //   first != 0:  every row starts unfinished (step 0)
+// GUARD (early stop): a select other than the first that reads *live == 0 -- every row has produced an EOS -- is a dead select: no
+// vocabulary scan, no logits copy, `unfinished` left as it is (all zeros); it writes the pad id, which is what the scan would have
+// ended in.  The first select never reads `live` (it holds the previous call's value until llm_live_kernel has run).
+template <bool GUARD>
 __global__ __launch_bounds__(256) void llm_select_kernel(const float* src, int64_t lds, float* dst, int64_t ldd, int vocab,
                                                          int mask_eos, EosIds eos, long long pad, int first, int* __restrict__ unfinished,
                                                          long long* __restrict__ tokens_out, int64_t ld_tokens,
-                                                         long long* __restrict__ next_tok) {
+                                                         long long* __restrict__ next_tok, const int* __restrict__ live) {
     __shared__ float bv[4];
     __shared__ int bi[4];
     const int row = blockIdx.x;
+    if constexpr (GUARD) {
+        if (!first && *live == 0) {
+            if (threadIdx.x == 0) {
+                tokens_out[(int64_t)row * ld_tokens] = pad;
+                next_tok[row] = pad;
+            }
+            return;
+        }
+    }
     const float* s = src + (int64_t)row * lds;
     float* d = dst ? dst + (int64_t)row * ldd : nullptr;
     float best = -INFINITY;
@@ -312,6 +339,20 @@ __global__ __launch_bounds__(256) void llm_select_kernel(const float* src, int64
     }
 }
 
+// The reduction behind early stop, ONE workgroup of 256 threads after a select (rows <= 256): live = any(unfinished[0 .. rows)), and
+// live_steps counts the token steps of the call that run: reset by the first select's launch, + 1 when a step follows this select
+// (`more`) and some row is unfinished.  The next launches of the stream read `live` (the kernel boundary orders the store).
+__global__ __launch_bounds__(256) void llm_live_kernel(const int* __restrict__ unfinished, int rows, int first, int more,
+                                                       int* __restrict__ live, int* __restrict__ live_steps) {
+    const int u = (int)threadIdx.x < rows ? unfinished[threadIdx.x] : 0;
+    const int any = __syncthreads_or(u) ? 1 : 0;
+    if (threadIdx.x == 0) {
+        const int steps = first ? 0 : *live_steps;
+        *live = any;
+        *live_steps = steps + (any & more);
+    }
+}
+
 // One fused layer matrix [up256(N)][K]: fp16 (`w`) on an fp16 handle; int8 `q` with one fp16 scale per row (`s`) on an int8 handle.
 struct Mat {
     half_t* w = nullptr;
@@ -333,6 +374,11 @@ struct cgpt_llm {
     float *slabs = nullptr, *logits = nullptr;
     long long* tok = nullptr;
     int* unfinished = nullptr;
+    // early stop (cgpt_llm_set_early_stop): `live` = 1 while some row of the running greedy call is unfinished, `live_steps` = the
+    // token steps of that call that ran; both written by llm_live_kernel only.  With early stop off nothing on the device maintains
+    // them: the last call's count (num_new - 1, every step runs) is kept in `off_steps`, and `last_on` says which of the two holds.
+    int *live = nullptr, *live_steps = nullptr;
+    int early_stop = 0, last_on = 0, off_steps = 0;
     std::set<std::string> loaded;
     size_t expected = 0;
     std::vector<void*> allocs;
@@ -379,45 +425,48 @@ cgpt_status check_cache(cgpt_llm* m, const char* who, int B, int last_pos, void*
 #define LAUNCHED() HIPCHK(hipGetLastError())
 
 cgpt_status gemm(cgpt_llm* m, int epi, const half_t* A, int K, const Mat& W, int N, void* out, int64_t ldo, const half_t* resid,
-                 int B, hipStream_t st) {
+                 int B, hipStream_t st, const int* live = nullptr) {
     DecodeGemmParams p{};
     p.A = A; p.lda = K; p.W = W.q ? reinterpret_cast<const half_t*>(W.q) : W.w; p.ldw = K; p.out = out; p.ldo = ldo; p.resid = resid;
     p.ldr = ldo; p.slabs = m->slabs;
     p.M = B; p.N = N; p.K = K;
-    HIPCHK(launch_decode_gemm(epi, p, st, W.q ? W.s : nullptr));
+    HIPCHK(launch_decode_gemm(epi, p, st, W.q ? W.s : nullptr, live));
     return CGPT_OK;
 }
 
 // One token step on rows 0..B-1: tokens -> logits (fp32, row stride ld_logits).
 // starts (device, or null): per-row left padding, clamped into 0 .. smax, see llm_attn_kernel.
+// GUARD: every launch is the guarded instantiation on m->live (a greedy call with early stop on); otherwise the plain kernels.
+template <bool GUARD>
 cgpt_status run_step(cgpt_llm* m, const long long* tokens, int B, int pos, const int32_t* starts, int smax, void* const* kp, void* const* vp,
                      int64_t len_stride, float* logits, int64_t ld_logits, hipStream_t st) {
     const cgpt_llm_config& c = m->cfg;
     const int H = c.hidden;
-    hipLaunchKernelGGL(llm_embed_kernel, dim3(B), dim3(256), 0, st, tokens, m->embed, c.vocab, H, m->h);
+    const int* live = GUARD ? m->live : nullptr;
+    hipLaunchKernelGGL(llm_embed_kernel<GUARD>, dim3(B), dim3(256), 0, st, tokens, m->embed, c.vocab, H, m->h, live);
     LAUNCHED();
     const size_t attn_lds = (size_t)(2 * HD + pos + 1) * sizeof(float);      // scores of the longest row a batch can hold
     for (int l = 0; l < c.layers; ++l) {
         const Layer& L = m->layers[l];
-        hipLaunchKernelGGL(llm_rmsnorm_kernel, dim3(B), dim3(256), 0, st, m->h, L.ln1, H, c.rms_eps, m->xn);
+        hipLaunchKernelGGL(llm_rmsnorm_kernel<GUARD>, dim3(B), dim3(256), 0, st, m->h, L.ln1, H, c.rms_eps, m->xn, live);
         LAUNCHED();
-        CGCHK(gemm(m, DEC_F16, m->xn, H, L.wqkv, 3 * H, m->qkv, 3 * H, nullptr, B, st));
+        CGCHK(gemm(m, DEC_F16, m->xn, H, L.wqkv, 3 * H, m->qkv, 3 * H, nullptr, B, st, live));
         if (starts)
-            hipLaunchKernelGGL(llm_attn_kernel<true>, dim3(B * c.heads), dim3(64), attn_lds, st, m->qkv, H, c.heads, (half_t*)kp[l],
-                               (half_t*)vp[l], len_stride, m->rope, pos, m->attn, starts, smax);
+            hipLaunchKernelGGL((llm_attn_kernel<true, GUARD>), dim3(B * c.heads), dim3(64), attn_lds, st, m->qkv, H, c.heads, (half_t*)kp[l],
+                               (half_t*)vp[l], len_stride, m->rope, pos, m->attn, starts, smax, live);
         else
-            hipLaunchKernelGGL(llm_attn_kernel<false>, dim3(B * c.heads), dim3(64), attn_lds, st, m->qkv, H, c.heads, (half_t*)kp[l],
-                               (half_t*)vp[l], len_stride, m->rope, pos, m->attn, nullptr, 0);
+            hipLaunchKernelGGL((llm_attn_kernel<false, GUARD>), dim3(B * c.heads), dim3(64), attn_lds, st, m->qkv, H, c.heads, (half_t*)kp[l],
+                               (half_t*)vp[l], len_stride, m->rope, pos, m->attn, nullptr, 0, live);
         LAUNCHED();
-        CGCHK(gemm(m, DEC_F16_RESID, m->attn, H, L.wo, H, m->h, H, m->h, B, st));
-        hipLaunchKernelGGL(llm_rmsnorm_kernel, dim3(B), dim3(256), 0, st, m->h, L.ln2, H, c.rms_eps, m->xn);
+        CGCHK(gemm(m, DEC_F16_RESID, m->attn, H, L.wo, H, m->h, H, m->h, B, st, live));
+        hipLaunchKernelGGL(llm_rmsnorm_kernel<GUARD>, dim3(B), dim3(256), 0, st, m->h, L.ln2, H, c.rms_eps, m->xn, live);
         LAUNCHED();
-        CGCHK(gemm(m, DEC_SWIGLU, m->xn, H, L.wgu, 2 * c.mlp, m->act, c.mlp, nullptr, B, st));
-        CGCHK(gemm(m, DEC_F16_RESID, m->act, c.mlp, L.wdown, H, m->h, H, m->h, B, st));
+        CGCHK(gemm(m, DEC_SWIGLU, m->xn, H, L.wgu, 2 * c.mlp, m->act, c.mlp, nullptr, B, st, live));
+        CGCHK(gemm(m, DEC_F16_RESID, m->act, c.mlp, L.wdown, H, m->h, H, m->h, B, st, live));
     }
-    hipLaunchKernelGGL(llm_rmsnorm_kernel, dim3(B), dim3(256), 0, st, m->h, m->norm, H, c.rms_eps, m->xn);
+    hipLaunchKernelGGL(llm_rmsnorm_kernel<GUARD>, dim3(B), dim3(256), 0, st, m->h, m->norm, H, c.rms_eps, m->xn, live);
     LAUNCHED();
-    return gemm(m, DEC_F32, m->xn, H, Mat{m->lm_head}, c.vocab, logits, ld_logits, nullptr, B, st);
+    return gemm(m, DEC_F32, m->xn, H, Mat{m->lm_head}, c.vocab, logits, ld_logits, nullptr, B, st, live);
 }
 
 // C[M, N] = A[M, K] * W[N, K]^T, fp16 result of the fp32 sum, through the large-shape GEMM of the ViT (gemm.hip / gemm9.hip).
@@ -581,6 +630,8 @@ cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
     za(MAX_ROWS * V * sizeof(float), &m->logits);
     za(MAX_ROWS * sizeof(long long), &m->tok);
     za(MAX_ROWS * sizeof(int), &m->unfinished);
+    za(sizeof(int), &m->live);
+    za(sizeof(int), &m->live_steps);
     size_t slab = 0;
     const int shapes[5][2] = {{(int)(3 * H), (int)H}, {(int)H, (int)H}, {(int)(2 * F), (int)H}, {(int)H, (int)F}, {(int)V, (int)H}};
     for (auto& sh : shapes) slab = std::max(slab, decode_gemm_slab_bytes(sh[0], sh[1]));
@@ -676,7 +727,7 @@ static cgpt_status llm_step_entry(const char* who, cgpt_llm_handle h, const int6
     CGCHK(ready(h, who));
     HIPCHK(hipSetDevice(h->cfg.device));
     CGCHK(check_cache(h, who, B, pos, k_ptrs_host, v_ptrs_host, kv_len_stride));
-    return run_step(h, (const long long*)tokens_dev, B, pos, starts_dev, pos, k_ptrs_host, v_ptrs_host, kv_len_stride, logits_dev,
+    return run_step<false>(h, (const long long*)tokens_dev, B, pos, starts_dev, pos, k_ptrs_host, v_ptrs_host, kv_len_stride, logits_dev,
                     h->cfg.vocab, (hipStream_t)stream);
 }
 
@@ -712,6 +763,9 @@ static cgpt_status llm_greedy_entry(const char* who_c, cgpt_llm_handle h, const 
     for (int e = 0; e < num_eos; ++e) eos.id[e] = eos_ids_host[e];
     const int V = h->cfg.vocab;
     const int64_t ld_out = (int64_t)num_new * V;
+    const bool early = h->early_stop != 0;                 // read now: a captured call keeps the setting it was captured under
+    h->last_on = early ? 1 : 0;
+    h->off_steps = num_new - 1;
     for (int i = 0; i < num_new; ++i) {
         const float* src;
         int64_t lds;
@@ -721,13 +775,26 @@ static cgpt_status llm_greedy_entry(const char* who_c, cgpt_llm_handle h, const 
         const int mask = (i < min_new && num_eos > 0) ? 1 : 0;
         float* dst = nullptr;
         if (step_logits_out_dev && (i == 0 || mask)) dst = step_logits_out_dev + (int64_t)i * V;
-        hipLaunchKernelGGL(llm_select_kernel, dim3(B), dim3(256), 0, st, src, lds, dst, ld_out, V, mask, eos, (long long)pad_id,
-                           i == 0 ? 1 : 0, h->unfinished, (long long*)tokens_out_dev + i, (int64_t)num_new, h->tok);
+        if (early) {
+            hipLaunchKernelGGL(llm_select_kernel<true>, dim3(B), dim3(256), 0, st, src, lds, dst, ld_out, V, mask, eos, (long long)pad_id,
+                               i == 0 ? 1 : 0, h->unfinished, (long long*)tokens_out_dev + i, (int64_t)num_new, h->tok, h->live);
+            LAUNCHED();
+            hipLaunchKernelGGL(llm_live_kernel, dim3(1), dim3(256), 0, st, h->unfinished, B, i == 0 ? 1 : 0, i + 1 < num_new ? 1 : 0,
+                               h->live, h->live_steps);
+        } else {
+            hipLaunchKernelGGL(llm_select_kernel<false>, dim3(B), dim3(256), 0, st, src, lds, dst, ld_out, V, mask, eos, (long long)pad_id,
+                               i == 0 ? 1 : 0, h->unfinished, (long long*)tokens_out_dev + i, (int64_t)num_new, h->tok, nullptr);
+        }
         LAUNCHED();
         if (i + 1 == num_new) break;
         float* next = step_logits_out_dev ? step_logits_out_dev + (int64_t)(i + 1) * V : h->logits;
-        CGCHK(run_step(h, h->tok, B, prompt_len + i, starts_dev, prompt_len - 1, k_ptrs_host, v_ptrs_host, kv_len_stride, next,
-                       step_logits_out_dev ? ld_out : (int64_t)V, st));
+        const int64_t ld_next = step_logits_out_dev ? ld_out : (int64_t)V;
+        if (early)
+            CGCHK(run_step<true>(h, h->tok, B, prompt_len + i, starts_dev, prompt_len - 1, k_ptrs_host, v_ptrs_host, kv_len_stride, next,
+                                 ld_next, st));
+        else
+            CGCHK(run_step<false>(h, h->tok, B, prompt_len + i, starts_dev, prompt_len - 1, k_ptrs_host, v_ptrs_host, kv_len_stride, next,
+                                  ld_next, st));
     }
     return CGPT_OK;
 }
@@ -747,6 +814,23 @@ cgpt_status cgpt_llm_greedy_ragged(cgpt_llm_handle h, const float* first_logits_
     if (!starts_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_greedy_ragged: null starts_dev");
     return llm_greedy_entry("cgpt_llm_greedy_ragged", h, first_logits_dev, B, prompt_len, starts_dev, num_new, min_new, eos_ids_host,
                             num_eos, pad_id, k_ptrs_host, v_ptrs_host, kv_len_stride, tokens_out_dev, step_logits_out_dev, stream);
+}
+
+cgpt_status cgpt_llm_set_early_stop(cgpt_llm_handle h, int32_t on) {
+    if (!h) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_set_early_stop: null handle");
+    if (on != 0 && on != 1) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_set_early_stop: the value must be 0 or 1");
+    h->early_stop = on;
+    return CGPT_OK;
+}
+
+cgpt_status cgpt_llm_live_steps(cgpt_llm_handle h, int32_t* out_host, void* stream) {
+    if (!h || !out_host) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_live_steps: null argument");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    int v = h->off_steps;
+    if (h->last_on) HIPCHK(hipMemcpy(&v, h->live_steps, sizeof(int), hipMemcpyDeviceToHost));
+    *out_host = v;
+    return CGPT_OK;
 }
 
 // Grows the prefill workspace to `rows` token rows (a multiple of 256); `who` names the entry in messages.

@@ -20,6 +20,10 @@
 // row.  Only the W staging differs: a thread loads the 8 bytes of its chunk, converts them to fp16 exactly (|q| <= 127) and forms
 // W'[n, k] = fp16(q) * s_n with ONE packed fp16 multiply per pair -- the thread's row never changes, so s_n is one register loaded
 // once -- and writes the same swizzled LDS image.  From there on the kernel is the fp16 kernel on W' (DESIGN.md 4.4.3).
+//
+// GUARD (the last template parameter, cgpt_llm_set_early_stop): the kernel reads *live -- one int, uniform over the
+// grid, written by an earlier launch of the same stream -- before anything else and returns when it is 0: no load, no LDS write, no
+// barrier, no store.  GUARD = false never looks at `live` (null) and is the kernel as it was: every other caller takes it.
 #include "gemm_common.h"
 #include "llm.h"
 
@@ -68,9 +72,12 @@ __device__ __forceinline__ f16x8 dequant8(i8x8 q, half_t s) {
     return v;
 }
 
-template <int EPI, bool W8>
-__global__ __launch_bounds__(512) void decode_gemm_kernel(DecodeGemmParams p, int tiles_n, int splitk, const half_t* __restrict__ wscale) {
+template <int EPI, bool W8, bool GUARD>
+__global__ __launch_bounds__(512) void decode_gemm_kernel(DecodeGemmParams p, int tiles_n, int splitk, const half_t* __restrict__ wscale,
+                                                          const int* __restrict__ live) {
     extern __shared__ __attribute__((aligned(16))) half_t dsmem[];   // [2 stages][A 256x64 | W 64x64]
+    if constexpr (GUARD)
+        if (*live == 0) return;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -187,8 +194,10 @@ __global__ __launch_bounds__(512) void decode_gemm_kernel(DecodeGemmParams p, in
 }
 
 // out = epilogue(slab 0 + slab 1 + ... + slab splitk-1), summed in that order.  One thread per 4 consecutive output columns.
-template <int EPI>
-__global__ __launch_bounds__(256) void decode_combine_kernel(DecodeGemmParams p, int splitk) {
+template <int EPI, bool GUARD>
+__global__ __launch_bounds__(256) void decode_combine_kernel(DecodeGemmParams p, int splitk, const int* __restrict__ live) {
+    if constexpr (GUARD)
+        if (*live == 0) return;
     const int ncols = (EPI == DEC_SWIGLU) ? p.N / 2 : p.N;
     const int per_row = ncols / 4;
     const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -214,33 +223,59 @@ __global__ __launch_bounds__(256) void decode_combine_kernel(DecodeGemmParams p,
     }
 }
 
-template <int EPI, bool W8>
-hipError_t launch_epi(const DecodeGemmParams& p, int splitk, const half_t* wscale, hipStream_t stream) {
+template <int EPI, bool W8, bool GUARD>
+hipError_t launch_epi(const DecodeGemmParams& p, int splitk, const half_t* wscale, const int* live, hipStream_t stream) {
     const int tiles_n = p.N / DBN;
-    hipLaunchKernelGGL((decode_gemm_kernel<EPI, W8>), dim3(tiles_n * splitk), dim3(512), DLDS_BYTES, stream, p, tiles_n, splitk, wscale);
+    hipLaunchKernelGGL((decode_gemm_kernel<EPI, W8, GUARD>), dim3(tiles_n * splitk), dim3(512), DLDS_BYTES, stream, p, tiles_n, splitk, wscale,
+                       live);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || splitk == 1) return e;
     const int ncols = (EPI == DEC_SWIGLU) ? p.N / 2 : p.N;
     const int64_t threads = (int64_t)p.M * (ncols / 4);
-    hipLaunchKernelGGL(decode_combine_kernel<EPI>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, p, splitk);
+    hipLaunchKernelGGL((decode_combine_kernel<EPI, GUARD>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, p, splitk, live);
     return hipGetLastError();
 }
 
-}  // namespace
+template <bool GUARD>
+hipError_t launch_guard(int epilogue, const DecodeGemmParams& p, int splitk, const half_t* wscale, const int* live, hipStream_t stream) {
+    if (wscale) {                                          // int8 weights: the three layer epilogues (lm_head stays fp16)
+        switch (epilogue) {
+            case DEC_F16: return launch_epi<DEC_F16, true, GUARD>(p, splitk, wscale, live, stream);
+            case DEC_F16_RESID: return launch_epi<DEC_F16_RESID, true, GUARD>(p, splitk, wscale, live, stream);
+            case DEC_SWIGLU: return launch_epi<DEC_SWIGLU, true, GUARD>(p, splitk, wscale, live, stream);
+            default: return hipErrorInvalidValue;
+        }
+    }
+    switch (epilogue) {
+        case DEC_F16: return launch_epi<DEC_F16, false, GUARD>(p, splitk, nullptr, live, stream);
+        case DEC_F16_RESID: return launch_epi<DEC_F16_RESID, false, GUARD>(p, splitk, nullptr, live, stream);
+        case DEC_SWIGLU: return launch_epi<DEC_SWIGLU, false, GUARD>(p, splitk, nullptr, live, stream);
+        case DEC_F32: return launch_epi<DEC_F32, false, GUARD>(p, splitk, nullptr, live, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
 
-hipError_t decode_gemm_prepare() {
-    const void* kernels[7] = {reinterpret_cast<const void*>(decode_gemm_kernel<DEC_F16, false>),
-                              reinterpret_cast<const void*>(decode_gemm_kernel<DEC_F16_RESID, false>),
-                              reinterpret_cast<const void*>(decode_gemm_kernel<DEC_SWIGLU, false>),
-                              reinterpret_cast<const void*>(decode_gemm_kernel<DEC_F32, false>),
-                              reinterpret_cast<const void*>(decode_gemm_kernel<DEC_F16, true>),
-                              reinterpret_cast<const void*>(decode_gemm_kernel<DEC_F16_RESID, true>),
-                              reinterpret_cast<const void*>(decode_gemm_kernel<DEC_SWIGLU, true>)};
+template <bool GUARD>
+hipError_t prepare_guard() {
+    const void* kernels[7] = {reinterpret_cast<const void*>(decode_gemm_kernel<DEC_F16, false, GUARD>),
+                              reinterpret_cast<const void*>(decode_gemm_kernel<DEC_F16_RESID, false, GUARD>),
+                              reinterpret_cast<const void*>(decode_gemm_kernel<DEC_SWIGLU, false, GUARD>),
+                              reinterpret_cast<const void*>(decode_gemm_kernel<DEC_F32, false, GUARD>),
+                              reinterpret_cast<const void*>(decode_gemm_kernel<DEC_F16, true, GUARD>),
+                              reinterpret_cast<const void*>(decode_gemm_kernel<DEC_F16_RESID, true, GUARD>),
+                              reinterpret_cast<const void*>(decode_gemm_kernel<DEC_SWIGLU, true, GUARD>)};
     for (const void* k : kernels) {
         const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, DLDS_BYTES);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t decode_gemm_prepare() {
+    const hipError_t e = prepare_guard<false>();
+    return e != hipSuccess ? e : prepare_guard<true>();
 }
 
 int decode_gemm_splitk(int N, int K) {
@@ -255,27 +290,13 @@ size_t decode_gemm_slab_bytes(int N, int K) {
     return s > 1 ? (size_t)s * DBM * (size_t)N * sizeof(float) : 0;
 }
 
-hipError_t launch_decode_gemm(int epilogue, const DecodeGemmParams& p, hipStream_t stream, const half_t* wscale) {
+hipError_t launch_decode_gemm(int epilogue, const DecodeGemmParams& p, hipStream_t stream, const half_t* wscale, const int* live) {
     if (p.M < 1 || p.M > DBM || p.N < DBN || p.N % DBN || p.K < DBK || p.K % DBK || !p.A || !p.W || !p.out)
         return hipErrorInvalidValue;
     if (epilogue == DEC_F16_RESID && !p.resid) return hipErrorInvalidValue;
     const int splitk = decode_gemm_splitk(p.N, p.K);
     if (splitk > 1 && !p.slabs) return hipErrorInvalidValue;
-    if (wscale) {                                          // int8 weights: the three layer epilogues (lm_head stays fp16)
-        switch (epilogue) {
-            case DEC_F16: return launch_epi<DEC_F16, true>(p, splitk, wscale, stream);
-            case DEC_F16_RESID: return launch_epi<DEC_F16_RESID, true>(p, splitk, wscale, stream);
-            case DEC_SWIGLU: return launch_epi<DEC_SWIGLU, true>(p, splitk, wscale, stream);
-            default: return hipErrorInvalidValue;
-        }
-    }
-    switch (epilogue) {
-        case DEC_F16: return launch_epi<DEC_F16, false>(p, splitk, nullptr, stream);
-        case DEC_F16_RESID: return launch_epi<DEC_F16_RESID, false>(p, splitk, nullptr, stream);
-        case DEC_SWIGLU: return launch_epi<DEC_SWIGLU, false>(p, splitk, nullptr, stream);
-        case DEC_F32: return launch_epi<DEC_F32, false>(p, splitk, nullptr, stream);
-        default: return hipErrorInvalidValue;
-    }
+    return live ? launch_guard<true>(epilogue, p, splitk, wscale, live, stream) : launch_guard<false>(epilogue, p, splitk, wscale, nullptr, stream);
 }
 
 }  // namespace cgpt

@@ -313,12 +313,14 @@ class _HipDecoder:
     stream -- no host sync, capturable -- on the K/V buffers the prefill filled, in place."""
     MAX_LEN = 4096                                                     # positions the rotary table covers (prompt + new tokens)
 
-    def __init__(self, llama_model, max_batch, weights="fp16"):
+    def __init__(self, llama_model, max_batch, weights="fp16", early_stop=False):
         import ctypes as C
         from . import _lib
         if weights not in _lib.LLM_WEIGHT_FORMATS:
             raise ValueError(f'weights={weights!r}: expected "fp16" or "int8"')
         self.weights = weights
+        self.early_stop = bool(early_stop)
+        self._greedy_ran = False                                       # live_steps has nothing to report before the first `greedy`
         bad = hip_decode_unsupported(llama_model, max_batch)
         if bad:
             raise ValueError('decode="hip" does not support this decoder -- ' + "; ".join(bad))
@@ -349,6 +351,8 @@ class _HipDecoder:
             w = w.contiguous()
             _lib.check(self.L.cgpt_llm_load_weight_f16(self.handle, name.encode(), C.c_void_p(w.data_ptr()), w.numel(), st))
         torch.cuda.current_stream(self.device).synchronize()           # contiguous() temporaries may go once the copies have run
+        if self.early_stop:                                            # off is the handle's state at create: nothing is called for it
+            _lib.check(self.L.cgpt_llm_set_early_stop(self.handle, 1))
 
     @property
     def weight_bytes(self):
@@ -446,6 +450,7 @@ class _HipDecoder:
         tokens = torch.empty((B, num_new), dtype=torch.int64, device=self.device)
         steps = torch.empty((B, num_new, V), dtype=torch.float32, device=self.device) if return_logits else None
         eos = (C.c_int64 * max(1, len(eos_ids)))(*[int(e) for e in eos_ids])
+        self._greedy_ran = True
         st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         tail = (int(num_new), int(min_new), eos, len(eos_ids), int(pad_id), kp, vp, stride, C.c_void_p(tokens.data_ptr()),
                 C.c_void_p(steps.data_ptr()) if return_logits else None, st)
@@ -455,6 +460,23 @@ class _HipDecoder:
             self._lib_mod.check(self.L.cgpt_llm_greedy_ragged(self.handle, C.c_void_p(first_logits.data_ptr()), B, int(prompt_len),
                                                               self._starts_ptr(starts, B), *tail))
         return (tokens, steps) if return_logits else tokens
+
+    def set_early_stop(self, on):
+        """cgpt_llm_set_early_stop: read by the next `greedy` when it enqueues; a captured call keeps what it was captured under."""
+        self._lib_mod.check(self.L.cgpt_llm_set_early_stop(self.handle, int(bool(on))))
+        self.early_stop = bool(on)
+
+    def live_steps(self):
+        """cgpt_llm_live_steps after the last `greedy` (or the last replay of a graph that captured it): the token steps that ran.
+        Synchronises the CURRENT stream -- the one the call was enqueued or the graph replayed on; RuntimeError when no greedy has
+        been enqueued."""
+        C = self._C
+        if not self._greedy_ran:
+            raise RuntimeError("live_steps: no native greedy decode has run on this engine yet")
+        n = C.c_int32(-1)
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._lib_mod.check(self.L.cgpt_llm_live_steps(self.handle, C.byref(n), st))
+        return int(n.value)
 
     MAX_CANDS, MAX_TAIL = 64, 64                                       # SCORE_MAX_CANDS, SCORE_MAX_TAIL (csrc/llm.h)
 
@@ -493,6 +515,7 @@ class MiniGPT4Classifier:
        :param ragged: "hf" (default) | "hip" -- who decodes a call whose rows carry DIFFERENT texts (left padding + mask); see __init__
        :param prompt_bucket: None | int >= 1 (with ragged="hip") -- padded prompt lengths are rounded up to a multiple of it
        :param weights: "fp16" (default) | "int8" (with decode="hip" and prefill="hip") -- how the native engine holds the layer linears
+       :param early_stop: False (default) | True (with decode="hip") -- the native token steps do no work once every row has its EOS
        :param end_sym: text appended to every candidate answer of `multi_select` ("\n": the reference's default; its VQA configs: "###")
        :param label_smoothing: of the answer loss (0.1: modeling_llama.py:105)
        :param score: "hf" (default) | "hip" -- who computes the answer losses of `multi_select`; see __init__
@@ -508,7 +531,8 @@ class MiniGPT4Classifier:
 
     def __init__(self, encoder, llama_model, llama_tokenizer, prompt, label_map, max_new_tokens=20, max_batch=None,
                  generate_kwargs=None, decode="hf", prefill_linear="torch", prefill="model", ragged="hf", prompt_bucket=None,
-                 weights="fp16", end_sym="\n", label_smoothing=0.1, score="hf", classify="generate", candidates=None):
+                 weights="fp16", end_sym="\n", label_smoothing=0.1, score="hf", classify="generate", candidates=None,
+                 early_stop=False):
         self.encoder = encoder
         self.llama_model = llama_model
         self.llama_tokenizer = llama_tokenizer
@@ -556,6 +580,11 @@ class MiniGPT4Classifier:
         #   the model whose layer linears are `int8_state_dict(llama_model)` (tests/test_gpu_llm_int8.py).  With the model's own
         #   prefill the prompt would run on W and the steps on W': a mixed model, hence the ValueError.  Works with ragged = "hip" and
         #   prompt_bucket.  weights = "fp16" (default): the engine's own fp16 copies, as before.
+        # early_stop = True (with decode = "hip" only; anything else is a ValueError): once every row of a batch has produced an EOS,
+        #   the remaining token steps of the native greedy loop do no work (cgpt_llm_set_early_stop, DESIGN.md 4.4.5: a flag on the
+        #   device that every step kernel reads first; the captured graph keeps all its launches and one graph serves every finishing
+        #   step).  Tokens and answers are bit for bit those with it off; `last_live_steps()` tells how many steps ran.  Works with
+        #   either prefill, with ragged = "hip" and with weights = "int8".  early_stop = False (default): every step runs, as before.
         # score = "hf" (default): `multi_select` / `answer_losses_from_embeds` run the model's own forward once per candidate over the
         #   concatenated prompt + answer embeds, as the reference does (works on the CPU); counted in decode_stats["hf_score_forwards"].
         # score = "hip" (with decode = "hip" AND prefill = "hip" only; anything else is a ValueError, never another engine): ONE native
@@ -583,6 +612,11 @@ class MiniGPT4Classifier:
         if weights == "int8" and (decode != "hip" or prefill != "hip"):
             raise ValueError(f'weights="int8" needs decode="hip" and prefill="hip" (got decode={decode!r}, prefill={prefill!r}): '
                              "int8 weights exist on the native engine only, and prompt and steps must run on the same weights")
+        if not isinstance(early_stop, bool):
+            raise ValueError(f"early_stop={early_stop!r}: expected False or True")
+        if early_stop and decode != "hip":
+            raise ValueError(f'early_stop=True needs decode="hip" (got decode={decode!r}): only the native token steps can be switched '
+                             "off on the device")
         if prompt_bucket is not None:
             if isinstance(prompt_bucket, bool) or not isinstance(prompt_bucket, int) or prompt_bucket < 1:
                 raise ValueError(f"prompt_bucket={prompt_bucket!r}: expected None or an int >= 1")
@@ -616,7 +650,8 @@ class MiniGPT4Classifier:
         self.prompt_bucket = prompt_bucket
         self.prefill_linear = prefill_linear
         self.weights = weights
-        self._hip = _HipDecoder(llama_model, self.max_batch, weights=weights) if decode == "hip" else None
+        self.early_stop = early_stop
+        self._hip = _HipDecoder(llama_model, self.max_batch, weights=weights, early_stop=early_stop) if decode == "hip" else None
         self.routed_linears = (_LinearRoute.install(llama_model)
                                if (decode in ("graph", "hip") and prefill_linear == "cgpt" and prefill == "model") else 0)
         import collections
@@ -859,7 +894,16 @@ class MiniGPT4Classifier:
     def _graph_key(self, embs, ragged=False):
         key = (embs.shape[0], embs.shape[1], embs.dtype, embs.device.index, self.max_new_tokens, bool(self.routed_linears), self.decode,
                self.prefill)
-        return key + ("ragged",) if ragged else key                   # a graph of the _ragged entries is never an unpadded one's
+        key = key + ("ragged",) if ragged else key                    # a graph of the _ragged entries is never an unpadded one's
+        return key + ("early_stop",) if self.early_stop else key      # nor is one captured with early stop on one captured without
+
+    def last_live_steps(self):
+        """Token steps of the most recent native greedy decode (eager, or the last graph replay) that actually ran: max_new_tokens - 1
+        with early_stop off, min(F, max_new_tokens - 1) with it on, F = the first select at which every row had produced an EOS.
+        ONE host sync, which is why it is never read on its own after a replay.  RuntimeError when no native greedy decode has run."""
+        if self._hip is None:
+            raise RuntimeError('last_live_steps: no native engine (decode="hip") on this classifier')
+        return self._hip.live_steps()
 
     def _generate_graph(self, embs, starts=None):
         """One captured hipGraph per (batch, prompt length, dtype, device, max_new_tokens, routed prefill, engine, prefill engine), kept in an LRU of

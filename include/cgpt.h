@@ -434,6 +434,29 @@ cgpt_status cgpt_llm_greedy_ragged(cgpt_llm_handle h, const float* first_logits_
                                    int32_t num_eos, int64_t pad_id, void* const* k_ptrs_host, void* const* v_ptrs_host,
                                    int64_t kv_len_stride, int64_t* tokens_out_dev, float* step_logits_out_dev, void* stream);
 
+/* ---- Early stop: the greedy entries do no work once every row has produced an EOS ----
+ * cgpt_llm_set_early_stop(h, 1): handle state, read when cgpt_llm_greedy / cgpt_llm_greedy_ragged ENQUEUE (as cgpt_set_noise_law is):
+ * a captured graph keeps the setting it was captured under, whatever the handle says at replay.  Off (0) is the state after
+ * cgpt_llm_create, and with it both entries are exactly what they were.  CGPT_ERR_INVALID for a null handle or a value other than 0 / 1.
+ * With early stop on, a one-workgroup reduction after every select writes `live` = "some row is unfinished" to the handle, and
+ * every kernel of the token steps that follow reads it first and returns when it is 0: after the select at which the last unfinished
+ * row produces an EOS, the remaining steps of the call stream no weight byte, read and append no K / V row and write no logits; the
+ * remaining selects write pad_id without looking at any logits.  The call still enqueues every launch (a dead step costs its
+ * launches and nothing else), so it has no host sync, no allocation and no host->device copy, stays capturable, and ONE capture
+ * serves every finishing step.  The tokens are, bit for bit, those of the same call with early stop off.
+ * live_steps = the number of token steps of the call that ran = min(F, num_new - 1), F = the first select at which no row is left
+ * unfinished (num_new if there is none; with num_eos == 0 nothing ever stops).  The dead part of a call, with early stop on:
+ *   - cache rows prompt_len + live_steps .. of k_ptrs_host[l] / v_ptrs_host[l] are NOT written (rows below are, as without it);
+ *   - rows [.., i, ..] of step_logits_out_dev for selects i > live_steps are NOT written (rows i <= live_steps are, as without it);
+ *   - tokens_out_dev is fully written.
+ * cgpt_llm_step, cgpt_llm_step_ragged, the prefill entries and cgpt_llm_score never look at the setting.
+ * cgpt_llm_live_steps: SYNCHRONISES `stream`, then *out_host = live_steps of the greedy call this handle enqueued last (on that
+ * stream).  Not capturable: call it outside any capture.  After a call with early stop on the value is read from the device, so after
+ * replays of a graph that captured such a call it is the last replay's; after a call with early stop off it is num_new - 1 (every
+ * step runs), kept on the host when the call enqueues.  0 before any greedy call.  CGPT_ERR_INVALID for a null argument. */
+cgpt_status cgpt_llm_set_early_stop(cgpt_llm_handle h, int32_t on);
+cgpt_status cgpt_llm_live_steps(cgpt_llm_handle h, int32_t* out_host, void* stream);
+
 /* ---- Answer scoring: all candidates of a multiple-choice question on ONE prefilled prompt ----
  * Replaces: `MiniGPTBase.multi_select` (minigpt_base.py:451-467), i.e. `forward(..., reduction='none')` (minigpt_base.py:320-363;
  * modeling_llama.py:101-123) once per candidate: a whole forward over prompt + answer and

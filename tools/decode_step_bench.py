@@ -23,7 +23,17 @@ reads, over 6.3 TB/s (the copy rate the box reaches).
     fp16        the engine's own fp16 copies (today's path)
     int8        row-wise absmax int8 layer linears: the int8-weight decode GEMM in the steps, a dequant pass before each prefill GEMM
     parent      `fp16` on another build of the library (--parent-lib PATH), as under --ragged
-and reports the handles' weight_bytes beside the times."""
+and reports the handles' weight_bytes beside the times.
+
+--early-stop runs the early-stop leg instead (early_stop=True), same protocol, every engine decode="hip", prefill="hip".
+The finishing step is set exactly, without a trained model: lm_head is zeroed (the layers stay random) and eos_token_id = 0, so every
+logit is 0, the select picks token 1 while EOS is masked (min_length = F generated tokens) and token 0 = EOS for every row at select F:
+    off         early stop off, the law that never finishes (today's path: every step runs whatever the law)
+    on_never    early stop on, min_length = --new: no row ever finishes -- what the guards and the reduction cost a batch that runs on
+    on_f1/on_f3 early stop on, every row finishes at select 1 / 3: 18 / 16 of the 19 steps are dead
+    parent      `off` on another build of the library (--parent-lib PATH), as under --ragged
+The order of the legs is rotated from one repetition to the next.  dead_step_ms = the live step minus the saving per skipped step,
+(generate(on_never) - generate(on_fF)) / (19 - F)."""
 import argparse
 import json
 import os
@@ -243,6 +253,99 @@ def int8_leg(args, llm, embs, tok, lm):
     print(json.dumps(line))
 
 
+def early_stop_leg(args, llm, embs, tok, lm):
+    rows, new = args.rows, args.new
+    with torch.no_grad():
+        llm.lm_head.weight.zero_()
+    llm.config.eos_token_id = llm.generation_config.eos_token_id = 0
+    llm.config.pad_token_id = llm.generation_config.pad_token_id = 0
+
+    def build(n, min_length, **kw):
+        return MiniGPT4Classifier(_Rows(rows), llm, tok, "<ImageHere>", lm, max_new_tokens=n, max_batch=rows, decode="hip", prefill="hip",
+                                  generate_kwargs=dict(min_length=min_length), **kw)
+
+    finish = {"off": new, "on_never": new, "on_f1": 1, "on_f3": 3, "parent": new}
+    legs = ["off", "on_never", "on_f1", "on_f3"]
+    clfs = {(e, new): build(new, finish[e], early_stop=e != "off") for e in legs}
+    prefill = build(1, 1)                                                # one select, no step: the same call on every leg of this build
+    for e in legs:
+        clfs[(e, 1)] = prefill
+    if args.parent_lib:
+        with _other_library(args.parent_lib):
+            clfs.update({("parent", n): build(n, new) for n in (new, 1)})
+        legs.append("parent")
+
+    def timed(leg, n):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = clfs[(leg, n)]._generate_graph(embs)
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b), out
+
+    clock_before = _clock()
+    res = {e: {"generate_ms": [], "prefill_ms": [], "order": []} for e in legs}
+    tokens, live = {}, {}
+    with torch.no_grad():
+        for rep_i in range(args.warmup + args.reps):                   # interleaved, and rotated: every leg takes every place in turn
+            k = rep_i % len(legs)
+            for place, e in enumerate(legs[k:] + legs[:k]):
+                t, out = timed(e, new)
+                if e != "parent":
+                    live[e] = clfs[(e, new)].last_live_steps()         # after the timed region: it synchronises
+                tp = timed(e, 1)[0]
+                print(f"decode_step_bench: repetition {rep_i} {e} generate {t:.1f} ms prefill {tp:.1f} ms", file=sys.stderr, flush=True)
+                if rep_i >= args.warmup:
+                    res[e]["generate_ms"].append(t)
+                    res[e]["prefill_ms"].append(tp)
+                    res[e]["order"].append(place)
+                    tokens[e] = out
+        # the off engine on the two finishing laws, eagerly and untimed: the tokens the on legs must give
+        off = clfs[("off", new)]
+        for f in (1, 3):
+            off.generate_kwargs["min_length"] = f
+            tokens[f"off_f{f}"] = off.greedy_tokens(embs)
+        off.generate_kwargs["min_length"] = new
+    clock_after = _clock()
+    steps = new - 1
+    for r in res.values():
+        r["step_ms"] = [(gm - pm) / steps for gm, pm in zip(r["generate_ms"], r["prefill_ms"])]
+        for k in ("generate_ms", "prefill_ms", "step_ms"):
+            r[k + "_min_max"] = [min(r[k]), max(r[k])]
+
+    def overlap(a, b, k):
+        (a0, a1), (b0, b1) = res[a][k + "_min_max"], res[b][k + "_min_max"]
+        return a0 <= b1 and b0 <= a1
+
+    def med(e, k):
+        return sorted(res[e][k])[len(res[e][k]) // 2]
+
+    keys = ("prefill_ms", "step_ms", "generate_ms")
+    live_step = med("on_never", "step_ms")
+    dead = {}
+    for f in (1, 3):
+        saving = (med("on_never", "generate_ms") - med(f"on_f{f}", "generate_ms")) / (steps - f)
+        dead[f"f{f}"] = {"saving_per_skipped_step_ms": saving, "dead_step_ms": live_step - saving,
+                         "dead_step_over_live_step": (live_step - saving) / live_step}
+    same = lambda a, b: int((tokens[a] == tokens[b]).all(dim=1).sum())  # noqa: E731
+    line = {"tool": "decode_step_bench", "leg": "early_stop", "rows": rows, "prompt": args.prompt, "new_tokens": new, "layers": args.layers,
+            "reps": args.reps, "warmup": args.warmup, "leg_order": "rotated by one place per repetition", "engines": res,
+            "live_steps": live,
+            "on_never_over_off_median": {k: med("on_never", k) / med("off", k) for k in keys},
+            "on_never_and_off_ranges_overlap": {k: overlap("on_never", "off", k) for k in keys},
+            "on_over_off_generate_median": {e: med(e, "generate_ms") / med("off", "generate_ms") for e in ("on_f1", "on_f3")},
+            "on_and_off_generate_ranges_overlap": {e: overlap(e, "off", "generate_ms") for e in ("on_f1", "on_f3")},
+            "live_step_ms": live_step, "dead_step": dead,
+            "rows_with_off_tokens": {"on_never": same("on_never", "off"), "on_f1": same("on_f1", "off_f1"), "on_f3": same("on_f3", "off_f3")},
+            "shader_clock_mhz_before_after": [clock_before, clock_after], "device": torch.cuda.get_device_name(0)}
+    if "parent" in res:
+        line["parent_lib"] = os.path.basename(args.parent_lib)
+        line["off_and_parent_ranges_overlap"] = {k: overlap("off", "parent", k) for k in keys}
+        line["off_over_parent_median"] = {k: med("off", k) / med("parent", k) for k in keys}
+        line["off_rows_with_parent_tokens"] = same("off", "parent")
+    print(json.dumps(line))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=200)
@@ -256,7 +359,8 @@ def main():
     ap.add_argument("--bucket-len", type=int, default=48)
     ap.add_argument("--ragged-min", type=int, default=38)
     ap.add_argument("--int8", action="store_true", help="the weight-format leg (see the module docstring)")
-    ap.add_argument("--parent-lib", default=None, help="another build of libcgpt.so for the plain-path A/B of --ragged / --int8")
+    ap.add_argument("--early-stop", action="store_true", help="the early-stop leg (see the module docstring)")
+    ap.add_argument("--parent-lib", default=None, help="another build of libcgpt.so for the plain-path A/B of --ragged / --int8 / --early-stop")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "this benchmark measures device time: it needs the GPU"
     assert 1 <= args.rows <= 256 and args.new >= 2 and args.prompt >= 1
@@ -270,6 +374,8 @@ def main():
         return ragged_leg(args, llm, embs, tok, lm)
     if args.int8:
         return int8_leg(args, llm, embs, tok, lm)
+    if args.early_stop:
+        return early_stop_leg(args, llm, embs, tok, lm)
     how = {"graph": dict(decode="graph"), "hip": dict(decode="hip", prefill="model"), "hip_native": dict(decode="hip", prefill="hip")}
     clfs = {(e, n): MiniGPT4Classifier(_Rows(args.rows), llm, tok, "<ImageHere>", lm, max_new_tokens=n, max_batch=args.rows,
                                        prefill_linear="cgpt", **how[e]) for e in engines for n in (args.new, 1)}
