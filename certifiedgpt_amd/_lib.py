@@ -42,6 +42,12 @@ class LlmConfig(C.Structure):
     ]
 
 
+class LlmConfigGqa(C.Structure):
+    """struct cgpt_llm_config_gqa (include/cgpt.h): the config followed by the later switches.  base.struct_size = sizeof(this);
+    cgpt_llm_create takes a pointer to `base`."""
+    _fields_ = [("base", LlmConfig), ("grouped_kv", C.c_int32), ("reserved", C.c_int32)]
+
+
 LLM_WEIGHT_FORMATS = {"fp16": 0, "int8": 1}   # CGPT_LLM_W_F16, CGPT_LLM_W_INT8
 # sizeof(cgpt_llm_config) before weight_format existed: still accepted by cgpt_llm_create (fp16), and what older builds expect
 LLM_CONFIG_SIZE_F16 = LlmConfig.weight_format.offset

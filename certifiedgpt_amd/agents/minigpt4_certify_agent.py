@@ -17,7 +17,9 @@ Config (a plain dict or any mapping; the reference's YAMLs define no smoothing k
             #          prefill; needs decode "hip"), ragged: "hf" | "hip" (rows with different texts on the native engine; needs decode
             #          and prefill "hip"), prompt_bucket: null | int (with ragged "hip": prompt lengths rounded up to a multiple of it,
             #          one captured graph per bucket), early_stop: false | true (with decode "hip": the native token steps do no work
-            #          once every row of a batch has produced its EOS; same answers) -- see build_generating_classifier
+            #          once every row of a batch has produced its EOS; same answers), grouped_kv: false | true (with decode "hip": the
+            #          native engine takes a grouped-query decoder, heads / kv_heads in {1, 2, 4, 8}, e.g. Llama-3-8B; K/V buffers
+            #          shrink by that ratio) -- see build_generating_classifier
             #          also: classify: "generate" | "multi_select" (rank the answers by their teacher-forced loss instead of generating:
             #          every noisy copy votes for one of `answers`, never for "other"), score: "hf" | "hip" (who computes those losses;
             #          "hip" needs decode and prefill "hip"), end_sym: "\\n" (appended to every answer; the reference's VQA configs: "###")
@@ -197,7 +199,8 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
                   "hip", ragged "hip" needs both, prompt_bucket needs ragged "hip"); weights: "fp16" | "int8" (the native engine's
                   layer linears as row-wise absmax int8, the weight law of the reference's low_resource: true; needs decode and
                   prefill "hip"); early_stop: False | True (the native token steps stop working once every row of a batch has its
-                  EOS, same answers; needs decode "hip"); classify: "generate" | "multi_select" (the base classifier ranks `answers` by their answer loss,
+                  EOS, same answers; needs decode "hip"); grouped_kv: False | True (grouped-query attention on the native engine, for decoders
+                  with fewer K/V heads than query heads; needs decode "hip"); classify: "generate" | "multi_select" (the base classifier ranks `answers` by their answer loss,
                   MiniGPTBase.multi_select, instead of generating), score: "hf" | "hip" (the model's own forward per candidate | one
                   native prefill + the native scoring pass; needs decode and prefill "hip"), end_sym: "\\n" (appended to every answer)"""
     from ..minigpt4 import MiniGPT4Classifier
@@ -229,7 +232,7 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
                               decode=gen_cfg.get("decode", "hf"), prefill_linear=gen_cfg.get("prefill_linear", "torch"),
                               prefill=gen_cfg.get("prefill", "model"), ragged=gen_cfg.get("ragged", "hf"),
                               prompt_bucket=gen_cfg.get("prompt_bucket"), weights=gen_cfg.get("weights", "fp16"),
-                              early_stop=gen_cfg.get("early_stop", False),
+                              early_stop=gen_cfg.get("early_stop", False), grouped_kv=gen_cfg.get("grouped_kv", False),
                               classify=gen_cfg.get("classify", "generate"), score=gen_cfg.get("score", "hf"),
                               end_sym=gen_cfg.get("end_sym", "\n"))
 

@@ -41,6 +41,9 @@ hipError_t launch_decode_gemm(int epilogue, const DecodeGemmParams& p, hipStream
 
 // ------------------------------------------------------------------------------------- prefill (llm_prefill.hip)
 // Token row r = b * L + p of B prompts of L positions.  All fp16, rows `hidden` (or 3 hidden / 2 mlp / mlp) elements apart.
+// kv_heads (rope, attention, scoring attention): == heads is the plain layout and the plain kernel instantiations; a divisor of heads
+// below it is grouped-query attention -- qkv rows are hidden + 2 kv_heads 128 wide (q, then k, then v), Kc / Vc are
+// [B, kv_heads, len_stride, 128], query head h reads K/V head h / (heads / kv_heads).
 // x_out[r] = fp16(x[s] + delta[s]) (delta may be null), y[r] = LlamaRMSNorm(x_out[r]) * w, with s = r * src_mul + src_add
 // (identity: 1, 0; the last position of every prompt: L, L - 1).  x_out may alias x.
 hipError_t launch_prefill_addnorm(const half_t* x, const half_t* delta, int64_t src_mul, int64_t src_add, const half_t* w, int hidden,
@@ -48,11 +51,11 @@ hipError_t launch_prefill_addnorm(const half_t* x, const half_t* delta, int64_t 
 // Rotates q in place in qkv [B L, 3 hidden] and writes rotated k and v to rows 0 .. L-1 of Kc / Vc [B, heads, len_stride, 128].
 // starts (device, [B] int32, or null = no padding): row b is left-padded by start[b] positions (clamped into 0 .. L-1); its real
 // tokens sit at buffer positions start[b] .. L-1 and take rotary rows 0 ..; pad positions are not rotated and not written to the cache.
-hipError_t launch_prefill_rope(half_t* qkv, int B, int L, int hidden, int heads, half_t* Kc, half_t* Vc, int64_t len_stride,
+hipError_t launch_prefill_rope(half_t* qkv, int B, int L, int hidden, int heads, int kv_heads, half_t* Kc, half_t* Vc, int64_t len_stride,
                                const half_t* rope, const int32_t* starts, hipStream_t stream);
 // out[B L, hidden] = causal softmax(q . K^T / sqrt(128)) . V per head, q from qkv (already rotated), K / V rows 0 .. L-1 of the cache.
 // starts as above: row b attends over cache rows start[b] .. p only, walked from start[b]; pad rows of `out` are written as zeros.
-hipError_t launch_prefill_attention(const half_t* qkv, int B, int L, int hidden, int heads, const half_t* Kc, const half_t* Vc,
+hipError_t launch_prefill_attention(const half_t* qkv, int B, int L, int hidden, int heads, int kv_heads, const half_t* Kc, const half_t* Vc,
                                     int64_t len_stride, half_t* out, const int32_t* starts, hipStream_t stream);
 // act[rows, mlp] = fp16(fp16(silu(gate)) * up) from gu [rows, 2 mlp] with gate / up columns interleaved in blocks of 16.
 hipError_t launch_prefill_swiglu(const half_t* gu, int64_t rows, int mlp, half_t* act, hipStream_t stream);
@@ -75,7 +78,7 @@ hipError_t launch_score_embed(const long long* cand_tokens, const ScoreCands& t,
                               half_t* h, hipStream_t stream);
 // Rotary + attention of the tail rows: out[r, head] = softmax(q_r . [K_prompt(b, 0..L-1); k_tail(b, c, 0..j)] / sqrt(128)) . V alike,
 // q / k / v from qkv [B S, 3 hidden] (not modified).  Kc / Vc are read (rows 0 .. L-1) and NEVER written.
-hipError_t launch_score_attention(const half_t* qkv, const ScoreCands& t, int B, int L, int hidden, int heads, const half_t* Kc,
+hipError_t launch_score_attention(const half_t* qkv, const ScoreCands& t, int B, int L, int hidden, int heads, int kv_heads, const half_t* Kc,
                                   const half_t* Vc, int64_t len_stride, const half_t* rope, half_t* out, hipStream_t stream);
 // ce[b, tok(c) + j] = label-smoothed cross-entropy of one logits row against token j of candidate c, tok(c) = off[c] + c, a row of
 // ce holding S + C values.  first: token 0 of every candidate on the fp32 rows first_logits[b] (B x C workgroups).  tail: `rows`

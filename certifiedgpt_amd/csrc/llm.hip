@@ -216,6 +216,165 @@ __global__ __launch_bounds__(64) void llm_attn_kernel(const half_t* __restrict__
     }
 }
 
+// Grouped-query attention (cgpt_llm_config_gqa.grouped_kv): the token step's attention with ONE read of a K/V head for
+// the G = heads / kv_heads query heads that share it.  One workgroup per (row, K/V head), G wavefronts, wave w = query head
+// kvh * G + w.  The caches are [B, kv_heads, len_stride, 128]; the fused projection row is [hidden | kv_heads * 128 | kv_heads * 128].
+//   every wave rotates its own q; wave 0 rotates and appends the group's one new key / value row, to the cache and to LDS
+//   score pass: the group's cache rows are staged into LDS in chunks of 64 keys (16-byte loads, all waves load), every wave takes
+//       its dot products from the staged chunk; P.V pass: the same walk over V.  Two passes with the scores in LDS, as the plain kernel.
+// A query's arithmetic and key order are exactly llm_attn_kernel's: keys in groups of four from the row's first real key (chunks
+// begin at multiples of 64 keys from it, so the groups of four are the same groups), fp32 dot products with the 16-lane butterfly,
+// the maximum, then expf(sc - mx) and acc += p * v in key order, the same final shuffles and the division.  Staging changes where
+// a byte comes from, never the order of a sum: head h of a grouped handle gives the bits the plain kernel gives on a cache whose
+// head h holds K/V head h / G.  RAGGED and GUARD as in llm_attn_kernel; every barrier sits in block-uniform control flow (n depends on
+// the row alone).  Plain vector stores, no atomics.
+// Dynamic LDS: [64][128] halfs staging, [128 + 128] halfs new key / value, G x [128] floats rotated queries, G x [bufpos + 1] floats
+// scores (gqa_attn_lds_bytes; the limit is set at create, and a (G, max_len) that exceeds the CU's LDS is refused there).
+constexpr int GQA_KC = 64;                          // keys staged per chunk
+constexpr size_t LDS_PER_CU = 160 * 1024;           // gfx950
+
+template <int G, bool RAGGED, bool GUARD>
+__global__ __launch_bounds__(64 * G) void llm_attn_gqa_kernel(const half_t* __restrict__ qkv, int hidden, int kv_heads, half_t* Kc, half_t* Vc,
+                                                              int64_t len_stride, const half_t* __restrict__ rope, int bufpos,
+                                                              half_t* __restrict__ out, const int* __restrict__ starts, int smax,
+                                                              const int* __restrict__ live) {
+    extern __shared__ __attribute__((aligned(16))) float gsmem[];
+    if constexpr (GUARD)
+        if (*live == 0) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    half_t* stage = reinterpret_cast<half_t*>(gsmem);
+    half_t* knew = stage + GQA_KC * HD;
+    half_t* vnew = knew + HD;
+    float* qs = reinterpret_cast<float*>(vnew + HD) + wave * HD;
+    float* sc = reinterpret_cast<float*>(vnew + HD) + G * HD + (int64_t)wave * (bufpos + 1);
+    const int b = blockIdx.x / kv_heads, kvh = blockIdx.x % kv_heads, h = kvh * G + wave;
+    const int kvw = kv_heads * HD;
+    const half_t* q = qkv + (int64_t)b * (hidden + 2 * kvw) + h * HD;
+    const half_t* k = qkv + (int64_t)b * (hidden + 2 * kvw) + hidden + kvh * HD;
+    const half_t* v = k + kvw;
+    const int s = RAGGED ? min(max(starts[b], 0), min(smax, bufpos)) : 0;
+    const int pos = bufpos - s;
+    half_t* Kh = Kc + ((int64_t)(b * kv_heads + kvh) * len_stride + s) * HD;
+    half_t* Vh = Vc + ((int64_t)(b * kv_heads + kvh) * len_stride + s) * HD;
+
+    {   // lane i owns the rotary pair (i, i + 64)
+        const float c = (float)rope[(int64_t)pos * HD + lane], s = (float)rope[(int64_t)pos * HD + 64 + lane];
+        const float q0 = (float)q[lane], q1 = (float)q[lane + 64];
+        qs[lane] = rf16(mul_f16(q0, c) - mul_f16(q1, s));
+        qs[lane + 64] = rf16(mul_f16(q1, c) + mul_f16(q0, s));
+        if (wave == 0) {
+            const float k0 = (float)k[lane], k1 = (float)k[lane + 64];
+            const half_t r0 = (half_t)(mul_f16(k0, c) - mul_f16(k1, s)), r1 = (half_t)(mul_f16(k1, c) + mul_f16(k0, s));
+            const half_t v0 = v[lane], v1 = v[lane + 64];
+            Kh[(int64_t)pos * HD + lane] = knew[lane] = r0;
+            Kh[(int64_t)pos * HD + lane + 64] = knew[lane + 64] = r1;
+            Vh[(int64_t)pos * HD + lane] = vnew[lane] = v0;
+            Vh[(int64_t)pos * HD + lane + 64] = vnew[lane + 64] = v1;
+        }
+    }
+    __syncthreads();                                   // key `pos` is attended from LDS: the cache row just stored is not read back
+
+    const int n = pos + 1;
+    const int kk = lane >> 4, dc = (lane & 15) * 8;    // key within a group of 4, first of the lane's 8 dims
+    float qr[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) qr[e] = qs[dc + e];
+    const float scale = 0.08838834764831845f;          // 1 / sqrt(128)
+    float mx = -INFINITY;
+    for (int c0 = 0; c0 < n; c0 += GQA_KC) {
+        const int nk = min(GQA_KC, n - c0);
+        if (c0 > 0) __syncthreads();                   // the previous chunk has been read by every wave
+        for (int i = tid; i < nk * 16; i += 64 * G) {  // nk keys x 16 pieces of 16 bytes; key `pos` stays in knew
+            const int key = i >> 4, d8 = (i & 15) * 8;
+            if (c0 + key != pos)
+                *reinterpret_cast<h16x8*>(stage + key * HD + d8) = *reinterpret_cast<const h16x8*>(Kh + (int64_t)(c0 + key) * HD + d8);
+        }
+        __syncthreads();
+        for (int t0 = c0; t0 < c0 + nk; t0 += 4) {
+            const int t = t0 + kk;
+            float d = 0.0f;
+            if (t < n) {
+                const h16x8 kv = *reinterpret_cast<const h16x8*>(t == pos ? knew + dc : stage + (t - c0) * HD + dc);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) d += qr[e] * (float)kv[e];
+            }
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) d += __shfl_xor(d, o);
+            d *= scale;
+            if (t < n) {
+                mx = fmaxf(mx, d);
+                if ((lane & 15) == 0) sc[t] = d;
+            }
+        }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16));
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float l = 0.0f;
+    for (int c0 = 0; c0 < n; c0 += GQA_KC) {
+        const int nk = min(GQA_KC, n - c0);
+        __syncthreads();                               // the scores are written / the previous chunk has been read by every wave
+        for (int i = tid; i < nk * 16; i += 64 * G) {
+            const int key = i >> 4, d8 = (i & 15) * 8;
+            if (c0 + key != pos)
+                *reinterpret_cast<h16x8*>(stage + key * HD + d8) = *reinterpret_cast<const h16x8*>(Vh + (int64_t)(c0 + key) * HD + d8);
+        }
+        __syncthreads();
+        for (int t0 = c0; t0 < c0 + nk; t0 += 4) {
+            const int t = t0 + kk;
+            if (t < n) {
+                const float p = expf(sc[t] - mx);
+                const h16x8 vv = *reinterpret_cast<const h16x8*>(t == pos ? vnew + dc : stage + (t - c0) * HD + dc);
+                l += p;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[e] += p * (float)vv[e];
+            }
+        }
+    }
+    l += __shfl_xor(l, 16);
+    l += __shfl_xor(l, 32);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        acc[e] += __shfl_xor(acc[e], 16);
+        acc[e] += __shfl_xor(acc[e], 32);
+    }
+    if (kk == 0) {
+        h16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (half_t)(acc[e] / l);
+        *reinterpret_cast<h16x8*>(out + (int64_t)b * hidden + h * HD + dc) = o;
+    }
+}
+
+size_t gqa_attn_lds_bytes(int G, int positions) {
+    return (size_t)(GQA_KC + 2) * HD * sizeof(half_t) + (size_t)G * (HD + positions) * sizeof(float);
+}
+
+template <int G>
+hipError_t gqa_attn_prepare(int max_len) {
+    const int bytes = (int)gqa_attn_lds_bytes(G, max_len);
+    const void* fns[4] = {reinterpret_cast<const void*>(llm_attn_gqa_kernel<G, false, false>), reinterpret_cast<const void*>(llm_attn_gqa_kernel<G, false, true>),
+                          reinterpret_cast<const void*>(llm_attn_gqa_kernel<G, true, false>), reinterpret_cast<const void*>(llm_attn_gqa_kernel<G, true, true>)};
+    for (const void* f : fns) {
+        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+template <int G, bool GUARD>
+void gqa_attn_launch(const half_t* qkv, int hidden, int kv_heads, int B, half_t* Kc, half_t* Vc, int64_t len_stride, const half_t* rope, int pos,
+                     half_t* out, const int* starts, int smax, const int* live, hipStream_t st) {
+    const size_t lds = gqa_attn_lds_bytes(G, pos + 1);
+    if (starts)
+        hipLaunchKernelGGL((llm_attn_gqa_kernel<G, true, GUARD>), dim3(B * kv_heads), dim3(64 * G), lds, st, qkv, hidden, kv_heads, Kc, Vc, len_stride,
+                           rope, pos, out, starts, smax, live);
+    else
+        hipLaunchKernelGGL((llm_attn_gqa_kernel<G, false, GUARD>), dim3(B * kv_heads), dim3(64 * G), lds, st, qkv, hidden, kv_heads, Kc, Vc, len_stride,
+                           rope, pos, out, nullptr, 0, live);
+}
+
 typedef signed char i8x16 __attribute__((ext_vector_type(16)));
 
 // The weight law of an int8 handle, one workgroup per source row of an HF nn.Linear.weight [rows, K] in fp16:
@@ -353,6 +512,11 @@ __global__ __launch_bounds__(256) void llm_live_kernel(const int* __restrict__ u
     }
 }
 
+// The config a handle keeps: the caller's cgpt_llm_config and the switches of cgpt_llm_config_gqa (0 for a plain config).
+struct LlmCfg : cgpt_llm_config {
+    int32_t grouped_kv = 0;
+};
+
 // One fused layer matrix [up256(N)][K]: fp16 (`w`) on an fp16 handle; int8 `q` with one fp16 scale per row (`s`) on an int8 handle.
 struct Mat {
     half_t* w = nullptr;
@@ -367,7 +531,7 @@ struct Layer {
 }  // namespace
 
 struct cgpt_llm {
-    cgpt_llm_config cfg;
+    LlmCfg cfg;
     std::vector<Layer> layers;
     half_t *embed = nullptr, *norm = nullptr, *lm_head = nullptr, *rope = nullptr;
     half_t *h = nullptr, *xn = nullptr, *qkv = nullptr, *attn = nullptr, *act = nullptr;
@@ -397,6 +561,9 @@ struct cgpt_llm {
 };
 
 namespace {
+
+// columns of the fused q/k/v projection: hidden + 2 kv_heads 128 (3 hidden on a plain handle, where kv_heads == heads)
+inline int qkv_width(const cgpt_llm_config& c) { return c.hidden + 2 * c.kv_heads * HD; }
 
 cgpt_status dev_zalloc(cgpt_llm* m, size_t bytes, void** out) {
     HIPCHK(hipMalloc(out, bytes));
@@ -440,8 +607,8 @@ cgpt_status gemm(cgpt_llm* m, int epi, const half_t* A, int K, const Mat& W, int
 template <bool GUARD>
 cgpt_status run_step(cgpt_llm* m, const long long* tokens, int B, int pos, const int32_t* starts, int smax, void* const* kp, void* const* vp,
                      int64_t len_stride, float* logits, int64_t ld_logits, hipStream_t st) {
-    const cgpt_llm_config& c = m->cfg;
-    const int H = c.hidden;
+    const LlmCfg& c = m->cfg;
+    const int H = c.hidden, NQ = qkv_width(c);
     const int* live = GUARD ? m->live : nullptr;
     hipLaunchKernelGGL(llm_embed_kernel<GUARD>, dim3(B), dim3(256), 0, st, tokens, m->embed, c.vocab, H, m->h, live);
     LAUNCHED();
@@ -450,8 +617,16 @@ cgpt_status run_step(cgpt_llm* m, const long long* tokens, int B, int pos, const
         const Layer& L = m->layers[l];
         hipLaunchKernelGGL(llm_rmsnorm_kernel<GUARD>, dim3(B), dim3(256), 0, st, m->h, L.ln1, H, c.rms_eps, m->xn, live);
         LAUNCHED();
-        CGCHK(gemm(m, DEC_F16, m->xn, H, L.wqkv, 3 * H, m->qkv, 3 * H, nullptr, B, st, live));
-        if (starts)
+        CGCHK(gemm(m, DEC_F16, m->xn, H, L.wqkv, NQ, m->qkv, NQ, nullptr, B, st, live));
+        if (c.grouped_kv) {
+            half_t *Kl = (half_t*)kp[l], *Vl = (half_t*)vp[l];
+            switch (c.heads / c.kv_heads) {
+                case 1: gqa_attn_launch<1, GUARD>(m->qkv, H, c.kv_heads, B, Kl, Vl, len_stride, m->rope, pos, m->attn, starts, smax, live, st); break;
+                case 2: gqa_attn_launch<2, GUARD>(m->qkv, H, c.kv_heads, B, Kl, Vl, len_stride, m->rope, pos, m->attn, starts, smax, live, st); break;
+                case 4: gqa_attn_launch<4, GUARD>(m->qkv, H, c.kv_heads, B, Kl, Vl, len_stride, m->rope, pos, m->attn, starts, smax, live, st); break;
+                default: gqa_attn_launch<8, GUARD>(m->qkv, H, c.kv_heads, B, Kl, Vl, len_stride, m->rope, pos, m->attn, starts, smax, live, st); break;
+            }
+        } else if (starts)
             hipLaunchKernelGGL((llm_attn_kernel<true, GUARD>), dim3(B * c.heads), dim3(64), attn_lds, st, m->qkv, H, c.heads, (half_t*)kp[l],
                                (half_t*)vp[l], len_stride, m->rope, pos, m->attn, starts, smax, live);
         else
@@ -502,10 +677,10 @@ cgpt_status run_prefill(cgpt_llm* m, const half_t* embeds, int B, int L, const i
         const Layer& Lw = m->layers[l];
         HIPCHK(launch_prefill_addnorm(x, pending, 1, 0, Lw.ln1, H, c.rms_eps, m->p_h, m->p_xn, M, st));
         x = m->p_h;
-        CGCHK(big_gemm(m, m->p_xn, H, Lw.wqkv, 3 * H, m->p_qkv, M, st));
-        HIPCHK(launch_prefill_rope(m->p_qkv, B, L, H, c.heads, (half_t*)kp[l], (half_t*)vp[l], len_stride, m->rope, starts, st));
-        HIPCHK(launch_prefill_attention(m->p_qkv, B, L, H, c.heads, (const half_t*)kp[l], (const half_t*)vp[l], len_stride, m->p_attn, starts,
-                                          st));
+        CGCHK(big_gemm(m, m->p_xn, H, Lw.wqkv, qkv_width(c), m->p_qkv, M, st));
+        HIPCHK(launch_prefill_rope(m->p_qkv, B, L, H, c.heads, c.kv_heads, (half_t*)kp[l], (half_t*)vp[l], len_stride, m->rope, starts, st));
+        HIPCHK(launch_prefill_attention(m->p_qkv, B, L, H, c.heads, c.kv_heads, (const half_t*)kp[l], (const half_t*)vp[l], len_stride,
+                                          m->p_attn, starts, st));
         CGCHK(big_gemm(m, m->p_attn, H, Lw.wo, H, m->p_proj, M, st));
         HIPCHK(launch_prefill_addnorm(m->p_h, m->p_proj, 1, 0, Lw.ln2, H, c.rms_eps, m->p_h, m->p_xn, M, st));
         CGCHK(big_gemm(m, m->p_xn, H, Lw.wgu, 2 * F, m->p_gu, M, st));
@@ -536,8 +711,8 @@ cgpt_status run_score(cgpt_llm* m, const float* first_logits, int B, int L, cons
         for (int l = 0; l < c.layers; ++l) {
             const Layer& Lw = m->layers[l];
             HIPCHK(launch_prefill_addnorm(m->p_h, pending, 1, 0, Lw.ln1, H, c.rms_eps, m->p_h, m->p_xn, R, st));
-            CGCHK(big_gemm(m, m->p_xn, H, Lw.wqkv, 3 * H, m->p_qkv, R, st));
-            HIPCHK(launch_score_attention(m->p_qkv, t, B, L, H, c.heads, (const half_t*)kp[l], (const half_t*)vp[l], len_stride, m->rope,
+            CGCHK(big_gemm(m, m->p_xn, H, Lw.wqkv, qkv_width(c), m->p_qkv, R, st));
+            HIPCHK(launch_score_attention(m->p_qkv, t, B, L, H, c.heads, c.kv_heads, (const half_t*)kp[l], (const half_t*)vp[l], len_stride, m->rope,
                                           m->p_attn, st));
             CGCHK(big_gemm(m, m->p_attn, H, Lw.wo, H, m->p_proj, R, st));
             HIPCHK(launch_prefill_addnorm(m->p_h, m->p_proj, 1, 0, Lw.ln2, H, c.rms_eps, m->p_h, m->p_xn, R, st));
@@ -563,19 +738,34 @@ extern "C" {
 
 cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
     if (!cfg || !out) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: null argument");
-    // two sizes are valid: the struct up to max_len (callers built before weight_format existed: fp16) and the whole struct
+    // three sizes are valid: the struct up to max_len (callers built before weight_format existed: fp16), the whole struct, and
+    // cgpt_llm_config_gqa (the struct is then the `base` of one, and the switches behind it are read)
     constexpr int32_t kOldSize = (int32_t)offsetof(cgpt_llm_config, weight_format);
-    if (cfg->struct_size != (int32_t)sizeof(cgpt_llm_config) && cfg->struct_size != kOldSize)
+    constexpr int32_t kGqaSize = (int32_t)sizeof(cgpt_llm_config_gqa);
+    static_assert(offsetof(cgpt_llm_config_gqa, grouped_kv) == sizeof(cgpt_llm_config), "the switches follow the base without padding");
+    if (cfg->struct_size != (int32_t)sizeof(cgpt_llm_config) && cfg->struct_size != kGqaSize && cfg->struct_size != kOldSize)
         return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: cgpt_llm_config.struct_size mismatch (header/library drift)");
-    cgpt_llm_config c{};
-    memcpy(&c, cfg, (size_t)cfg->struct_size);
+    LlmCfg c{};
+    memcpy(static_cast<cgpt_llm_config*>(&c), cfg, std::min((size_t)cfg->struct_size, sizeof(cgpt_llm_config)));
     if (cfg->struct_size == kOldSize) c.weight_format = CGPT_LLM_W_F16;
+    if (cfg->struct_size == kGqaSize) {
+        const cgpt_llm_config_gqa* ext = reinterpret_cast<const cgpt_llm_config_gqa*>(cfg);
+        if (ext->reserved != 0) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: cgpt_llm_config_gqa.reserved must be 0");
+        c.grouped_kv = ext->grouped_kv;
+    }
     c.struct_size = (int32_t)sizeof(cgpt_llm_config);
     if (c.weight_format != CGPT_LLM_W_F16 && c.weight_format != CGPT_LLM_W_INT8)
         return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: weight_format must be CGPT_LLM_W_F16 (0) or CGPT_LLM_W_INT8 (1)");
     if (c.head_dim != HD) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: head_dim must be 128");
-    if (c.heads < 1 || c.kv_heads != c.heads)
-        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: kv_heads must equal heads (no grouped-query attention)");
+    if (c.grouped_kv != 0 && c.grouped_kv != 1) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: grouped_kv must be 0 or 1");
+    if (c.heads < 1 || (!c.grouped_kv && c.kv_heads != c.heads))
+        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: kv_heads must equal heads (grouped-query attention needs grouped_kv = 1)");
+    if (c.grouped_kv) {
+        const int G = (c.kv_heads >= 1 && c.kv_heads <= c.heads && c.heads % c.kv_heads == 0) ? c.heads / c.kv_heads : 0;
+        if (G != 1 && G != 2 && G != 4 && G != 8)
+            return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: grouped_kv needs 1 <= kv_heads <= heads, heads % kv_heads == 0 and "
+                                               "heads / kv_heads in {1, 2, 4, 8}");
+    }
     if (c.hidden < 64 || c.hidden % 64 || c.hidden != c.heads * HD)
         return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: hidden must be heads * 128 and a multiple of 64");
     if (c.layers < 1 || c.mlp < 64 || c.mlp % 64 || c.vocab < 64 || c.vocab % 64)
@@ -583,6 +773,11 @@ cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
     if (c.max_batch < 1 || c.max_batch > MAX_ROWS) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: max_batch must be 1..256");
     if (c.max_len < 1 || c.max_len > 8192) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: max_len must be 1..8192");
     if (!(c.rms_eps > 0.0f) || !(c.rope_theta > 0.0f)) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: rms_eps and rope_theta must be positive");
+    if (c.grouped_kv && gqa_attn_lds_bytes(c.heads / c.kv_heads, c.max_len) > LDS_PER_CU)
+        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: grouped_kv with heads / kv_heads = " + std::to_string(c.heads / c.kv_heads) +
+                                               " and max_len = " + std::to_string(c.max_len) + " needs " +
+                                               std::to_string(gqa_attn_lds_bytes(c.heads / c.kv_heads, c.max_len)) +
+                                               " bytes of LDS for the token step's scores, a CU has 163840: lower max_len");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return cgpt_fail(CGPT_ERR_NO_DEVICE, "cgpt_llm_create: no HIP device visible (this library has no CPU fallback)");
@@ -590,11 +785,19 @@ cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
     HIPCHK(hipSetDevice(c.device));
     HIPCHK(decode_gemm_prepare());                        // kernel attributes now: nothing but launches is left for a captured stream
     HIPCHK(score_prepare());
+    if (c.grouped_kv) {                                   // the grouped step attention's dynamic LDS, for this handle's longest row
+        switch (c.heads / c.kv_heads) {
+            case 1: HIPCHK(gqa_attn_prepare<1>(c.max_len)); break;
+            case 2: HIPCHK(gqa_attn_prepare<2>(c.max_len)); break;
+            case 4: HIPCHK(gqa_attn_prepare<4>(c.max_len)); break;
+            default: HIPCHK(gqa_attn_prepare<8>(c.max_len)); break;
+        }
+    }
     cgpt_llm* m = new cgpt_llm();
     m->cfg = c;
     m->layers.resize(c.layers);
     m->expected = 3 + (size_t)c.layers * 9;
-    const size_t H = c.hidden, F = c.mlp, V = c.vocab, hs = sizeof(half_t);
+    const size_t H = c.hidden, F = c.mlp, V = c.vocab, hs = sizeof(half_t), NQ = (size_t)qkv_width(c);
     auto up256 = [](size_t n) { return (n + 255) / 256 * 256; };   // the prefill's GEMM reads whole 256-row tiles of W (pad rows: zeros)
     auto fail = [&](cgpt_status s) { cgpt_llm_destroy(m); return s; };
     cgpt_status s = CGPT_OK;
@@ -612,7 +815,7 @@ cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
     za(up256(V) * H * hs, &m->lm_head);
     m->weight_bytes += (int64_t)(V * H * hs);
     for (Layer& L : m->layers) {
-        mat(L.wqkv, 3 * H, H);
+        mat(L.wqkv, NQ, H);
         mat(L.wo, H, H);
         mat(L.wgu, 2 * F, H);
         mat(L.wdown, H, F);
@@ -620,11 +823,11 @@ cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
         za(H * hs, &L.ln2);
     }
     if (int8)                                             // the largest fused layer matrix, up256(2 mlp) x hidden at LLaMA's shapes
-        counted(std::max(std::max(up256(3 * H) * H, up256(2 * F) * H), up256(H) * std::max(H, F)) * hs, &m->scratch);
+        counted(std::max(std::max(up256(NQ) * H, up256(2 * F) * H), up256(H) * std::max(H, F)) * hs, &m->scratch);
     // activations: whole 256-row tiles (the GEMM stages every row of its tile; rows past the batch hold zeros)
     za(MAX_ROWS * H * hs, &m->h);
     za(MAX_ROWS * H * hs, &m->xn);
-    za(MAX_ROWS * 3 * H * hs, &m->qkv);
+    za(MAX_ROWS * NQ * hs, &m->qkv);
     za(MAX_ROWS * H * hs, &m->attn);
     za(MAX_ROWS * F * hs, &m->act);
     za(MAX_ROWS * V * sizeof(float), &m->logits);
@@ -633,7 +836,7 @@ cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
     za(sizeof(int), &m->live);
     za(sizeof(int), &m->live_steps);
     size_t slab = 0;
-    const int shapes[5][2] = {{(int)(3 * H), (int)H}, {(int)H, (int)H}, {(int)(2 * F), (int)H}, {(int)H, (int)F}, {(int)V, (int)H}};
+    const int shapes[5][2] = {{(int)NQ, (int)H}, {(int)H, (int)H}, {(int)(2 * F), (int)H}, {(int)H, (int)F}, {(int)V, (int)H}};
     for (auto& sh : shapes) slab = std::max(slab, decode_gemm_slab_bytes(sh[0], sh[1]));
     za(std::max(slab, (size_t)16), &m->slabs);
     za((size_t)c.max_len * HD * hs, &m->rope);
@@ -669,7 +872,7 @@ cgpt_status cgpt_llm_weight_bytes(cgpt_llm_handle h, int64_t* out) {
 cgpt_status cgpt_llm_load_weight_f16(cgpt_llm_handle h, const char* name, const void* data_dev, int64_t numel, void* stream) {
     if (!h || !name || !data_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_load_weight_f16: null argument");
     const cgpt_llm_config& c = h->cfg;
-    const int64_t H = c.hidden, F = c.mlp, V = c.vocab;
+    const int64_t H = c.hidden, F = c.mlp, V = c.vocab, KV = (int64_t)c.kv_heads * HD;       // KV == H on a plain handle
     hipStream_t st = (hipStream_t)stream;
     const std::string n(name);
     half_t* dst = nullptr;
@@ -686,8 +889,8 @@ cgpt_status cgpt_llm_load_weight_f16(cgpt_llm_handle h, const char* name, const 
         const std::string rest(name + used);
         Layer& L = h->layers[li];
         if (rest == "self_attn.q_proj.weight") { mat = &L.wqkv; want = H * H; K = H; }
-        else if (rest == "self_attn.k_proj.weight") { mat = &L.wqkv; row0 = H; want = H * H; K = H; }
-        else if (rest == "self_attn.v_proj.weight") { mat = &L.wqkv; row0 = 2 * H; want = H * H; K = H; }
+        else if (rest == "self_attn.k_proj.weight") { mat = &L.wqkv; row0 = H; want = KV * H; K = H; }
+        else if (rest == "self_attn.v_proj.weight") { mat = &L.wqkv; row0 = H + KV; want = KV * H; K = H; }
         else if (rest == "self_attn.o_proj.weight") { mat = &L.wo; want = H * H; K = H; }
         else if (rest == "mlp.gate_proj.weight") { mat = &L.wgu; want = F * H; K = H; interleave = 0; }
         else if (rest == "mlp.up_proj.weight") { mat = &L.wgu; want = F * H; K = H; interleave = 1; }
@@ -838,7 +1041,7 @@ static cgpt_status grow_workspace(cgpt_llm_handle h, int64_t rows, const std::st
     if (rows <= h->p_rows) return CGPT_OK;                 // grows only; a second call with the same sizes does nothing
     HIPCHK(hipSetDevice(h->cfg.device));
     const size_t H = h->cfg.hidden, F = h->cfg.mlp, hs = sizeof(half_t);
-    const size_t cols[7] = {H, H, 3 * H, H, H, 2 * F, F};
+    const size_t cols[7] = {H, H, (size_t)qkv_width(h->cfg), H, H, 2 * F, F};
     // The larger workspace is built beside the one in use and takes its place only when it is complete: a failure leaves the
     // handle as it was.  The replaced buffers are NOT freed (they stay in `allocs` until destroy): a graph captured before this
     // call replays on their addresses.

@@ -77,10 +77,14 @@ __global__ __launch_bounds__(256) void llm_prefill_addnorm_kernel(const half_t* 
 // rotated k and the v go to cache row p of (b, head).  The arithmetic is llm_attn_kernel's head: x' = x cos + rotate_half(x) sin,
 // each product and the sum rounded to fp16.  RAGGED: the rotary angle of buffer position p is table row p - start[b] (start clamped
 // into 0 .. L-1); pad positions p < start[b] are left alone -- q is not rotated, their cache rows are NOT written.
-template <bool RAGGED>
+// GROUPED (grouped-query attention): the projection row is [hidden | kv_heads * 128 | kv_heads * 128] and the cache
+// [B, kv_heads, len_stride, 128]: q is rotated for all heads; k is rotated, and k / v written, by the threads of heads 0 .. kv_heads-1.
+// The plain instantiation never reads kv_heads.
+template <bool RAGGED, bool GROUPED>
 __global__ __launch_bounds__(256) void llm_prefill_rope_kernel(half_t* __restrict__ qkv, int64_t rows, int L, int hidden, int heads,
                                                                half_t* __restrict__ Kc, half_t* __restrict__ Vc, int64_t len_stride,
-                                                               const half_t* __restrict__ rope, const int* __restrict__ starts) {
+                                                               const half_t* __restrict__ rope, const int* __restrict__ starts,
+                                                               int kv_heads) {
     const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (id >= rows * heads * 8) return;
     const int c8 = (int)(id & 7) * 8;
@@ -93,12 +97,28 @@ __global__ __launch_bounds__(256) void llm_prefill_rope_kernel(half_t* __restric
         if (p < s) return;
         rp = p - s;
     }
-    half_t* q = qkv + r * 3 * hidden + h * HD + c8;
-    half_t* k = q + hidden;
-    const half_t* v = k + hidden;
-    const int64_t crow = ((int64_t)(b * heads + h) * len_stride + p) * HD + c8;
     const h16x8 cs = *reinterpret_cast<const h16x8*>(rope + (int64_t)rp * HD + c8);
     const h16x8 sn = *reinterpret_cast<const h16x8*>(rope + (int64_t)rp * HD + 64 + c8);
+    if constexpr (GROUPED) {
+        if (h >= kv_heads) {                                 // a query head without a K/V head of its own: q only
+            half_t* q = qkv + r * (hidden + 2 * kv_heads * HD) + h * HD + c8;
+            const h16x8 q0 = *reinterpret_cast<const h16x8*>(q), q1 = *reinterpret_cast<const h16x8*>(q + 64);
+            h16x8 qa, qb;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float c = (float)cs[e], s = (float)sn[e];
+                qa[e] = (half_t)(mul_f16((float)q0[e], c) - mul_f16((float)q1[e], s));
+                qb[e] = (half_t)(mul_f16((float)q1[e], c) + mul_f16((float)q0[e], s));
+            }
+            *reinterpret_cast<h16x8*>(q) = qa;
+            *reinterpret_cast<h16x8*>(q + 64) = qb;
+            return;
+        }
+    }
+    half_t* q = qkv + r * (GROUPED ? hidden + 2 * kv_heads * HD : 3 * hidden) + h * HD + c8;
+    half_t* k = q + hidden;                                  // head h of the k block: h < kv_heads
+    const half_t* v = k + (GROUPED ? kv_heads * HD : hidden);
+    const int64_t crow = ((int64_t)(b * (GROUPED ? kv_heads : heads) + h) * len_stride + p) * HD + c8;
     const h16x8 q0 = *reinterpret_cast<const h16x8*>(q), q1 = *reinterpret_cast<const h16x8*>(q + 64);
     const h16x8 k0 = *reinterpret_cast<const h16x8*>(k), k1 = *reinterpret_cast<const h16x8*>(k + 64);
     h16x8 qa, qb, ka, kb;
@@ -135,11 +155,14 @@ __global__ __launch_bounds__(256) void llm_prefill_rope_kernel(half_t* __restric
 // query leaves before the first barrier (block-uniform).
 constexpr int AQ = 64, AKC = 64, AKP = HD + 8, AVP = AKC + 8;
 
-template <bool RAGGED>
+// GROUPED: query head h reads K/V head h / (heads / kv_heads) of a [B, kv_heads, len_stride, 128] cache, and a
+// projection row is hidden + 2 kv_heads 128 wide.  Each query head still stages its K/V head for itself (the G heads of a group do
+// not share a staged chunk here: this kernel is 3 % of a prefill).  The plain instantiation never reads kv_heads.
+template <bool RAGGED, bool GROUPED>
 __global__ __launch_bounds__(256) void llm_prefill_attn_kernel(const half_t* __restrict__ qkv, int Lbuf, int hidden, int heads,
                                                                const half_t* __restrict__ Kc, const half_t* __restrict__ Vc,
                                                                int64_t len_stride, half_t* __restrict__ out,
-                                                               const int* __restrict__ starts) {
+                                                               const int* __restrict__ starts, int kv_heads) {
     __shared__ __attribute__((aligned(16))) half_t ks[AKC * AKP];
     __shared__ __attribute__((aligned(16))) half_t vt[HD * AVP];
     const int b = blockIdx.x / heads, h = blockIdx.x % heads;
@@ -159,14 +182,16 @@ __global__ __launch_bounds__(256) void llm_prefill_attn_kernel(const half_t* __r
     }
     const int L = Lbuf - s;                                  // real positions; everything below is relative to the first of them
     const int64_t row0 = (int64_t)b * Lbuf + s;
-    const half_t* Kh = Kc + ((int64_t)(b * heads + h) * len_stride + s) * HD;
-    const half_t* Vh = Vc + ((int64_t)(b * heads + h) * len_stride + s) * HD;
+    const int64_t chead = GROUPED ? (int64_t)b * kv_heads + h / (heads / kv_heads) : (int64_t)(b * heads + h);
+    const int64_t ldq = GROUPED ? hidden + 2 * kv_heads * HD : 3 * hidden;
+    const half_t* Kh = Kc + (chead * len_stride + s) * HD;
+    const half_t* Vh = Vc + (chead * len_stride + s) * HD;
 
     // B fragments of the wave's 16 queries: Q[q0 + r15][32 d + 8 g ..]
     h16x8 qf[4];
     {
         const int qrow = min(q0 + r15, L - 1);
-        const half_t* qp = qkv + (row0 + qrow) * 3 * hidden + h * HD + 8 * g;
+        const half_t* qp = qkv + (row0 + qrow) * ldq + h * HD + 8 * g;
 #pragma unroll
         for (int d = 0; d < 4; ++d) qf[d] = *reinterpret_cast<const h16x8*>(qp + 32 * d);
     }
@@ -291,29 +316,48 @@ hipError_t launch_prefill_addnorm(const half_t* x, const half_t* delta, int64_t 
     return hipGetLastError();
 }
 
-hipError_t launch_prefill_rope(half_t* qkv, int B, int L, int hidden, int heads, half_t* Kc, half_t* Vc, int64_t len_stride,
+hipError_t launch_prefill_rope(half_t* qkv, int B, int L, int hidden, int heads, int kv_heads, half_t* Kc, half_t* Vc, int64_t len_stride,
                                const half_t* rope, const int32_t* starts, hipStream_t stream) {
-    if (B < 1 || L < 1 || L > len_stride || hidden != heads * HD || !qkv || !Kc || !Vc || !rope) return hipErrorInvalidValue;
+    if (B < 1 || L < 1 || L > len_stride || hidden != heads * HD || kv_heads < 1 || kv_heads > heads || heads % kv_heads || !qkv || !Kc ||
+        !Vc || !rope)
+        return hipErrorInvalidValue;
     const int64_t rows = (int64_t)B * L, threads = rows * heads * 8;
     const dim3 grid((unsigned)((threads + 255) / 256));
-    if (starts)
-        hipLaunchKernelGGL(llm_prefill_rope_kernel<true>, grid, dim3(256), 0, stream, qkv, rows, L, hidden, heads, Kc, Vc, len_stride, rope,
-                           starts);
+    const bool grouped = kv_heads != heads;
+    if (grouped && starts)
+        hipLaunchKernelGGL((llm_prefill_rope_kernel<true, true>), grid, dim3(256), 0, stream, qkv, rows, L, hidden, heads, Kc, Vc, len_stride,
+                           rope, starts, kv_heads);
+    else if (grouped)
+        hipLaunchKernelGGL((llm_prefill_rope_kernel<false, true>), grid, dim3(256), 0, stream, qkv, rows, L, hidden, heads, Kc, Vc, len_stride,
+                           rope, nullptr, kv_heads);
+    else if (starts)
+        hipLaunchKernelGGL((llm_prefill_rope_kernel<true, false>), grid, dim3(256), 0, stream, qkv, rows, L, hidden, heads, Kc, Vc, len_stride,
+                           rope, starts, heads);
     else
-        hipLaunchKernelGGL(llm_prefill_rope_kernel<false>, grid, dim3(256), 0, stream, qkv, rows, L, hidden, heads, Kc, Vc, len_stride, rope,
-                           nullptr);
+        hipLaunchKernelGGL((llm_prefill_rope_kernel<false, false>), grid, dim3(256), 0, stream, qkv, rows, L, hidden, heads, Kc, Vc, len_stride,
+                           rope, nullptr, heads);
     return hipGetLastError();
 }
 
-hipError_t launch_prefill_attention(const half_t* qkv, int B, int L, int hidden, int heads, const half_t* Kc, const half_t* Vc,
+hipError_t launch_prefill_attention(const half_t* qkv, int B, int L, int hidden, int heads, int kv_heads, const half_t* Kc, const half_t* Vc,
                                     int64_t len_stride, half_t* out, const int32_t* starts, hipStream_t stream) {
-    if (B < 1 || L < 1 || L > len_stride || hidden != heads * HD || !qkv || !Kc || !Vc || !out) return hipErrorInvalidValue;
+    if (B < 1 || L < 1 || L > len_stride || hidden != heads * HD || kv_heads < 1 || kv_heads > heads || heads % kv_heads || !qkv || !Kc ||
+        !Vc || !out)
+        return hipErrorInvalidValue;
     const dim3 grid((unsigned)(B * heads), (unsigned)((L + AQ - 1) / AQ));
-    if (starts)
-        hipLaunchKernelGGL(llm_prefill_attn_kernel<true>, grid, dim3(256), 0, stream, qkv, L, hidden, heads, Kc, Vc, len_stride, out, starts);
+    const bool grouped = kv_heads != heads;
+    if (grouped && starts)
+        hipLaunchKernelGGL((llm_prefill_attn_kernel<true, true>), grid, dim3(256), 0, stream, qkv, L, hidden, heads, Kc, Vc, len_stride, out,
+                           starts, kv_heads);
+    else if (grouped)
+        hipLaunchKernelGGL((llm_prefill_attn_kernel<false, true>), grid, dim3(256), 0, stream, qkv, L, hidden, heads, Kc, Vc, len_stride, out,
+                           nullptr, kv_heads);
+    else if (starts)
+        hipLaunchKernelGGL((llm_prefill_attn_kernel<true, false>), grid, dim3(256), 0, stream, qkv, L, hidden, heads, Kc, Vc, len_stride, out,
+                           starts, heads);
     else
-        hipLaunchKernelGGL(llm_prefill_attn_kernel<false>, grid, dim3(256), 0, stream, qkv, L, hidden, heads, Kc, Vc, len_stride, out,
-                           nullptr);
+        hipLaunchKernelGGL((llm_prefill_attn_kernel<false, false>), grid, dim3(256), 0, stream, qkv, L, hidden, heads, Kc, Vc, len_stride, out,
+                           nullptr, heads);
     return hipGetLastError();
 }
 

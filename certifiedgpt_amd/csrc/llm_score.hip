@@ -65,10 +65,14 @@ __global__ __launch_bounds__(256) void llm_score_embed_kernel(const long long* _
 // acc e^(m - max) + sum p v).  The state of a query sits in LDS between chunks; every lane reads back only addresses it wrote
 // itself (lanes that share a dim group hold equal values after the butterflies), so no barrier inside a wavefront is needed.
 // The chunk grid depends on L alone and the tail walk on (c, j) alone: a query's key order is fixed by (L, candidate, j).
+// GROUPED (grouped-query attention): query head h reads K/V head kh = h / (heads / kv_heads) -- of the
+// [B, kv_heads, len_stride, 128] cache, and of the tail rows' k / v in a projection row hidden + 2 kv_heads 128 wide.  The G heads of a
+// group do not share a staged chunk here.  The plain instantiation never reads kv_heads.
+template <bool GROUPED>
 __global__ __launch_bounds__(256) void llm_score_attn_kernel(const half_t* __restrict__ qkv, ScoreCands t, int L, int hidden, int heads,
                                                              const half_t* __restrict__ Kc, const half_t* __restrict__ Vc,
                                                              int64_t len_stride, const half_t* __restrict__ rope,
-                                                             half_t* __restrict__ out) {
+                                                             half_t* __restrict__ out, int kv_heads) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int S = t.off[t.n];
     half_t* ks = reinterpret_cast<half_t*>(smem);             // [KC][128] staged prompt keys
@@ -81,16 +85,18 @@ __global__ __launch_bounds__(256) void llm_score_attn_kernel(const half_t* __res
     const int b = blockIdx.x / heads, h = blockIdx.x % heads;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t row0 = (int64_t)b * S;
-    const half_t* Kh = Kc + (int64_t)(b * heads + h) * len_stride * HD;
-    const half_t* Vh = Vc + (int64_t)(b * heads + h) * len_stride * HD;
+    const int kh = GROUPED ? h / (heads / kv_heads) : h;
+    const int64_t ldq = GROUPED ? hidden + 2 * kv_heads * HD : 3 * hidden;
+    const half_t* Kh = Kc + (int64_t)(b * (GROUPED ? kv_heads : heads) + kh) * len_stride * HD;
+    const half_t* Vh = Vc + (int64_t)(b * (GROUPED ? kv_heads : heads) + kh) * len_stride * HD;
 
     for (int i = tid; i < S * 64; i += 256) {                 // thread (s, p) owns the rotary pair (p, p + 64) of tail row s
         const int s = i >> 6, p = i & 63;
         int c, j;
         slot_of(t, s, c, j);
-        const half_t* q = qkv + (row0 + s) * 3 * hidden + h * HD;
-        const half_t* k = q + hidden;
-        const half_t* v = k + hidden;
+        const half_t* q = qkv + (row0 + s) * ldq + h * HD;
+        const half_t* k = qkv + (row0 + s) * ldq + hidden + kh * HD;
+        const half_t* v = k + (GROUPED ? kv_heads * HD : hidden);
         const half_t* rp = rope + (int64_t)(L + j) * HD;
         const float cs = (float)rp[p], sn = (float)rp[64 + p];
         const float q0 = (float)q[p], q1 = (float)q[p + 64], k0 = (float)k[p], k1 = (float)k[p + 64];
@@ -297,7 +303,10 @@ bool cands_ok(const ScoreCands& t) {
 }  // namespace
 
 hipError_t score_prepare() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(llm_score_attn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(llm_score_attn_kernel<false>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_lds_bytes(SCORE_MAX_TAIL));
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(llm_score_attn_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)attn_lds_bytes(SCORE_MAX_TAIL));
 }
 
@@ -308,12 +317,17 @@ hipError_t launch_score_embed(const long long* cand_tokens, const ScoreCands& t,
     return hipGetLastError();
 }
 
-hipError_t launch_score_attention(const half_t* qkv, const ScoreCands& t, int B, int L, int hidden, int heads, const half_t* Kc,
+hipError_t launch_score_attention(const half_t* qkv, const ScoreCands& t, int B, int L, int hidden, int heads, int kv_heads, const half_t* Kc,
                                   const half_t* Vc, int64_t len_stride, const half_t* rope, half_t* out, hipStream_t stream) {
-    if (!cands_ok(t) || t.off[t.n] < 1 || B < 1 || L < 1 || L > len_stride || hidden != heads * HD || !qkv || !Kc || !Vc || !rope || !out)
+    if (!cands_ok(t) || t.off[t.n] < 1 || B < 1 || L < 1 || L > len_stride || hidden != heads * HD || kv_heads < 1 || kv_heads > heads ||
+        heads % kv_heads || !qkv || !Kc || !Vc || !rope || !out)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(llm_score_attn_kernel, dim3((unsigned)(B * heads)), dim3(256), attn_lds_bytes(t.off[t.n]), stream, qkv, t, L, hidden,
-                       heads, Kc, Vc, len_stride, rope, out);
+    if (kv_heads != heads)
+        hipLaunchKernelGGL(llm_score_attn_kernel<true>, dim3((unsigned)(B * heads)), dim3(256), attn_lds_bytes(t.off[t.n]), stream, qkv, t, L,
+                           hidden, heads, Kc, Vc, len_stride, rope, out, kv_heads);
+    else
+        hipLaunchKernelGGL(llm_score_attn_kernel<false>, dim3((unsigned)(B * heads)), dim3(256), attn_lds_bytes(t.off[t.n]), stream, qkv, t, L,
+                           hidden, heads, Kc, Vc, len_stride, rope, out, heads);
     return hipGetLastError();
 }
 

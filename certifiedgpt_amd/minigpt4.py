@@ -186,6 +186,31 @@ def int8_state_dict(llama_model, device=None):
     return out
 
 
+GQA_RATIOS = (1, 2, 4, 8)                                              # heads / kv_heads the grouped kernels are instantiated for
+
+
+def expand_kv_state_dict(llama_model):
+    """The state dict of the multi-head twin of a grouped-query `llama_model`: every `k_proj` / `v_proj` weight [kv_heads * d, hidden]
+    becomes [heads * d, hidden] with each head's block of d rows repeated G = heads / kv_heads times in `repeat_interleave` order
+    (twin head h = K/V head h // G, which is HF's `repeat_kv`); everything else as it is.  Loadable into an HF model of the same
+    config with `num_key_value_heads = num_attention_heads`, which then computes what the grouped model computes: the oracle of
+    grouped_kv=True, in the role `int8_state_dict` has for weights="int8".  Plain torch; works on CPU tensors."""
+    cfg = llama_model.config
+    heads = int(cfg.num_attention_heads)
+    kv = int(getattr(cfg, "num_key_value_heads", None) or heads)
+    if kv < 1 or heads % kv:
+        raise ValueError(f"expand_kv_state_dict: num_key_value_heads {kv} does not divide num_attention_heads {heads}")
+    G = heads // kv
+    out = {}
+    for name, w in llama_model.state_dict().items():
+        if name.endswith("self_attn.k_proj.weight") or name.endswith("self_attn.v_proj.weight"):
+            d = w.shape[0] // kv
+            out[name] = w.detach().view(kv, d, w.shape[1]).repeat_interleave(G, dim=0).reshape(heads * d, w.shape[1]).clone()
+        else:
+            out[name] = w.detach().clone()
+    return out
+
+
 class _LinearRoute:
     """Routes the bias-free fp16 `nn.Linear` layers of a frozen decoder through libcgpt's MFMA GEMM (`cgpt_linear_f16`, the kernel
     of the ViT's qkv / proj / MLP) for calls with at least `min_rows` rows, i.e. the PREFILL of a Monte-Carlo batch (200 rows x 44
@@ -253,12 +278,14 @@ class _LinearRoute:
         return ctx()
 
 
-def hip_decode_unsupported(llama_model, max_batch=None):
+def hip_decode_unsupported(llama_model, max_batch=None, grouped_kv=False):
     """Every property of `llama_model` (and of the classifier batch) that keeps it off the native token step (`decode="hip"`,
     csrc/llm.hip), as a list of sentences; empty = supported.  The step kernels are written for HF `LlamaForCausalLM` in fp16 on
     a HIP device: bias-free linears, RMSNorm, `rotate_half` rotary with the default (unscaled) rope_theta law, as many K/V heads
     as query heads, head size 128, SwiGLU, no sliding window -- Vicuna-7B / 13B.  ALL failing properties are collected, so one
-    message names them all."""
+    message names them all.
+    grouped_kv=True (the engine's grouped-query mode): fewer K/V heads than query heads are accepted when they
+    divide them and heads / kv_heads is 1, 2, 4 or 8 -- Llama-3-8B (32 / 8), Llama-2-70B's shape (64 / 8)."""
     cfg = getattr(llama_model, "config", None)
     bad = []
     if type(llama_model).__name__ != "LlamaForCausalLM" or cfg is None:
@@ -274,7 +301,11 @@ def hip_decode_unsupported(llama_model, max_batch=None):
     if head_dim != 128 or hidden != heads * 128:
         bad.append(f"head size: head_dim {head_dim} with hidden_size {hidden} / {heads} heads (head_dim 128 and hidden = heads x 128 required)")
     kv = int(getattr(cfg, "num_key_value_heads", None) or heads)
-    if kv != heads:
+    if grouped_kv:
+        if kv < 1 or heads % kv or heads // kv not in GQA_RATIOS:
+            bad.append(f"K/V heads: num_key_value_heads {kv} with num_attention_heads {heads} (grouped_kv takes a count that divides "
+                       f"the query heads with a ratio in {list(GQA_RATIOS)})")
+    elif kv != heads:
         bad.append(f"K/V heads: num_key_value_heads {kv} != num_attention_heads {heads} (grouped-query attention is not supported)")
     with_bias = [n for n, m in llama_model.named_modules() if isinstance(m, torch.nn.Linear) and m.bias is not None]
     if getattr(cfg, "attention_bias", False) or getattr(cfg, "mlp_bias", False) or with_bias:
@@ -313,7 +344,7 @@ class _HipDecoder:
     stream -- no host sync, capturable -- on the K/V buffers the prefill filled, in place."""
     MAX_LEN = 4096                                                     # positions the rotary table covers (prompt + new tokens)
 
-    def __init__(self, llama_model, max_batch, weights="fp16", early_stop=False):
+    def __init__(self, llama_model, max_batch, weights="fp16", early_stop=False, grouped_kv=False):
         import ctypes as C
         from . import _lib
         if weights not in _lib.LLM_WEIGHT_FORMATS:
@@ -321,23 +352,29 @@ class _HipDecoder:
         self.weights = weights
         self.early_stop = bool(early_stop)
         self._greedy_ran = False                                       # live_steps has nothing to report before the first `greedy`
-        bad = hip_decode_unsupported(llama_model, max_batch)
+        self.grouped_kv = bool(grouped_kv)
+        bad = hip_decode_unsupported(llama_model, max_batch, grouped_kv=self.grouped_kv)
         if bad:
             raise ValueError('decode="hip" does not support this decoder -- ' + "; ".join(bad))
         self._C, self._lib_mod, self.L = C, _lib, _lib.lib()
         cfg = llama_model.config
         self.device = next(llama_model.parameters()).device
         self.layers, self.heads, self.vocab = int(cfg.num_hidden_layers), int(cfg.num_attention_heads), int(cfg.vocab_size)
+        # K/V heads of the caches every entry works on: the model's own count under grouped_kv, the query heads otherwise
+        self.kv_heads = int(getattr(cfg, "num_key_value_heads", None) or self.heads) if self.grouped_kv else self.heads
         self.max_batch = int(max_batch)
         # fp16 handles pass the config up to max_len, which every build of the library accepts (an A/B against an older build loads it
         # through CGPT_LIB_PATH); weight_format travels only when it says something
-        size = C.sizeof(_lib.LlmConfig) if weights != "fp16" else _lib.LLM_CONFIG_SIZE_F16
+        # and so does grouped_kv: the extended struct (cgpt_llm_config_gqa) is sent only when the flag is set
+        size = (C.sizeof(_lib.LlmConfigGqa) if self.grouped_kv else
+                C.sizeof(_lib.LlmConfig) if weights != "fp16" else _lib.LLM_CONFIG_SIZE_F16)
         c = _lib.LlmConfig(struct_size=size, weight_format=_lib.LLM_WEIGHT_FORMATS[weights], device=self.device.index or 0, hidden=int(cfg.hidden_size),
-                           layers=self.layers, heads=self.heads, kv_heads=self.heads, head_dim=128, mlp=int(cfg.intermediate_size),
+                           layers=self.layers, heads=self.heads, kv_heads=self.kv_heads, head_dim=128, mlp=int(cfg.intermediate_size),
                            vocab=self.vocab, rms_eps=float(cfg.rms_norm_eps), rope_theta=_rope_theta(cfg),
                            max_batch=self.max_batch, max_len=self.MAX_LEN)
         self.handle = C.c_void_p()
-        _lib.check(self.L.cgpt_llm_create(C.byref(c), C.byref(self.handle)))
+        ext = _lib.LlmConfigGqa(base=c, grouped_kv=int(self.grouped_kv), reserved=0)     # create reads past `base` only when the size says so
+        _lib.check(self.L.cgpt_llm_create(C.byref(ext.base), C.byref(self.handle)))
         st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         wanted = ["model.embed_tokens.weight", "model.norm.weight", "lm_head.weight"]
         for i in range(self.layers):
@@ -378,14 +415,15 @@ class _HipDecoder:
 
     def _cache_tables(self, k_bufs, v_bufs, B, need_len):
         """Host tables of the per-layer K / V device pointers, after checking every buffer is what the kernels index:
-        [B, heads, len_stride, 128] fp16, contiguous, on the handle's device, long enough for the last appended row."""
+        [B, heads, len_stride, 128] fp16 ([B, kv_heads, len_stride, 128] under grouped_kv), contiguous, on the handle's device, long
+        enough for the last appended row."""
         C = self._C
         assert len(k_bufs) == len(v_bufs) == self.layers, "one K and one V buffer per layer"
         stride = int(k_bufs[0].shape[2])
         assert need_len <= stride and need_len <= self.MAX_LEN, (need_len, stride, self.MAX_LEN)
         for t in list(k_bufs) + list(v_bufs):
             assert (t.dtype == torch.float16 and t.device == self.device and t.is_contiguous()
-                    and tuple(t.shape) == (B, self.heads, stride, 128)), (tuple(t.shape), t.dtype, t.device)
+                    and tuple(t.shape) == (B, self.kv_heads, stride, 128)), (tuple(t.shape), t.dtype, t.device)
         kp = (C.c_void_p * self.layers)(*[t.data_ptr() for t in k_bufs])
         vp = (C.c_void_p * self.layers)(*[t.data_ptr() for t in v_bufs])
         return kp, vp, stride
@@ -516,6 +554,7 @@ class MiniGPT4Classifier:
        :param prompt_bucket: None | int >= 1 (with ragged="hip") -- padded prompt lengths are rounded up to a multiple of it
        :param weights: "fp16" (default) | "int8" (with decode="hip" and prefill="hip") -- how the native engine holds the layer linears
        :param early_stop: False (default) | True (with decode="hip") -- the native token steps do no work once every row has its EOS
+       :param grouped_kv: False (default) | True (with decode="hip") -- the native engine takes a grouped-query decoder; see __init__
        :param end_sym: text appended to every candidate answer of `multi_select` ("\n": the reference's default; its VQA configs: "###")
        :param label_smoothing: of the answer loss (0.1: modeling_llama.py:105)
        :param score: "hf" (default) | "hip" -- who computes the answer losses of `multi_select`; see __init__
@@ -532,7 +571,7 @@ class MiniGPT4Classifier:
     def __init__(self, encoder, llama_model, llama_tokenizer, prompt, label_map, max_new_tokens=20, max_batch=None,
                  generate_kwargs=None, decode="hf", prefill_linear="torch", prefill="model", ragged="hf", prompt_bucket=None,
                  weights="fp16", end_sym="\n", label_smoothing=0.1, score="hf", classify="generate", candidates=None,
-                 early_stop=False):
+                 early_stop=False, grouped_kv=False):
         self.encoder = encoder
         self.llama_model = llama_model
         self.llama_tokenizer = llama_tokenizer
@@ -585,6 +624,13 @@ class MiniGPT4Classifier:
         #   device that every step kernel reads first; the captured graph keeps all its launches and one graph serves every finishing
         #   step).  Tokens and answers are bit for bit those with it off; `last_live_steps()` tells how many steps ran.  Works with
         #   either prefill, with ragged = "hip" and with weights = "int8".  early_stop = False (default): every step runs, as before.
+        # grouped_kv = True (with decode = "hip" only; anything else is a ValueError): the native engine runs grouped-query attention
+        #   (cgpt_llm_config_gqa.grouped_kv): a decoder with fewer K/V heads than query heads -- heads / kv_heads in
+        #   {1, 2, 4, 8}: Llama-3-8B's 32 / 8 -- is accepted, every K/V buffer is [rows, kv_heads, positions, 128] (1 / G of the pool),
+        #   and the token step reads a K/V head once for the G query heads that share it.  Works with either prefill (HF's cache holds
+        #   the un-repeated heads too), ragged = "hip", prompt_bucket, weights = "int8", early_stop and score = "hip".  Every result is
+        #   what the engine gives on the multi-head twin `expand_kv_state_dict(llama_model)` (tests/test_gpu_llm_gqa.py).
+        #   grouped_kv = False (default): as before, a grouped-query decoder is a ValueError.
         # score = "hf" (default): `multi_select` / `answer_losses_from_embeds` run the model's own forward once per candidate over the
         #   concatenated prompt + answer embeds, as the reference does (works on the CPU); counted in decode_stats["hf_score_forwards"].
         # score = "hip" (with decode = "hip" AND prefill = "hip" only; anything else is a ValueError, never another engine): ONE native
@@ -617,6 +663,11 @@ class MiniGPT4Classifier:
         if early_stop and decode != "hip":
             raise ValueError(f'early_stop=True needs decode="hip" (got decode={decode!r}): only the native token steps can be switched '
                              "off on the device")
+        if not isinstance(grouped_kv, bool):
+            raise ValueError(f"grouped_kv={grouped_kv!r}: expected False or True")
+        if grouped_kv and decode != "hip":
+            raise ValueError(f'grouped_kv=True needs decode="hip" (got decode={decode!r}): grouped-query attention is a mode of the '
+                             "native engine")
         if prompt_bucket is not None:
             if isinstance(prompt_bucket, bool) or not isinstance(prompt_bucket, int) or prompt_bucket < 1:
                 raise ValueError(f"prompt_bucket={prompt_bucket!r}: expected None or an int >= 1")
@@ -651,7 +702,10 @@ class MiniGPT4Classifier:
         self.prefill_linear = prefill_linear
         self.weights = weights
         self.early_stop = early_stop
-        self._hip = _HipDecoder(llama_model, self.max_batch, weights=weights, early_stop=early_stop) if decode == "hip" else None
+        self.grouped_kv = grouped_kv
+        # the keyword reaches the engine only when it is set (as `law` reaches an encoder)
+        gqa = {"grouped_kv": True} if grouped_kv else {}
+        self._hip = _HipDecoder(llama_model, self.max_batch, weights=weights, early_stop=early_stop, **gqa) if decode == "hip" else None
         self.routed_linears = (_LinearRoute.install(llama_model)
                                if (decode in ("graph", "hip") and prefill_linear == "cgpt" and prefill == "model") else 0)
         import collections
@@ -845,7 +899,7 @@ class MiniGPT4Classifier:
         assert starts is None or self.prefill == "hip", 'left-padded rows need prefill="hip"'
         if self.prefill == "hip":                                      # the whole decode in this library: no HF forward, no DynamicCache
             assert B <= self.max_batch, f"{B} rows > max_batch {self.max_batch} (the native decoder's workspace)"
-            shape = (B, self._hip.heads, L + self.max_new_tokens, 128)    # what PreallocLayer allocates on the other path
+            shape = (B, self._hip.kv_heads, L + self.max_new_tokens, 128)    # what PreallocLayer allocates on the other path
             k_bufs = [embs.new_empty(shape) for _ in range(self._hip.layers)]
             v_bufs = [embs.new_empty(shape) for _ in range(self._hip.layers)]
             logits = self._hip.prefill(embs.contiguous(), k_bufs, v_bufs, starts=starts)
@@ -895,6 +949,7 @@ class MiniGPT4Classifier:
         key = (embs.shape[0], embs.shape[1], embs.dtype, embs.device.index, self.max_new_tokens, bool(self.routed_linears), self.decode,
                self.prefill)
         key = key + ("ragged",) if ragged else key                    # a graph of the _ragged entries is never an unpadded one's
+        key = key + ("grouped_kv",) if self.grouped_kv else key
         return key + ("early_stop",) if self.early_stop else key      # nor is one captured with early stop on one captured without
 
     def last_live_steps(self):
@@ -1060,7 +1115,7 @@ class MiniGPT4Classifier:
         table = torch.zeros((len(toks), Tmax), dtype=torch.long)
         for c, t in enumerate(toks):
             table[c, :lens[c]] = t
-        shape = (B, hip.heads, L, 128)                                 # the prompt's rows only: scoring appends nothing
+        shape = (B, hip.kv_heads, L, 128)                              # the prompt's rows only: scoring appends nothing
         k_bufs = [embs.new_empty(shape) for _ in range(hip.layers)]
         v_bufs = [embs.new_empty(shape) for _ in range(hip.layers)]
         first = hip.prefill(embs, k_bufs, v_bufs)

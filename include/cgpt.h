@@ -314,10 +314,12 @@ cgpt_status cgpt_layernorm(const float* x_dev, int64_t ldx, const float* gamma_d
  *      minigpt_base.py:418-431 -- greedy, one new token per row, K/V cache) ----
  * A decoder is not a cgpt_model: it has its own handle.  Supported architecture (checked by cgpt_llm_create BEFORE any device
  * call): HF LlamaForCausalLM in fp16 -- bias-free linears, RMSNorm, rotate_half rotary with the default (unscaled) rope_theta
- * law, kv_heads == heads (no grouped-query attention), head_dim == 128, hidden == heads * 128, SwiGLU MLP; hidden, mlp and
- * vocab multiples of 64; max_batch <= 256 (one GEMM row tile); max_len <= 8192 (positions the rotary table covers).
- * That is Vicuna-7B / 13B.  The step entries work on the caller's K/V buffers in place, layout [B, heads, kv_len_stride, 128]
- * fp16 per layer, rows 0 .. pos-1 filled by the prefill.  The prefill is either the caller's (the model's own forward writes
+ * law, kv_heads == heads (with cgpt_llm_config_gqa.grouped_kv = 1: grouped-query attention, heads / kv_heads in {1, 2, 4, 8}, see
+ * below), head_dim == 128, hidden == heads * 128, SwiGLU MLP; hidden, mlp and vocab multiples of 64; max_batch <= 256 (one GEMM
+ * row tile); max_len <= 8192 (positions the rotary table covers).  That is Vicuna-7B / 13B, and with grouped_kv = 1 the
+ * Llama-3-8B (32 / 8 heads) and Llama-2-70B (64 / 8) shapes.  The step entries work on the caller's K/V buffers in place, layout
+ * [B, heads, kv_len_stride, 128] fp16 per layer ([B, kv_heads, kv_len_stride, 128] on a grouped_kv = 1 handle), rows 0 .. pos-1
+ * filled by the prefill.  The prefill is either the caller's (the model's own forward writes
  * those rows) or cgpt_llm_prefill: the same layers on B x L token rows in this library's kernels, filling the same buffers.
  * Rounding: where HF's fp16 eager model rounds ("LLaMA decode steps"); split-K partial sums are combined in slice
  * order, so results are bit-identical from launch to launch and a row's result does not depend on the batch around it.
@@ -330,7 +332,7 @@ typedef struct cgpt_llm_config {
     int32_t hidden;           /* 4096 (Vicuna-7B)                                                  */
     int32_t layers;           /* 32                                                                */
     int32_t heads;            /* 32                                                                */
-    int32_t kv_heads;         /* must equal heads                                                  */
+    int32_t kv_heads;         /* must equal heads unless grouped_kv = 1                            */
     int32_t head_dim;         /* must be 128                                                       */
     int32_t mlp;              /* 11008 (intermediate_size)                                         */
     int32_t vocab;            /* 32000                                                             */
@@ -341,6 +343,29 @@ typedef struct cgpt_llm_config {
     int32_t weight_format;    /* CGPT_LLM_W_F16 (0) | CGPT_LLM_W_INT8 (1): how the layer linears are held; read only when
                                  struct_size covers it -- a caller that passes the size up to max_len gets fp16 */
 } cgpt_llm_config;
+
+/* The extended config: a cgpt_llm_config followed by the switches added after weight_format.  A caller that wants one of them fills
+ * this struct, sets base.struct_size = sizeof(cgpt_llm_config_gqa) and passes &cfg.base to cgpt_llm_create, which tells the two
+ * apart by struct_size alone.  cgpt_llm_config itself keeps its fields and its two sizes (the whole struct, the struct up to
+ * max_len), so sizeof(cgpt_llm_config) + 4 stays what it has always been: header / library drift, refused.  That is why the
+ * extension is 8 bytes: `reserved` must be 0 (anything else is CGPT_ERR_INVALID) and is room for the next switch. */
+typedef struct cgpt_llm_config_gqa {
+    cgpt_llm_config base;     /* base.struct_size = sizeof(cgpt_llm_config_gqa)                    */
+    int32_t grouped_kv;       /* 0 | 1: grouped-query attention (below)                            */
+    int32_t reserved;         /* must be 0                                                         */
+} cgpt_llm_config_gqa;
+
+/* cgpt_llm_config_gqa.grouped_kv = 1: grouped-query attention.  Requires 1 <= kv_heads <= heads, heads % kv_heads == 0 and
+ * G = heads / kv_heads in {1, 2, 4, 8}; query head h reads K/V head h / G (HF's repeat_kv).  The switch is explicit because the
+ * caller owns the K/V buffers: on such a handle EVERY entry that takes k_ptrs_host / v_ptrs_host reads and writes caches laid out
+ * [B, kv_heads, kv_len_stride, 128] -- 1 / G of the bytes -- and a caller that sized or indexed them by `heads` must say that it
+ * knows.  k_proj / v_proj are loaded as [kv_heads * 128, hidden] (HF's shapes).  The token step's attention keeps G score arrays of
+ * max_len floats in LDS: a (G, max_len) pair that does not fit the CU's 160 KiB (G = 8 with max_len > 4464) is CGPT_ERR_INVALID
+ * at create.  grouped_kv = 0 (or a plain cgpt_llm_config, which has no such field) is the handle as it was, CGPT_ERR_INVALID for
+ * kv_heads != heads included; any other value of the field is CGPT_ERR_INVALID.
+ * Rounding and summation orders per query head are those of the plain handle, with one consequence of the narrower fused q/k/v
+ * projection: the decode GEMM's K split depends on N, so at hidden 4096 the grouped N = 6144 runs 2 K slices where the expanded
+ * (repeat_interleave'd) twin's N = 12288 runs 1 -- two valid summation orders, not bit-equal. */
 
 /* cgpt_llm_config.weight_format.
  * CGPT_LLM_W_INT8 (W8A16): the seven linears of every layer are held as row-wise absmax int8, one fp16 scale per output row
@@ -357,13 +382,14 @@ typedef struct cgpt_llm* cgpt_llm_handle;
 /* Allocates the library's own weight copies (fused q/k/v and gate/up, 2 bytes per parameter: 13.5 GB MORE HBM at 7B, beside the
  * HF module's; CGPT_LLM_W_INT8: 1 byte per layer-linear parameter, the row scales and ONE fp16 scratch matrix of the largest fused
  * layer matrix for the prefill, 7.2 GB at 7B) and the step workspace.  CGPT_ERR_INVALID for an unsupported config, a struct_size
- * that is neither the whole struct nor the struct up to max_len, or an unknown weight_format; CGPT_ERR_NO_DEVICE without a GPU. */
+ * that is none of the three valid ones (cgpt_llm_config_gqa, the whole cgpt_llm_config, cgpt_llm_config up to max_len), or an unknown
+ * weight_format / grouped_kv; CGPT_ERR_NO_DEVICE without a GPU. */
 cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out);
 cgpt_status cgpt_llm_destroy(cgpt_llm_handle h);
 /* Device-to-device copy of one fp16 parameter of the HF module under its state_dict name: "model.embed_tokens.weight",
  * "model.layers.<i>.self_attn.{q,k,v,o}_proj.weight", "model.layers.<i>.mlp.{gate,up,down}_proj.weight",
- * "model.layers.<i>.{input,post_attention}_layernorm.weight", "model.norm.weight", "lm_head.weight" (contiguous, PyTorch shape;
- * numel must match).  Enqueued on `stream`.  The step entries return CGPT_ERR_STATE until every name has been loaded. */
+ * "model.layers.<i>.{input,post_attention}_layernorm.weight", "model.norm.weight", "lm_head.weight" (contiguous, PyTorch shape:
+ * k_proj / v_proj are [kv_heads * 128, hidden]; numel must match).  Enqueued on `stream`.  The step entries return CGPT_ERR_STATE until every name has been loaded. */
 cgpt_status cgpt_llm_load_weight_f16(cgpt_llm_handle h, const char* name, const void* data_dev, int64_t numel, void* stream);
 /* On a CGPT_LLM_W_INT8 handle cgpt_llm_load_weight_f16 of a layer linear is a quantising kernel instead of a copy: it reads the
  * caller's fp16 rows and writes int8 rows and their scales into the fused matrix (rows keep their scales through the q/k/v fusion
@@ -373,7 +399,8 @@ cgpt_status cgpt_llm_load_weight_f16(cgpt_llm_handle h, const char* name, const 
  * RMSNorm vectors, the rotary table and the step / prefill workspaces are not counted. */
 cgpt_status cgpt_llm_weight_bytes(cgpt_llm_handle h, int64_t* out);
 /* One token step: row b feeds token tokens_dev[b] (int64) at position `pos`; layer l appends its rotated key and its value to
- * row `pos` of k_ptrs_host[l] / v_ptrs_host[l] (device buffers [B, heads, kv_len_stride, 128] fp16; the two tables are HOST
+ * row `pos` of k_ptrs_host[l] / v_ptrs_host[l] (device buffers [B, heads, kv_len_stride, 128] fp16, [B, kv_heads, kv_len_stride, 128]
+ * on a grouped_kv = 1 handle -- at this and every other entry that takes the tables; the two tables are HOST
  * arrays of `layers` device pointers, read when the call enqueues) and attends over rows 0 .. pos.  No other cache row is
  * written.  logits_dev: [B, vocab] fp32 (fp16-rounded values, as HF's `.float()` of fp16 logits).  Tests drive this entry
  * teacher-forced. */
@@ -383,7 +410,7 @@ cgpt_status cgpt_llm_step(cgpt_llm_handle h, const int64_t* tokens_dev, int32_t 
  * modified): num_new x select, with num_new - 1 steps between them, all enqueued by this one call.  Select = HF greedy search:
  * the num_eos ids of eos_ids_host (<= 8) read as -inf on the first min_new tokens, first-max arg-max, pad_id for a row that has
  * produced an EOS.  tokens_out_dev: [B, num_new] int64.  step_logits_out_dev (or NULL): [B, num_new, vocab] fp32, the logits each
- * arg-max was taken on (EOS columns at -inf where suppressed). */
+ * arg-max was taken on (EOS columns at -inf where suppressed).  K/V layout as cgpt_llm_step (grouped_kv = 1: kv_heads heads). */
 cgpt_status cgpt_llm_greedy(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len, int32_t num_new,
                             int32_t min_new, const int64_t* eos_ids_host, int32_t num_eos, int64_t pad_id, void* const* k_ptrs_host,
                             void* const* v_ptrs_host, int64_t kv_len_stride, int64_t* tokens_out_dev, float* step_logits_out_dev,
@@ -400,7 +427,7 @@ cgpt_status cgpt_llm_greedy(cgpt_llm_handle h, const float* first_logits_dev, in
 cgpt_status cgpt_llm_prefill_reserve(cgpt_llm_handle h, int32_t max_rows, int32_t max_prompt_len);
 /* The prefill of B prompts of L positions each (no padding, positions 0 .. L-1, causal): embeds_dev is [B, L, hidden] fp16,
  * contiguous.  Layer l writes its rotated keys and its values to rows 0 .. L-1 of k_ptrs_host[l] / v_ptrs_host[l] (layout and
- * tables as cgpt_llm_step; no other cache row is written); logits_dev receives the LAST position's logits, [B, vocab] fp32
+ * tables as cgpt_llm_step, [B, kv_heads, kv_len_stride, 128] on a grouped_kv = 1 handle; no other cache row is written); logits_dev receives the LAST position's logits, [B, vocab] fp32
  * (fp16-rounded values).  Rounding as the step entries, except that the attention probabilities are rounded to fp16 as the
  * matrix-core operand of P.V.  Enqueues only: no host sync, no allocation, no host->device copy -- capturable.
  * CGPT_ERR_STATE while weights are missing or when B x L exceeds the reserved workspace; CGPT_ERR_INVALID for B outside
@@ -422,6 +449,7 @@ cgpt_status cgpt_llm_prefill(cgpt_llm_handle h, const void* embeds_dev, int32_t 
  * replay, so one graph per (B, L) serves every mix of prompt lengths.  All three calls of one decode must see the same contents.
  * Same contracts as the plain entries (enqueue only, capturable, CGPT_ERR_STATE / CGPT_ERR_INVALID rules, all checks before the
  * first launch; the workspace is cgpt_llm_prefill_reserve's, for B x L rows), plus CGPT_ERR_INVALID for a null starts_dev.
+ * K/V layout as the plain entries: [B, heads, kv_len_stride, 128], [B, kv_heads, kv_len_stride, 128] on a grouped_kv = 1 handle.
  * cgpt_llm_greedy_ragged: prompt_len is the PADDED length L; its steps run at buffer positions L, L + 1, ... */
 cgpt_status cgpt_llm_prefill_ragged(cgpt_llm_handle h, const void* embeds_dev, int32_t B, int32_t L, const int32_t* starts_dev,
                                     void* const* k_ptrs_host, void* const* v_ptrs_host, int64_t kv_len_stride, float* logits_dev,
@@ -479,7 +507,8 @@ cgpt_status cgpt_llm_score_reserve(cgpt_llm_handle h, int32_t max_rows, int32_t 
  * with z the fp16 logits widened to fp32 (HF's `logits.float()`), all statistics in fp32: token 0 on first_logits_dev, token j >= 1
  * on the logits of tail row j - 1.  The caller divides (the reference's `.view(B, -1).mean(1)` divides by sequence length - 1).
  * A token id outside 0 .. vocab-1 reads as 0 (the host cannot check device contents without a sync).
- * Reads cache rows 0 .. prompt_len-1 of k_ptrs_host[l] / v_ptrs_host[l] (layout and tables as cgpt_llm_step) and WRITES NO CACHE ROW:
+ * Reads cache rows 0 .. prompt_len-1 of k_ptrs_host[l] / v_ptrs_host[l] (layout and tables as cgpt_llm_step; kv_heads heads on a
+ * grouped_kv = 1 handle) and WRITES NO CACHE ROW:
  * after the call the same cache serves cgpt_llm_greedy or another cgpt_llm_score.  A (row, candidate) result depends on that row's
  * cache and that candidate's tokens only -- not on B, C, the other candidates or their order; fixed summation orders, no atomics.
  * Enqueues only: no host sync, no allocation, no host->device copy (the lengths travel as kernel arguments).

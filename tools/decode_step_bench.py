@@ -33,7 +33,15 @@ logit is 0, the select picks token 1 while EOS is masked (min_length = F generat
     on_f1/on_f3 early stop on, every row finishes at select 1 / 3: 18 / 16 of the 19 steps are dead
     parent      `off` on another build of the library (--parent-lib PATH), as under --ragged
 The order of the legs is rotated from one repetition to the next.  dead_step_ms = the live step minus the saving per skipped step,
-(generate(on_never) - generate(on_fF)) / (19 - F)."""
+(generate(on_never) - generate(on_fF)) / (19 - F).
+
+--gqa runs the grouped-query leg instead (grouped_kv=True), same protocol with the rotated leg order, on a
+Llama-3-8B-shaped random-init decoder (hidden 4096, 32 query / 8 K/V heads, MLP 14336, rope_theta 500000, --gqa-vocab tokens):
+    gqa         decode="hip", prefill="hip", grouped_kv=True: prefill and steps in this library, caches of 8 heads
+    graph       decode="graph" on the same model (PyTorch-ROCm steps replayed from one graph)
+    plain       with --parent-lib: the DEFAULT path (no keyword) on the Vicuna-7B-shaped decoder of the other legs, this build
+    parent      the same on another build of the library (--parent-lib PATH): the claim to check is that the default path is unchanged
+and reports the grouped engine's K/V pool bytes and weight_bytes beside the times."""
 import argparse
 import json
 import os
@@ -56,10 +64,11 @@ class _Rows:
         self.max_batch = n
 
 
-def _decoder(layers, dev):
+def _decoder(layers, dev, kv_heads=32, mlp=11008, vocab=32000, theta=10000.0):
     from transformers import LlamaConfig, LlamaForCausalLM
-    lcfg = LlamaConfig(vocab_size=32000, hidden_size=4096, intermediate_size=11008, num_hidden_layers=layers, num_attention_heads=32,
-                       num_key_value_heads=32, max_position_embeddings=2048, pad_token_id=0, bos_token_id=1, eos_token_id=2)
+    lcfg = LlamaConfig(vocab_size=vocab, hidden_size=4096, intermediate_size=mlp, num_hidden_layers=layers, num_attention_heads=32,
+                       num_key_value_heads=kv_heads, max_position_embeddings=2048, pad_token_id=0, bos_token_id=1, eos_token_id=2,
+                       rope_theta=theta)
     torch.manual_seed(0)
     prev = torch.get_default_dtype()
     torch.set_default_dtype(torch.float16)
@@ -346,6 +355,88 @@ def early_stop_leg(args, llm, embs, tok, lm):
     print(json.dumps(line))
 
 
+def gqa_leg(args, dev):
+    rows, new = args.rows, args.new
+    lm = AnswerLabelMap(4, ())
+    llm = _decoder(args.layers, dev, kv_heads=8, mlp=14336, vocab=args.gqa_vocab, theta=500000.0)
+    g = torch.Generator(device="cpu").manual_seed(1)
+    embs = {"gqa": llm.get_input_embeddings()(torch.randint(3, args.gqa_vocab, (rows, args.prompt), generator=g).to(dev))}
+    embs["graph"] = embs["gqa"]
+    tok = WordHashTokenizer(args.gqa_vocab)
+
+    def build(model, t, n, **kw):
+        return MiniGPT4Classifier(_Rows(rows), model, t, "<ImageHere>", lm, max_new_tokens=n, max_batch=rows, **kw)
+
+    legs = ["gqa", "graph"]
+    clfs = {("gqa", n): build(llm, tok, n, decode="hip", prefill="hip", grouped_kv=True) for n in (new, 1)}
+    clfs.update({("graph", n): build(llm, tok, n, decode="graph") for n in (new, 1)})
+    if args.parent_lib:
+        mha = _decoder(args.layers, dev)
+        g = torch.Generator(device="cpu").manual_seed(1)
+        embs["plain"] = embs["parent"] = mha.get_input_embeddings()(torch.randint(3, 32000, (rows, args.prompt), generator=g).to(dev))
+        tok7 = WordHashTokenizer(32000)
+        clfs.update({("plain", n): build(mha, tok7, n, decode="hip", prefill="hip") for n in (new, 1)})
+        with _other_library(args.parent_lib):
+            clfs.update({("parent", n): build(mha, tok7, n, decode="hip", prefill="hip") for n in (new, 1)})
+        legs += ["plain", "parent"]
+
+    def timed(leg, n):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = clfs[(leg, n)]._generate_graph(embs[leg])
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b), out
+
+    clock_before = _clock()
+    res = {e: {"generate_ms": [], "prefill_ms": []} for e in legs}
+    tokens = {}
+    with torch.no_grad():
+        for rep_i in range(args.warmup + args.reps):                   # interleaved, and the order rotated by one place per repetition
+            k = rep_i % len(legs)
+            for e in legs[k:] + legs[:k]:
+                t, out = timed(e, new)
+                tp = timed(e, 1)[0]
+                print(f"decode_step_bench: repetition {rep_i} {e} generate {t:.1f} ms prefill {tp:.1f} ms", file=sys.stderr, flush=True)
+                if rep_i >= args.warmup:
+                    res[e]["generate_ms"].append(t)
+                    res[e]["prefill_ms"].append(tp)
+                    tokens[e] = out
+    clock_after = _clock()
+    steps = new - 1
+    for r in res.values():
+        r["step_ms"] = [(gm - pm) / steps for gm, pm in zip(r["generate_ms"], r["prefill_ms"])]
+        for k in ("generate_ms", "prefill_ms", "step_ms"):
+            r[k + "_min_max"] = [min(r[k]), max(r[k])]
+
+    def overlap(a, b, k):
+        (a0, a1), (b0, b1) = res[a][k + "_min_max"], res[b][k + "_min_max"]
+        return a0 <= b1 and b0 <= a1
+
+    def med(e, k):
+        return sorted(res[e][k])[len(res[e][k]) // 2]
+
+    keys = ("prefill_ms", "step_ms", "generate_ms")
+    hip = clfs[("gqa", new)]._hip
+    pool = 2 * 2 * rows * args.layers * hip.kv_heads * 128 * (args.prompt + new)
+    layer_bytes = 2 * sum(p.numel() for n, p in llm.named_parameters() if "_proj." in n)
+    kv_mean = 2 * 2 * rows * args.layers * hip.kv_heads * 128 * (args.prompt + (steps + 1) / 2.0)
+    line = {"tool": "decode_step_bench", "leg": "gqa", "rows": rows, "prompt": args.prompt, "new_tokens": new, "layers": args.layers,
+            "heads_kv_heads": [hip.heads, hip.kv_heads], "vocab": args.gqa_vocab, "reps": args.reps, "warmup": args.warmup, "engines": res,
+            "kv_pool_bytes": pool, "kv_pool_bytes_at_32_kv_heads": pool * hip.heads // hip.kv_heads, "weight_bytes": hip.weight_bytes,
+            "gqa_over_graph_median": {k: med("gqa", k) / med("graph", k) for k in keys},
+            "gqa_and_graph_ranges_overlap": {k: overlap("gqa", "graph", k) for k in keys},
+            "gqa_rows_with_graph_tokens": int((tokens["gqa"] == tokens["graph"]).all(dim=1).sum()),
+            "floor_ms_per_step": (layer_bytes + 2 * args.gqa_vocab * 4096 + kv_mean) / COPY_RATE * 1e3, "copy_rate_bytes_per_s": COPY_RATE,
+            "shader_clock_mhz_before_after": [clock_before, clock_after], "device": torch.cuda.get_device_name(0)}
+    if "parent" in res:
+        line["parent_lib"] = os.path.basename(args.parent_lib)
+        line["plain_and_parent_ranges_overlap"] = {k: overlap("plain", "parent", k) for k in keys}
+        line["plain_over_parent_median"] = {k: med("plain", k) / med("parent", k) for k in keys}
+        line["plain_rows_with_parent_tokens"] = int((tokens["plain"] == tokens["parent"]).all(dim=1).sum())
+    print(json.dumps(line))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=200)
@@ -360,11 +451,16 @@ def main():
     ap.add_argument("--ragged-min", type=int, default=38)
     ap.add_argument("--int8", action="store_true", help="the weight-format leg (see the module docstring)")
     ap.add_argument("--early-stop", action="store_true", help="the early-stop leg (see the module docstring)")
-    ap.add_argument("--parent-lib", default=None, help="another build of libcgpt.so for the plain-path A/B of --ragged / --int8 / --early-stop")
+    ap.add_argument("--gqa", action="store_true", help="the grouped-query leg (see the module docstring)")
+    ap.add_argument("--gqa-vocab", type=int, default=128256)
+    ap.add_argument("--parent-lib", default=None,
+                    help="another build of libcgpt.so for the plain-path A/B of --ragged / --int8 / --early-stop / --gqa")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "this benchmark measures device time: it needs the GPU"
     assert 1 <= args.rows <= 256 and args.new >= 2 and args.prompt >= 1
     dev = "cuda:0"
+    if args.gqa:
+        return gqa_leg(args, dev)
     engines = args.engines.split(",")
     llm = _decoder(args.layers, dev)
     g = torch.Generator(device="cpu").manual_seed(1)
