@@ -48,6 +48,14 @@ class LlmConfigGqa(C.Structure):
     _fields_ = [("base", LlmConfig), ("grouped_kv", C.c_int32), ("reserved", C.c_int32)]
 
 
+class LlmConfigAct(C.Structure):
+    """struct cgpt_llm_config_act (include/cgpt.h): cgpt_llm_config_gqa followed by the activation format.  gqa.base.struct_size =
+    sizeof(this); cgpt_llm_create takes a pointer to `gqa.base`."""
+    _fields_ = [("gqa", LlmConfigGqa), ("act_format", C.c_int32), ("act_threshold", C.c_float), ("outlier_cap", C.c_int32),
+                ("reserved2", C.c_int32)]
+
+
+LLM_ACT_FORMATS = {"fp16": 0, "int8": 1}      # CGPT_LLM_A_F16, CGPT_LLM_A_INT8
 LLM_WEIGHT_FORMATS = {"fp16": 0, "int8": 1}   # CGPT_LLM_W_F16, CGPT_LLM_W_INT8
 # sizeof(cgpt_llm_config) before weight_format existed: still accepted by cgpt_llm_create (fp16), and what older builds expect
 LLM_CONFIG_SIZE_F16 = LlmConfig.weight_format.offset
@@ -114,6 +122,10 @@ SIGNATURES = {
     "cgpt_llm_set_early_stop": (_I32, [_P, _I32]),
     "cgpt_llm_live_steps": (_I32, [_P, C.POINTER(_I32), _P]),
     "cgpt_llm_score_reserve": (_I32, [_P, _I32, _I32]),
+    "cgpt_llm_act_stats": (_I32, [_P, C.POINTER(_I64)]),
+    "cgpt_llm_linear_i8": (_I32, [_P, _P, _P, _I64, _I64, _I64, _F, _I32, _I32, _P, _P, _I64, _P, _I64, _P]),
+    "cgpt_llm_linear_i8_workspace": (_I64, [_I64, _I64, _I64, _I32, C.POINTER(_I64)]),
+    "cgpt_llm_linear_i8_slices": (_I32, [_I64, _I64]),
     "cgpt_llm_score": (_I32, [_P, _P, _I32, _I32, _P, _P, _I32, _I32, _F, _P, _P, _I64, _P, _P]),
 }
 

@@ -19,7 +19,9 @@ Config (a plain dict or any mapping; the reference's YAMLs define no smoothing k
             #          one captured graph per bucket), early_stop: false | true (with decode "hip": the native token steps do no work
             #          once every row of a batch has produced its EOS; same answers), grouped_kv: false | true (with decode "hip": the
             #          native engine takes a grouped-query decoder, heads / kv_heads in {1, 2, 4, 8}, e.g. Llama-3-8B; K/V buffers
-            #          shrink by that ratio) -- see build_generating_classifier
+            #          shrink by that ratio), activations: "fp16" | "int8" (with decode "hip", prefill "hip" and weights "int8": int8
+            #          activations with a per-row outlier split, the LLM.int8() forward; int8_threshold: 6.0, outlier_cap: 64)
+            #          -- see build_generating_classifier
             #          also: classify: "generate" | "multi_select" (rank the answers by their teacher-forced loss instead of generating:
             #          every noisy copy votes for one of `answers`, never for "other"), score: "hf" | "hip" (who computes those losses;
             #          "hip" needs decode and prefill "hip"), end_sym: "\\n" (appended to every answer; the reference's VQA configs: "###")
@@ -200,7 +202,9 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
                   layer linears as row-wise absmax int8, the weight law of the reference's low_resource: true; needs decode and
                   prefill "hip"); early_stop: False | True (the native token steps stop working once every row of a batch has its
                   EOS, same answers; needs decode "hip"); grouped_kv: False | True (grouped-query attention on the native engine, for decoders
-                  with fewer K/V heads than query heads; needs decode "hip"); classify: "generate" | "multi_select" (the base classifier ranks `answers` by their answer loss,
+                  with fewer K/V heads than query heads; needs decode "hip"); activations: "fp16" | "int8" (the LLM.int8() forward: int8
+                  activations with a per-row outlier split at int8_threshold (6.0), at most outlier_cap (64) outliers per row; needs
+                  decode and prefill "hip" and weights "int8"); classify: "generate" | "multi_select" (the base classifier ranks `answers` by their answer loss,
                   MiniGPTBase.multi_select, instead of generating), score: "hf" | "hip" (the model's own forward per candidate | one
                   native prefill + the native scoring pass; needs decode and prefill "hip"), end_sym: "\\n" (appended to every answer)"""
     from ..minigpt4 import MiniGPT4Classifier
@@ -234,7 +238,8 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
                               prompt_bucket=gen_cfg.get("prompt_bucket"), weights=gen_cfg.get("weights", "fp16"),
                               early_stop=gen_cfg.get("early_stop", False), grouped_kv=gen_cfg.get("grouped_kv", False),
                               classify=gen_cfg.get("classify", "generate"), score=gen_cfg.get("score", "hf"),
-                              end_sym=gen_cfg.get("end_sym", "\n"))
+                              end_sym=gen_cfg.get("end_sym", "\n"), activations=gen_cfg.get("activations", "fp16"),
+                              int8_threshold=gen_cfg.get("int8_threshold", 6.0), outlier_cap=gen_cfg.get("outlier_cap", 64))
 
 
 def build_classifier(model_cfg, num_classes, max_batch, device_index, tokenizer=None, llama_model=None):

@@ -39,6 +39,33 @@ hipError_t decode_gemm_prepare();
 hipError_t launch_decode_gemm(int epilogue, const DecodeGemmParams& p, hipStream_t stream, const half_t* wscale = nullptr,
                               const int* live = nullptr);
 
+// ------------------------------------------------------------------------------------- int8-activation linear (llm_gemm_i8.hip)
+// The W8A8 linear with a per-row outlier split (the law is written out at the top of llm_gemm_i8.hip).  Two launches
+// per linear: the quantiser turns fp16 rows into int8 codes, one fp32 scale per row and the row's outlier list; the GEMM multiplies the
+// codes with the int8 weight rows on the int8 MFMA into int32 and applies scales, outlier term and epilogue.  Integer accumulation is
+// exact, so a result does not depend on M, the row tile, the K split or the launch.
+//   x [rows, K] fp16 (rows K apart) -> a8 [rows, K] int8, sa [rows] fp32, lists [rows][cap + 1] uint32: word 0 = entries kept
+//   (<= cap), word 1 + i = k | fp16 bits << 16 in ascending k.  counters[4]: rows, outliers, max outliers of a row, rows with more
+//   than `cap` outliers (those keep their first `cap`; their result is finite but not the law's).  K % 128 == 0, K <= 65536, cap 1..1024.
+hipError_t launch_act_quant(const half_t* x, int64_t rows, int K, float threshold, int cap, signed char* a8, float* sa, uint32_t* lists,
+                            unsigned long long* counters, hipStream_t stream, const int* live = nullptr);
+struct I8GemmParams {
+    const signed char* A; int64_t lda;      // int8 codes, readable for round_up(M, 256) rows
+    const float* sa;                        // [M]
+    const uint32_t* lists; int cap;         // [M][cap + 1]
+    const signed char* W; int64_t ldw;      // q [N, K]
+    const half_t* wscale;                   // [N]
+    half_t* out; int64_t ldo;
+    const half_t* resid; int64_t ldr;       // DEC_F16_RESID (may alias out)
+    int* slabs;                             // [splitk][256][N] int32 workspace (used when there is one row tile and splitk > 1)
+    int M, N, K;
+};
+int i8_gemm_splitk(int N, int K);                           // slices a one-row-tile call of this shape runs with (more row tiles: 1)
+size_t i8_gemm_slab_bytes(int N, int K);
+hipError_t i8_gemm_prepare();                               // dynamic-LDS limit on the CURRENT device, outside any capture
+// DEC_F16, DEC_F16_RESID or DEC_SWIGLU; N % 64 == 0, K % 128 == 0; any M >= 1 (256-row tiles on the grid's second dimension).
+hipError_t launch_i8_gemm(int epilogue, const I8GemmParams& p, hipStream_t stream, const int* live = nullptr);
+
 // ------------------------------------------------------------------------------------- prefill (llm_prefill.hip)
 // Token row r = b * L + p of B prompts of L positions.  All fp16, rows `hidden` (or 3 hidden / 2 mlp / mlp) elements apart.
 // kv_heads (rope, attention, scoring attention): == heads is the plain layout and the plain kernel instantiations; a divisor of heads

@@ -18,6 +18,10 @@
 // instantiation of the decode GEMM; the prefill expands each matrix into ONE fp16 scratch matrix right before its GEMM
 // (llm_dequant_kernel, same stream).  Both form W' = fp16(q) * s with one fp16 multiply, so every result is bit for bit that of
 // an fp16 handle loaded with W'.
+//
+// Activations-int8 handles (cgpt_llm_config_act.act_format = 1): on top of the int8 weights, every layer linear of
+// the token step, the prefill and the scoring pass is quantise (llm_act_quant_kernel) + int8 GEMM (llm_gemm_i8.hip), in gemm() and
+// big_gemm() below -- the only two call sites.  lm_head stays on the fp16 kernels.  Such a handle has no fp16 scratch.
 #include <math.h>
 #include <stddef.h>
 #include <string.h>
@@ -515,6 +519,9 @@ __global__ __launch_bounds__(256) void llm_live_kernel(const int* __restrict__ u
 // The config a handle keeps: the caller's cgpt_llm_config and the switches of cgpt_llm_config_gqa (0 for a plain config).
 struct LlmCfg : cgpt_llm_config {
     int32_t grouped_kv = 0;
+    int32_t act_format = 0;                // cgpt_llm_config_act: 1 = int8 activations with the outlier split
+    float act_threshold = 6.0f;
+    int32_t outlier_cap = 64;
 };
 
 // One fused layer matrix [up256(N)][K]: fp16 (`w`) on an fp16 handle; int8 `q` with one fp16 scale per row (`s`) on an int8 handle.
@@ -553,6 +560,12 @@ struct cgpt_llm {
     // int8 handles: the prefill's ONE fp16 expansion of the layer matrix its next GEMM reads (stream order makes one enough)
     half_t* scratch = nullptr;
     int64_t weight_bytes = 0;              // matrices, scales and scratch, as allocated (cgpt_llm_weight_bytes)
+    // activations-int8 handles: codes, row scales and outlier lists of the rows the next int8 GEMM reads -- 256 rows for the token step,
+    // `p_rows` for the prefill / scoring workspace (one set each: stream order makes one enough) -- and the four statistics counters
+    signed char *a8 = nullptr, *p_a8 = nullptr;
+    float *sa = nullptr, *p_sa = nullptr;
+    uint32_t *lists = nullptr, *p_lists = nullptr;
+    unsigned long long* act_counters = nullptr;
     // scoring workspace (cgpt_llm_score_reserve) beside the prefill workspace, which holds the tail rows: fp16 logits of `s_rows`
     // tail rows (a multiple of 256; more rows run in chunks) and `s_ce` per-token cross-entropies.  Replaced buffers stay in `allocs`.
     int64_t s_rows = 0, s_ce = 0;
@@ -593,6 +606,15 @@ cgpt_status check_cache(cgpt_llm* m, const char* who, int B, int last_pos, void*
 
 cgpt_status gemm(cgpt_llm* m, int epi, const half_t* A, int K, const Mat& W, int N, void* out, int64_t ldo, const half_t* resid,
                  int B, hipStream_t st, const int* live = nullptr) {
+    if (m->cfg.act_format && W.q) {                        // a layer linear of an activations-int8 handle: quantise the rows, int8 GEMM
+        HIPCHK(launch_act_quant(A, B, K, m->cfg.act_threshold, m->cfg.outlier_cap, m->a8, m->sa, m->lists, m->act_counters, st, live));
+        I8GemmParams q{};
+        q.A = m->a8; q.lda = K; q.sa = m->sa; q.lists = m->lists; q.cap = m->cfg.outlier_cap; q.W = W.q; q.ldw = K; q.wscale = W.s;
+        q.out = (half_t*)out; q.ldo = ldo; q.resid = resid; q.ldr = ldo; q.slabs = reinterpret_cast<int*>(m->slabs);
+        q.M = B; q.N = N; q.K = K;
+        HIPCHK(launch_i8_gemm(epi, q, st, live));
+        return CGPT_OK;
+    }
     DecodeGemmParams p{};
     p.A = A; p.lda = K; p.W = W.q ? reinterpret_cast<const half_t*>(W.q) : W.w; p.ldw = K; p.out = out; p.ldo = ldo; p.resid = resid;
     p.ldr = ldo; p.slabs = m->slabs;
@@ -649,6 +671,15 @@ cgpt_status run_step(cgpt_llm* m, const long long* tokens, int B, int pos, const
 // the expansion of the next matrix is ordered behind this GEMM, so one scratch serves every layer.
 cgpt_status big_gemm(cgpt_llm* m, const half_t* A, int K, const Mat& Wm, int N, half_t* out, int64_t M, hipStream_t st) {
     const half_t* W = Wm.w;
+    if (m->cfg.act_format && Wm.q) {                       // activations-int8 handle: the token step's two launches on M rows (row tiles
+        HIPCHK(launch_act_quant(A, M, K, m->cfg.act_threshold, m->cfg.outlier_cap, m->p_a8, m->p_sa, m->p_lists, m->act_counters, st));
+        I8GemmParams q{};                                  // on the grid's second dimension); no expansion, no scratch
+        q.A = m->p_a8; q.lda = K; q.sa = m->p_sa; q.lists = m->p_lists; q.cap = m->cfg.outlier_cap; q.W = Wm.q; q.ldw = K; q.wscale = Wm.s;
+        q.out = out; q.ldo = N; q.resid = nullptr; q.ldr = 0; q.slabs = reinterpret_cast<int*>(m->slabs);
+        q.M = (int)M; q.N = N; q.K = K;
+        HIPCHK(launch_i8_gemm(DEC_F16, q, st));
+        return CGPT_OK;
+    }
     if (Wm.q) {
         const int64_t chunks = (int64_t)((N + 255) / 256 * 256) * (K / 16);
         hipLaunchKernelGGL(llm_dequant_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st, Wm.q, Wm.s, K, chunks, m->scratch);
@@ -742,20 +773,46 @@ cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
     // cgpt_llm_config_gqa (the struct is then the `base` of one, and the switches behind it are read)
     constexpr int32_t kOldSize = (int32_t)offsetof(cgpt_llm_config, weight_format);
     constexpr int32_t kGqaSize = (int32_t)sizeof(cgpt_llm_config_gqa);
+    constexpr int32_t kActSize = (int32_t)sizeof(cgpt_llm_config_act);
+    static_assert(offsetof(cgpt_llm_config_act, act_format) == sizeof(cgpt_llm_config_gqa) && sizeof(cgpt_llm_config_act) % 8 == 0,
+                  "the activation fields follow the gqa struct without padding");
     static_assert(offsetof(cgpt_llm_config_gqa, grouped_kv) == sizeof(cgpt_llm_config), "the switches follow the base without padding");
-    if (cfg->struct_size != (int32_t)sizeof(cgpt_llm_config) && cfg->struct_size != kGqaSize && cfg->struct_size != kOldSize)
+    if (cfg->struct_size != (int32_t)sizeof(cgpt_llm_config) && cfg->struct_size != kGqaSize && cfg->struct_size != kOldSize &&
+        cfg->struct_size != kActSize)
         return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: cgpt_llm_config.struct_size mismatch (header/library drift)");
     LlmCfg c{};
     memcpy(static_cast<cgpt_llm_config*>(&c), cfg, std::min((size_t)cfg->struct_size, sizeof(cgpt_llm_config)));
     if (cfg->struct_size == kOldSize) c.weight_format = CGPT_LLM_W_F16;
-    if (cfg->struct_size == kGqaSize) {
+    if (cfg->struct_size == kGqaSize || cfg->struct_size == kActSize) {
         const cgpt_llm_config_gqa* ext = reinterpret_cast<const cgpt_llm_config_gqa*>(cfg);
         if (ext->reserved != 0) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: cgpt_llm_config_gqa.reserved must be 0");
         c.grouped_kv = ext->grouped_kv;
     }
+    c.act_format = 0;
+    if (cfg->struct_size == kActSize) {
+        const cgpt_llm_config_act* act = reinterpret_cast<const cgpt_llm_config_act*>(cfg);
+        if (act->reserved2 != 0) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: cgpt_llm_config_act.reserved2 must be 0");
+        if (act->act_format != CGPT_LLM_A_F16 && act->act_format != CGPT_LLM_A_INT8)
+            return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: act_format must be CGPT_LLM_A_F16 (0) or CGPT_LLM_A_INT8 (1)");
+        c.act_format = act->act_format;
+        if (c.act_format) {
+            c.act_threshold = act->act_threshold;
+            c.outlier_cap = act->outlier_cap;
+        }
+    }
     c.struct_size = (int32_t)sizeof(cgpt_llm_config);
     if (c.weight_format != CGPT_LLM_W_F16 && c.weight_format != CGPT_LLM_W_INT8)
         return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: weight_format must be CGPT_LLM_W_F16 (0) or CGPT_LLM_W_INT8 (1)");
+    if (c.act_format) {
+        if (c.weight_format != CGPT_LLM_W_INT8)
+            return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: act_format = CGPT_LLM_A_INT8 needs weight_format = CGPT_LLM_W_INT8 (int8 "
+                                               "activations multiply int8 weights)");
+        if (!(fabsf(c.act_threshold) <= 3.0e38f)) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: act_threshold must be finite");
+        if (c.outlier_cap < 1 || c.outlier_cap > 1024) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: outlier_cap must be 1..1024");
+        if (c.hidden % 128 || c.mlp % 128 || c.mlp > 65536)
+            return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: act_format = CGPT_LLM_A_INT8 needs hidden and mlp multiples of 128 (one "
+                                               "K-tile of the int8 kernel is 128 bytes) and mlp <= 65536");
+    }
     if (c.head_dim != HD) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: head_dim must be 128");
     if (c.grouped_kv != 0 && c.grouped_kv != 1) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: grouped_kv must be 0 or 1");
     if (c.heads < 1 || (!c.grouped_kv && c.kv_heads != c.heads))
@@ -785,6 +842,7 @@ cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
     HIPCHK(hipSetDevice(c.device));
     HIPCHK(decode_gemm_prepare());                        // kernel attributes now: nothing but launches is left for a captured stream
     HIPCHK(score_prepare());
+    if (c.act_format) HIPCHK(i8_gemm_prepare());
     if (c.grouped_kv) {                                   // the grouped step attention's dynamic LDS, for this handle's longest row
         switch (c.heads / c.kv_heads) {
             case 1: HIPCHK(gqa_attn_prepare<1>(c.max_len)); break;
@@ -822,7 +880,7 @@ cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
         za(H * hs, &L.ln1);
         za(H * hs, &L.ln2);
     }
-    if (int8)                                             // the largest fused layer matrix, up256(2 mlp) x hidden at LLaMA's shapes
+    if (int8 && !c.act_format)                            // the largest fused layer matrix, up256(2 mlp) x hidden at LLaMA's shapes
         counted(std::max(std::max(up256(NQ) * H, up256(2 * F) * H), up256(H) * std::max(H, F)) * hs, &m->scratch);
     // activations: whole 256-row tiles (the GEMM stages every row of its tile; rows past the batch hold zeros)
     za(MAX_ROWS * H * hs, &m->h);
@@ -838,6 +896,13 @@ cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
     size_t slab = 0;
     const int shapes[5][2] = {{(int)NQ, (int)H}, {(int)H, (int)H}, {(int)(2 * F), (int)H}, {(int)H, (int)F}, {(int)V, (int)H}};
     for (auto& sh : shapes) slab = std::max(slab, decode_gemm_slab_bytes(sh[0], sh[1]));
+    if (c.act_format) {                                   // the int32 slabs of the int8 GEMM share the buffer; codes, scales, lists
+        for (int i = 0; i < 4; ++i) slab = std::max(slab, i8_gemm_slab_bytes(shapes[i][0], shapes[i][1]));
+        za(MAX_ROWS * std::max(H, F), &m->a8);
+        za(MAX_ROWS * sizeof(float), &m->sa);
+        za(MAX_ROWS * (size_t)(c.outlier_cap + 1) * sizeof(uint32_t), &m->lists);
+        za(4 * sizeof(unsigned long long), &m->act_counters);
+    }
     za(std::max(slab, (size_t)16), &m->slabs);
     za((size_t)c.max_len * HD * hs, &m->rope);
     float* inv_freq = nullptr;
@@ -866,6 +931,76 @@ cgpt_status cgpt_llm_destroy(cgpt_llm_handle h) {
 cgpt_status cgpt_llm_weight_bytes(cgpt_llm_handle h, int64_t* out) {
     if (!h || !out) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_weight_bytes: null argument");
     *out = h->weight_bytes;
+    return CGPT_OK;
+}
+
+cgpt_status cgpt_llm_act_stats(cgpt_llm_handle h, int64_t* out_host) {
+    if (!h || !out_host) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_act_stats: null argument");
+    for (int i = 0; i < 4; ++i) out_host[i] = 0;
+    if (!h->cfg.act_format) return CGPT_OK;
+    HIPCHK(hipSetDevice(h->cfg.device));
+    HIPCHK(hipDeviceSynchronize());
+    unsigned long long v[4];
+    HIPCHK(hipMemcpy(v, h->act_counters, sizeof(v), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemset(h->act_counters, 0, sizeof(v)));
+    for (int i = 0; i < 4; ++i) out_host[i] = (int64_t)v[i];
+    return CGPT_OK;
+}
+
+int32_t cgpt_llm_linear_i8_slices(int64_t N, int64_t K) {
+    if (N < 64 || N % 64 || N > (1 << 24) || K < 128 || K % 128 || K > 65536) return -1;
+    return i8_gemm_splitk((int)N, (int)K);
+}
+
+int64_t cgpt_llm_linear_i8_workspace(int64_t M, int64_t N, int64_t K, int32_t outlier_cap, int64_t* offsets_out) {
+    if (M < 1 || M > (1 << 24) || outlier_cap < 1 || outlier_cap > 1024 || cgpt_llm_linear_i8_slices(N, K) < 0) return -1;
+    const int64_t rows = (M + 255) / 256 * 256;
+    auto up = [](int64_t b) { return (b + 255) / 256 * 256; };
+    int64_t off[5];
+    off[0] = 0;
+    off[1] = 256;
+    off[2] = off[1] + up(rows * K);
+    off[3] = off[2] + up(rows * 4);
+    off[4] = off[3] + up(rows * (int64_t)(outlier_cap + 1) * 4);
+    const int64_t total = off[4] + up(M <= 256 ? (int64_t)i8_gemm_slab_bytes((int)N, (int)K) : 0);
+    if (offsets_out)
+        for (int i = 0; i < 5; ++i) offsets_out[i] = off[i];
+    return total;
+}
+
+cgpt_status cgpt_llm_linear_i8(const void* A_dev, const void* q_dev, const void* sw_dev, int64_t M, int64_t N, int64_t K, float threshold,
+                               int32_t outlier_cap, int32_t epilogue, const void* resid_dev, void* out_dev, int64_t out_bytes,
+                               void* workspace_dev, int64_t workspace_bytes, void* stream) {
+    if (!A_dev || !q_dev || !sw_dev || !out_dev || !workspace_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_linear_i8: null argument");
+    int64_t off[5];
+    const int64_t need = cgpt_llm_linear_i8_workspace(M, N, K, outlier_cap, off);
+    if (need < 0)
+        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_linear_i8: bad sizes (1 <= M <= 2^24, N a multiple of 64, K a multiple of 128 up to "
+                                           "65536, outlier_cap 1..1024)");
+    if (epilogue != DEC_F16 && epilogue != DEC_F16_RESID && epilogue != DEC_SWIGLU)
+        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_linear_i8: epilogue must be 0 (fp16), 1 (fp16 + resid) or 2 (SwiGLU)");
+    if (epilogue == DEC_F16_RESID && !resid_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_linear_i8: epilogue 1 needs resid_dev");
+    if (!(fabsf(threshold) <= 3.0e38f)) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_linear_i8: threshold must be finite");
+    const int64_t ncols = epilogue == DEC_SWIGLU ? N / 2 : N;
+    if (out_bytes < M * ncols * (int64_t)sizeof(half_t))
+        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_linear_i8: out_bytes " + std::to_string(out_bytes) + " < " +
+                                               std::to_string(M * ncols * (int64_t)sizeof(half_t)) + " the result needs");
+    if (workspace_bytes < need)
+        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_linear_i8: workspace_bytes " + std::to_string(workspace_bytes) + " < " +
+                                               std::to_string(need) + " (cgpt_llm_linear_i8_workspace)");
+    if ((uintptr_t)workspace_dev % 256) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_linear_i8: workspace_dev must be 256-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace_dev;
+    HIPCHK(i8_gemm_prepare());
+    HIPCHK(hipMemsetAsync(ws + off[0], 0, 4 * sizeof(unsigned long long), st));
+    HIPCHK(launch_act_quant((const half_t*)A_dev, M, (int)K, threshold, outlier_cap, (signed char*)(ws + off[1]), (float*)(ws + off[2]),
+                            (uint32_t*)(ws + off[3]), (unsigned long long*)(ws + off[0]), st));
+    I8GemmParams p{};
+    p.A = (const signed char*)(ws + off[1]); p.lda = K; p.sa = (const float*)(ws + off[2]); p.lists = (const uint32_t*)(ws + off[3]);
+    p.cap = outlier_cap; p.W = (const signed char*)q_dev; p.ldw = K; p.wscale = (const half_t*)sw_dev; p.out = (half_t*)out_dev; p.ldo = ncols;
+    p.resid = (const half_t*)resid_dev; p.ldr = ncols; p.slabs = (int*)(ws + off[4]);
+    p.M = (int)M; p.N = (int)N; p.K = (int)K;
+    HIPCHK(launch_i8_gemm(epilogue, p, st));
     return CGPT_OK;
 }
 
@@ -1051,15 +1186,28 @@ static cgpt_status grow_workspace(cgpt_llm_handle h, int64_t rows, const std::st
         e = hipMalloc((void**)&fresh[i], (size_t)rows * cols[i] * hs);
         if (e == hipSuccess) e = hipMemset(fresh[i], 0, (size_t)rows * cols[i] * hs);
     }
+    // activations-int8 handles: codes, row scales and outlier lists for the same rows
+    void* fresh8[3] = {nullptr, nullptr, nullptr};
+    const size_t bytes8[3] = {(size_t)rows * std::max(H, F), (size_t)rows * sizeof(float),
+                              (size_t)rows * (size_t)(h->cfg.outlier_cap + 1) * sizeof(uint32_t)};
+    for (int i = 0; i < 3 && e == hipSuccess && h->cfg.act_format; ++i) {
+        e = hipMalloc(&fresh8[i], bytes8[i]);
+        if (e == hipSuccess) e = hipMemset(fresh8[i], 0, bytes8[i]);
+    }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         for (half_t* p : fresh) (void)hipFree(p);
+        for (void* p : fresh8) (void)hipFree(p);
         return cgpt_fail(CGPT_ERR_HIP, who + ": workspace allocation failed -> " + hipGetErrorString(e));
     }
     half_t** bufs[7] = {&h->p_h, &h->p_xn, &h->p_qkv, &h->p_attn, &h->p_proj, &h->p_gu, &h->p_act};
     for (int i = 0; i < 7; ++i) {
         *bufs[i] = fresh[i];
         h->allocs.push_back(fresh[i]);
+    }
+    if (h->cfg.act_format) {
+        h->p_a8 = (signed char*)fresh8[0]; h->p_sa = (float*)fresh8[1]; h->p_lists = (uint32_t*)fresh8[2];
+        for (void* p : fresh8) h->allocs.push_back(p);
     }
     h->p_rows = rows;
     return CGPT_OK;

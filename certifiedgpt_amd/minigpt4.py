@@ -186,6 +186,93 @@ def int8_state_dict(llama_model, device=None):
     return out
 
 
+# ---- the activation law of activations="int8" (csrc/llm_gemm_i8.hip; include/cgpt.h: cgpt_llm_config_act), in plain torch: the oracle
+def quantize_act_rows_int8(x, threshold=6.0):
+    """Row-wise int8 codes of fp16 activations x [M, K] with a per-row outlier split -> (a int8 [M, K], s_a fp32 [M], outlier bool [M, K]):
+        outlier_mk = threshold > 0 and |x_mk| >= threshold
+        s_a[m]     = max over the row's non-outliers |x_mk| / 127        fp32 division; kept in fp32
+        a_mk       = clamp(rint(fp32(x_mk) / s_a[m]), -127, 127)          round to nearest even; 0 for outliers; the row 0 where s_a = 0
+    Every row is a function of that row alone.  Works on CPU tensors."""
+    if x.dtype != torch.float16 or x.dim() != 2:
+        raise ValueError(f"quantize_act_rows_int8: expected an fp16 matrix [M, K], got {x.dtype} {tuple(x.shape)}")
+    xf = x.float()
+    t = float(threshold)
+    out = (xf.abs() >= t) if t > 0 else torch.zeros_like(xf, dtype=torch.bool)
+    amax = torch.where(out, torch.zeros_like(xf), xf.abs()).amax(dim=1)
+    s = amax / torch.full_like(amax, 127.0)                            # tensor / tensor: a true division on every device
+    sf = s[:, None]
+    live = (sf != 0) & ~out
+    a = torch.round(xf / torch.where(sf != 0, sf, torch.ones_like(sf))).clamp_(-127, 127)
+    return torch.where(live, a, torch.zeros_like(a)).to(torch.int8), s, out
+
+
+def llm_int8_linear(x, q, s_w, threshold=6.0):
+    """The linear of an activations-int8 handle on fp16 rows x [M, K] against int8 weights q [N, K] with fp16 row scales s_w [N]
+    (`quantize_rows_int8`) -> v fp32 [M, N], before the epilogue's rounding:
+        acc = a . q^T in integers (exact);   y = fp32(acc) * (s_a * fp32(s_w));
+        o   = sum over the row's outliers in ascending k of fp32(x_k) * fp32(W'_nk), sequential fp32 from 0, W' = fp16(q) * s_w;
+        v   = y + o.
+    Plain torch on the tensors' device; the integer product runs in int64 on the CPU and in fp64 elsewhere (|acc| < 2^31: exact)."""
+    if q.dtype != torch.int8 or s_w.dtype != torch.float16 or q.dim() != 2 or tuple(s_w.shape) != (q.shape[0],) or x.shape[-1] != q.shape[1]:
+        raise ValueError("llm_int8_linear: expected x fp16 [M, K], q int8 [N, K] and s_w fp16 [N]")
+    a, s_a, out = quantize_act_rows_int8(x, threshold)
+    if x.is_cuda:
+        acc = (a.double() @ q.double().t()).to(torch.int32)
+    else:
+        acc = (a.long() @ q.long().t()).to(torch.int32)
+    y = acc.to(torch.float32) * (s_a[:, None] * s_w.float()[None, :])
+    o = torch.zeros_like(y)
+    cnt = out.sum(dim=1)
+    most = int(cnt.max()) if out.numel() else 0
+    if most:
+        wp = dequantize_rows_int8(q, s_w).float()                      # [N, K]
+        xf = x.float()
+        # the j-th outlier of every row at once: a stable sort lists a row's outlier positions first, in ascending k
+        order = torch.sort(out.to(torch.uint8), dim=1, descending=True, stable=True).indices[:, :most]
+        for j in range(most):                                          # sequential fp32, ascending k; every product is exact in fp32
+            kj = order[:, j]
+            term = xf.gather(1, kj[:, None]) * wp[:, kj].t()
+            o = torch.where((cnt > j)[:, None], o + term, o)
+    return y + o
+
+
+class _ActInt8Linear(torch.nn.Module):
+    """A bias-free linear evaluated by the activation law: input cast to fp16, `llm_int8_linear`, fp16 of v, in the input's dtype."""
+
+    def __init__(self, weight, threshold):
+        super().__init__()
+        q, s = quantize_rows_int8(weight.detach().to(torch.float16).cpu())      # the weight law's reference evaluation (as int8_state_dict's)
+        self.register_buffer("q", q.to(weight.device), persistent=False)
+        self.register_buffer("s_w", s.to(weight.device), persistent=False)
+        self.weight = weight                                            # the parameter stays: the state dict is unchanged
+        self.threshold = float(threshold)
+        self.in_features, self.out_features, self.bias = weight.shape[1], weight.shape[0], None
+
+    def forward(self, x):
+        x2 = x.reshape(-1, x.shape[-1]).to(torch.float16)
+        v = llm_int8_linear(x2, self.q, self.s_w, self.threshold).to(torch.float16)
+        return v.to(x.dtype).reshape(*x.shape[:-1], self.out_features)
+
+
+def act_int8_twin(llama_model, threshold=6.0):
+    """A copy of an HF `LlamaForCausalLM` whose seven linears per layer evaluate the law of activations="int8" (`llm_int8_linear` on
+    `quantize_rows_int8` of the fp16 weight, fp16 of the result): the oracle of the mode, in the role `int8_state_dict` and
+    `expand_kv_state_dict` have.  Everything else (embed_tokens, lm_head, the norms, attention, every rounding of the model's dtype) is
+    the copy's own, so an fp32 copy is the reference point and an fp16 copy is HF's fp16 evaluation of the same law.  The state dict
+    is that of `llama_model`.  Works on CPU and GPU."""
+    import copy
+    twin = copy.deepcopy(llama_model)
+    for layer in twin.model.layers:
+        for name in LAYER_LINEARS:
+            parent_name, attr = name.split(".")
+            parent = getattr(layer, parent_name)
+            lin = getattr(parent, attr)
+            if lin.bias is not None:
+                raise ValueError(f"act_int8_twin: {name} carries a bias (bias-free linears required)")
+            setattr(parent, attr, _ActInt8Linear(lin.weight, threshold))
+    return twin.eval()
+
+
 GQA_RATIOS = (1, 2, 4, 8)                                              # heads / kv_heads the grouped kernels are instantiated for
 
 
@@ -278,14 +365,16 @@ class _LinearRoute:
         return ctx()
 
 
-def hip_decode_unsupported(llama_model, max_batch=None, grouped_kv=False):
+def hip_decode_unsupported(llama_model, max_batch=None, grouped_kv=False, activations="fp16"):
     """Every property of `llama_model` (and of the classifier batch) that keeps it off the native token step (`decode="hip"`,
     csrc/llm.hip), as a list of sentences; empty = supported.  The step kernels are written for HF `LlamaForCausalLM` in fp16 on
     a HIP device: bias-free linears, RMSNorm, `rotate_half` rotary with the default (unscaled) rope_theta law, as many K/V heads
     as query heads, head size 128, SwiGLU, no sliding window -- Vicuna-7B / 13B.  ALL failing properties are collected, so one
     message names them all.
     grouped_kv=True (the engine's grouped-query mode): fewer K/V heads than query heads are accepted when they
-    divide them and heads / kv_heads is 1, 2, 4 or 8 -- Llama-3-8B (32 / 8), Llama-2-70B's shape (64 / 8)."""
+    divide them and heads / kv_heads is 1, 2, 4 or 8 -- Llama-3-8B (32 / 8), Llama-2-70B's shape (64 / 8).
+    activations="int8" (DESIGN.md 4.4.7): hidden_size and intermediate_size must be multiples of 128, because one K-tile of the int8
+    kernel is 128 bytes -- 7B, 13B, Llama-3-8B and 70B all are."""
     cfg = getattr(llama_model, "config", None)
     bad = []
     if type(llama_model).__name__ != "LlamaForCausalLM" or cfg is None:
@@ -321,6 +410,10 @@ def hip_decode_unsupported(llama_model, max_batch=None, grouped_kv=False):
     for name, val in (("hidden_size", hidden), ("intermediate_size", int(cfg.intermediate_size)), ("vocab_size", int(cfg.vocab_size))):
         if val % 64:
             bad.append(f"shape: {name} {val} is not a multiple of 64")
+    if activations == "int8":
+        for name, val in (("hidden_size", hidden), ("intermediate_size", int(cfg.intermediate_size))):
+            if val % 128:
+                bad.append(f'shape: {name} {val} is not a multiple of 128 (activations="int8": one K-tile of the int8 kernel is 128 bytes)')
     if max_batch is not None and int(max_batch) > 256:
         bad.append(f"batch: max_batch {int(max_batch)} > 256 rows (one GEMM row tile)")
     eos = getattr(getattr(llama_model, "generation_config", None), "eos_token_id", None)      # as greedy_tokens resolves it
@@ -344,16 +437,25 @@ class _HipDecoder:
     stream -- no host sync, capturable -- on the K/V buffers the prefill filled, in place."""
     MAX_LEN = 4096                                                     # positions the rotary table covers (prompt + new tokens)
 
-    def __init__(self, llama_model, max_batch, weights="fp16", early_stop=False, grouped_kv=False):
+    def __init__(self, llama_model, max_batch, weights="fp16", early_stop=False, grouped_kv=False, activations="fp16", int8_threshold=6.0,
+                 outlier_cap=64):
         import ctypes as C
         from . import _lib
         if weights not in _lib.LLM_WEIGHT_FORMATS:
             raise ValueError(f'weights={weights!r}: expected "fp16" or "int8"')
+        if activations not in _lib.LLM_ACT_FORMATS:
+            raise ValueError(f'activations={activations!r}: expected "fp16" or "int8"')
+        if activations == "int8" and weights != "int8":
+            raise ValueError('activations="int8" needs weights="int8": int8 activations multiply int8 weights')
+        if activations == "int8" and not 1 <= int(outlier_cap) <= 1024:
+            raise ValueError(f"outlier_cap={outlier_cap!r}: expected 1..1024")
         self.weights = weights
+        self.activations, self.int8_threshold, self.outlier_cap = activations, float(int8_threshold), int(outlier_cap)
+        self._act_stats = None
         self.early_stop = bool(early_stop)
         self._greedy_ran = False                                       # live_steps has nothing to report before the first `greedy`
         self.grouped_kv = bool(grouped_kv)
-        bad = hip_decode_unsupported(llama_model, max_batch, grouped_kv=self.grouped_kv)
+        bad = hip_decode_unsupported(llama_model, max_batch, grouped_kv=self.grouped_kv, activations=activations)
         if bad:
             raise ValueError('decode="hip" does not support this decoder -- ' + "; ".join(bad))
         self._C, self._lib_mod, self.L = C, _lib, _lib.lib()
@@ -366,7 +468,8 @@ class _HipDecoder:
         # fp16 handles pass the config up to max_len, which every build of the library accepts (an A/B against an older build loads it
         # through CGPT_LIB_PATH); weight_format travels only when it says something
         # and so does grouped_kv: the extended struct (cgpt_llm_config_gqa) is sent only when the flag is set
-        size = (C.sizeof(_lib.LlmConfigGqa) if self.grouped_kv else
+        # and so does the activation format (cgpt_llm_config_act)
+        size = (C.sizeof(_lib.LlmConfigAct) if activations != "fp16" else C.sizeof(_lib.LlmConfigGqa) if self.grouped_kv else
                 C.sizeof(_lib.LlmConfig) if weights != "fp16" else _lib.LLM_CONFIG_SIZE_F16)
         c = _lib.LlmConfig(struct_size=size, weight_format=_lib.LLM_WEIGHT_FORMATS[weights], device=self.device.index or 0, hidden=int(cfg.hidden_size),
                            layers=self.layers, heads=self.heads, kv_heads=self.kv_heads, head_dim=128, mlp=int(cfg.intermediate_size),
@@ -374,7 +477,9 @@ class _HipDecoder:
                            max_batch=self.max_batch, max_len=self.MAX_LEN)
         self.handle = C.c_void_p()
         ext = _lib.LlmConfigGqa(base=c, grouped_kv=int(self.grouped_kv), reserved=0)     # create reads past `base` only when the size says so
-        _lib.check(self.L.cgpt_llm_create(C.byref(ext.base), C.byref(self.handle)))
+        act = _lib.LlmConfigAct(gqa=ext, act_format=_lib.LLM_ACT_FORMATS[activations], act_threshold=self.int8_threshold,
+                                outlier_cap=self.outlier_cap, reserved2=0)
+        _lib.check(self.L.cgpt_llm_create(C.byref(act.gqa.base), C.byref(self.handle)))
         st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         wanted = ["model.embed_tokens.weight", "model.norm.weight", "lm_head.weight"]
         for i in range(self.layers):
@@ -401,6 +506,24 @@ class _HipDecoder:
         n = C.c_int64()
         self._lib_mod.check(self.L.cgpt_llm_weight_bytes(self.handle, C.byref(n)))
         return int(n.value)
+
+    def act_stats(self):
+        """{rows, outliers, max_outliers_per_row, overflow_rows} of the native calls since the last read (cgpt_llm_act_stats: one
+        device sync; the counters are reset).  When nothing ran since, the last non-empty reading is returned again.  RuntimeError when
+        a row had more outliers than `outlier_cap`: its result is not the law's."""
+        C = self._C
+        if self.activations != "int8":
+            raise RuntimeError('act_stats: the engine was built with activations="fp16"')
+        v = (C.c_int64 * 4)()
+        self._lib_mod.check(self.L.cgpt_llm_act_stats(self.handle, v))
+        if v[0] > 0 or self._act_stats is None:
+            self._act_stats = {"rows": int(v[0]), "outliers": int(v[1]), "max_outliers_per_row": int(v[2]), "overflow_rows": int(v[3])}
+        if self._act_stats["overflow_rows"] > 0:
+            stats, self._act_stats = self._act_stats, None
+            raise RuntimeError(f'activations="int8": {stats["overflow_rows"]} of {stats["rows"]} activation rows had more than '
+                               f'outlier_cap={self.outlier_cap} outliers (the largest row: {stats["max_outliers_per_row"]}); their '
+                               "results are not the law's -- raise outlier_cap (up to 1024) or int8_threshold")
+        return dict(self._act_stats)
 
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
@@ -553,6 +676,9 @@ class MiniGPT4Classifier:
        :param ragged: "hf" (default) | "hip" -- who decodes a call whose rows carry DIFFERENT texts (left padding + mask); see __init__
        :param prompt_bucket: None | int >= 1 (with ragged="hip") -- padded prompt lengths are rounded up to a multiple of it
        :param weights: "fp16" (default) | "int8" (with decode="hip" and prefill="hip") -- how the native engine holds the layer linears
+       :param activations: "fp16" (default) | "int8" (with decode="hip", prefill="hip" and weights="int8") -- the LLM.int8() forward
+       :param int8_threshold: outlier threshold of activations="int8" (6.0: HF's llm_int8_threshold default; <= 0: no outlier split)
+       :param outlier_cap: outliers kept per activation row under activations="int8" (1..1024; more in a row is a RuntimeError)
        :param early_stop: False (default) | True (with decode="hip") -- the native token steps do no work once every row has its EOS
        :param grouped_kv: False (default) | True (with decode="hip") -- the native engine takes a grouped-query decoder; see __init__
        :param end_sym: text appended to every candidate answer of `multi_select` ("\n": the reference's default; its VQA configs: "###")
@@ -571,7 +697,7 @@ class MiniGPT4Classifier:
     def __init__(self, encoder, llama_model, llama_tokenizer, prompt, label_map, max_new_tokens=20, max_batch=None,
                  generate_kwargs=None, decode="hf", prefill_linear="torch", prefill="model", ragged="hf", prompt_bucket=None,
                  weights="fp16", end_sym="\n", label_smoothing=0.1, score="hf", classify="generate", candidates=None,
-                 early_stop=False, grouped_kv=False):
+                 early_stop=False, grouped_kv=False, activations="fp16", int8_threshold=6.0, outlier_cap=64):
         self.encoder = encoder
         self.llama_model = llama_model
         self.llama_tokenizer = llama_tokenizer
@@ -619,6 +745,15 @@ class MiniGPT4Classifier:
         #   the model whose layer linears are `int8_state_dict(llama_model)` (tests/test_gpu_llm_int8.py).  With the model's own
         #   prefill the prompt would run on W and the steps on W': a mixed model, hence the ValueError.  Works with ragged = "hip" and
         #   prompt_bucket.  weights = "fp16" (default): the engine's own fp16 copies, as before.
+        # activations = "int8" (with decode = "hip", prefill = "hip" AND weights = "int8"; anything else is a ValueError naming what is
+        #   missing): the layer linears run the LLM.int8() forward the reference's `low_resource: true` configs select -- row-wise int8
+        #   activations against the int8 weights on the int8 MFMA, int32 accumulation, and every row's features of magnitude >=
+        #   int8_threshold multiplied in fp32 against W' instead (`llm_int8_linear`).  The outlier set is per ROW, not
+        #   per batch as in bitsandbytes: a row's result depends on that row alone.  The oracle is `act_int8_twin(llama_model)`
+        #   (tests/test_gpu_llm_act_int8.py); parity with bitsandbytes itself is not pinned.  No fp16 scratch: weight_bytes drops by
+        #   it.  A row with more than outlier_cap outliers is a RuntimeError from `last_act_stats()`, which generate and the native
+        #   scoring call where they read their results.  Works with ragged = "hip", prompt_bucket, early_stop, grouped_kv and
+        #   score = "hip".  activations = "fp16" (default): as before.
         # early_stop = True (with decode = "hip" only; anything else is a ValueError): once every row of a batch has produced an EOS,
         #   the remaining token steps of the native greedy loop do no work (cgpt_llm_set_early_stop, DESIGN.md 4.4.5: a flag on the
         #   device that every step kernel reads first; the captured graph keeps all its launches and one graph serves every finishing
@@ -658,6 +793,20 @@ class MiniGPT4Classifier:
         if weights == "int8" and (decode != "hip" or prefill != "hip"):
             raise ValueError(f'weights="int8" needs decode="hip" and prefill="hip" (got decode={decode!r}, prefill={prefill!r}): '
                              "int8 weights exist on the native engine only, and prompt and steps must run on the same weights")
+        if activations not in ("fp16", "int8"):
+            raise ValueError(f'activations={activations!r}: expected "fp16" or "int8"')
+        if activations == "int8":
+            missing = [kw for kw, ok in (('decode="hip"', decode == "hip"), ('prefill="hip"', prefill == "hip"),
+                                         ('weights="int8"', weights == "int8")) if not ok]
+            if missing:
+                raise ValueError(f'activations="int8" needs {", ".join(missing)} (got decode={decode!r}, prefill={prefill!r}, '
+                                 f"weights={weights!r}): int8 activations multiply the native engine's int8 weights, in the prompt and "
+                                 "in the steps alike")
+            if isinstance(outlier_cap, bool) or not isinstance(outlier_cap, int) or not 1 <= outlier_cap <= 1024:
+                raise ValueError(f"outlier_cap={outlier_cap!r}: expected an int in 1..1024")
+            if isinstance(int8_threshold, bool) or not isinstance(int8_threshold, (int, float)) or int8_threshold != int8_threshold \
+                    or abs(int8_threshold) == float("inf"):
+                raise ValueError(f"int8_threshold={int8_threshold!r}: expected a finite number (<= 0: no outlier split)")
         if not isinstance(early_stop, bool):
             raise ValueError(f"early_stop={early_stop!r}: expected False or True")
         if early_stop and decode != "hip":
@@ -705,6 +854,9 @@ class MiniGPT4Classifier:
         self.grouped_kv = grouped_kv
         # the keyword reaches the engine only when it is set (as `law` reaches an encoder)
         gqa = {"grouped_kv": True} if grouped_kv else {}
+        self.activations, self.int8_threshold, self.outlier_cap = activations, float(int8_threshold), int(outlier_cap)
+        if activations == "int8":
+            gqa.update(activations="int8", int8_threshold=self.int8_threshold, outlier_cap=self.outlier_cap)
         self._hip = _HipDecoder(llama_model, self.max_batch, weights=weights, early_stop=early_stop, **gqa) if decode == "hip" else None
         self.routed_linears = (_LinearRoute.install(llama_model)
                                if (decode in ("graph", "hip") and prefill_linear == "cgpt" and prefill == "model") else 0)
@@ -720,6 +872,13 @@ class MiniGPT4Classifier:
                              "hf_score_fallbacks": 0,             # score = "hip" calls that took the "hf" path (see __init__)
                              # bytes the native engine holds for weights, scales and scratch (None without one)
                              "weight_bytes": self._hip.weight_bytes if self._hip is not None else None}
+
+    def last_act_stats(self):
+        """activations="int8": {rows, outliers, max_outliers_per_row, overflow_rows} of the last native call (one device sync).
+        RuntimeError when overflow_rows > 0, naming outlier_cap."""
+        if self._hip is None or self.activations != "int8":
+            raise RuntimeError('last_act_stats needs activations="int8"')
+        return self._hip.act_stats()
 
     # ---- nn.Module-shaped surface used by Smooth (smoothing.py:42,71)
     def eval(self):
@@ -777,6 +936,8 @@ class MiniGPT4Classifier:
                 starts = None
         if self.decode in ("graph", "hip") and (shared or native_pad) and embs.is_cuda and self._greedy_defaults():
             outputs = self._generate_graph(embs, starts)
+            if self.activations == "int8":                              # the tokens are read next: the same sync
+                self.last_act_stats()
         else:
             self.decode_stats["hf_calls"] += 1
             if self.decode in ("graph", "hip") and (shared or self.ragged == "hip") and embs.is_cuda:
@@ -1122,6 +1283,8 @@ class MiniGPT4Classifier:
         sums = hip.score(first, L, table.to(embs.device), lens, self.label_smoothing, k_bufs, v_bufs)
         self.decode_stats["hip_prefills"] += 1
         self.decode_stats["hip_scores"] += 1
+        if self.activations == "int8":                                  # the losses are read next: the same sync
+            self.last_act_stats()
         # the reference runs one forward per candidate, so each candidate's divisor is its own sequence length - 1
         return sums / torch.tensor([float(L + t - 1) for t in lens], device=sums.device)
 

@@ -369,8 +369,8 @@ typedef struct cgpt_llm_config_gqa {
 
 /* cgpt_llm_config.weight_format.
  * CGPT_LLM_W_INT8 (W8A16): the seven linears of every layer are held as row-wise absmax int8, one fp16 scale per output row
- * (the weight law of bitsandbytes' load_in_8bit; activations stay fp16, no outlier decomposition -- parity with LLM.int8()'s
- * forward is NOT pinned).  For row n of an nn.Linear.weight [N, K]:  s_n = fp16(absmax_k |w_nk| / 127), the division in fp32;
+ * (the weight law of bitsandbytes' load_in_8bit; activations stay fp16 and there is no outlier decomposition unless
+ * cgpt_llm_config_act.act_format = 1, below -- parity with LLM.int8()'s forward is NOT pinned).  For row n of an nn.Linear.weight [N, K]:  s_n = fp16(absmax_k |w_nk| / 127), the division in fp32;
  * q_nk = clamp(rint(fp32(w_nk) / fp32(s_n)), -127, 127), round to nearest even, q = 0 where s_n = 0;  W'_nk = fp16(q_nk) * s_n,
  * ONE fp16 multiply.  Every result of an int8 handle is bit for bit the result of an fp16 handle whose layer linears were loaded
  * with W'.  lm_head, embed_tokens and the RMSNorm weights stay fp16. */
@@ -382,8 +382,8 @@ typedef struct cgpt_llm* cgpt_llm_handle;
 /* Allocates the library's own weight copies (fused q/k/v and gate/up, 2 bytes per parameter: 13.5 GB MORE HBM at 7B, beside the
  * HF module's; CGPT_LLM_W_INT8: 1 byte per layer-linear parameter, the row scales and ONE fp16 scratch matrix of the largest fused
  * layer matrix for the prefill, 7.2 GB at 7B) and the step workspace.  CGPT_ERR_INVALID for an unsupported config, a struct_size
- * that is none of the three valid ones (cgpt_llm_config_gqa, the whole cgpt_llm_config, cgpt_llm_config up to max_len), or an unknown
- * weight_format / grouped_kv; CGPT_ERR_NO_DEVICE without a GPU. */
+ * that is none of the valid ones (cgpt_llm_config_act, cgpt_llm_config_gqa, the whole cgpt_llm_config, cgpt_llm_config up to max_len),
+ * or an unknown weight_format / grouped_kv / act_format; CGPT_ERR_NO_DEVICE without a GPU. */
 cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out);
 cgpt_status cgpt_llm_destroy(cgpt_llm_handle h);
 /* Device-to-device copy of one fp16 parameter of the HF module under its state_dict name: "model.embed_tokens.weight",
@@ -395,7 +395,9 @@ cgpt_status cgpt_llm_load_weight_f16(cgpt_llm_handle h, const char* name, const 
  * caller's fp16 rows and writes int8 rows and their scales into the fused matrix (rows keep their scales through the q/k/v fusion
  * and the gate/up interleave); no fp16 copy of the layer survives the call.  The other names are copied as above.
  * cgpt_llm_weight_bytes: *out = the bytes this handle holds for weight matrices (embed_tokens, lm_head and the layer linears with
- * their padding to 256-row tiles), row scales and the dequantisation scratch, as allocated -- the library's own accounting.  The
+ * their padding to 256-row tiles), row scales and the dequantisation scratch (none with act_format = 1), as allocated -- the
+ * library's own accounting: embed + lm_head (2 V H bytes) + per layer, for each fused matrix [N, K], up256(N) K (int8) + 2 up256(N)
+ * (scales), or 2 up256(N) K (fp16); + the scratch, 2 max(up256(N) K) bytes, on an int8 handle with act_format = 0 only.  The
  * RMSNorm vectors, the rotary table and the step / prefill workspaces are not counted. */
 cgpt_status cgpt_llm_weight_bytes(cgpt_llm_handle h, int64_t* out);
 /* One token step: row b feeds token tokens_dev[b] (int64) at position `pos`; layer l appends its rotated key and its value to
@@ -519,6 +521,57 @@ cgpt_status cgpt_llm_score_reserve(cgpt_llm_handle h, int32_t max_rows, int32_t 
 cgpt_status cgpt_llm_score(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len,
                            const int64_t* cand_tokens_dev, const int32_t* cand_lens_host, int32_t C, int32_t Tmax, float label_smoothing,
                            void* const* k_ptrs_host, void* const* v_ptrs_host, int64_t kv_len_stride, float* out_dev, void* stream);
+
+/* ---- int8 activations: the LLM.int8() forward on the native engine (W8A8 with a per-row outlier split) ----
+ * Replaces: the `load_in_8bit=True` decoder the reference's configs select (`low_resource: true`, base_model.py:196-213): row-wise
+ * int8 weights, row-wise int8 activations, int32 accumulation, outlier features above a threshold multiplied in higher precision.
+ * One more extended config: a cgpt_llm_config_gqa followed by three fields, recognised by gqa.base.struct_size =
+ * sizeof(cgpt_llm_config_act) alone; pass &cfg.gqa.base to cgpt_llm_create.  The older structs, their sizes and their `reserved must
+ * be 0` rule are unchanged.  act_format = 1 needs weight_format = CGPT_LLM_W_INT8, hidden and mlp multiples of 128 (one K-tile of the
+ * int8 kernel is 128 bytes), a finite act_threshold and outlier_cap in 1..1024; each violation is CGPT_ERR_INVALID with a message,
+ * before any device call.  act_format = 0 ignores the other two fields and is the handle as it was.
+ * The law of a layer linear on such a handle, per input row x[K] (fp16), with q / s_w the weight law above and t = act_threshold:
+ *   k is an outlier iff t > 0 and |x_k| >= t;   s_a = max over non-outliers |x_k| / 127 (fp32, correctly rounded, kept in fp32);
+ *   a_k = clamp(rint(fp32(x_k) / s_a), -127, 127) (nearest even), 0 for outliers, the whole row 0 when s_a == 0;
+ *   acc_n = sum_k a_k q_nk in int32 (exact);   y_n = fp32(acc_n) * (s_a * fp32(s_w[n])), two fp32 multiplies, the inner first;
+ *   o_n = sum over outliers in ascending k of fp32(x_k) * fp32(W'_nk), sequential fp32 from 0;   v_n = y_n + o_n;
+ *   then the epilogue rounds where the fp16 engine's does.  lm_head, embed_tokens and the RMSNorm weights stay fp16.
+ * The outlier set is PER ROW (bitsandbytes takes outlier columns over the whole batch): a row's result is a function of that row
+ * alone, as every batch-independence identity of this engine requires.  Parity with bitsandbytes is NOT pinned.
+ * A row with more than outlier_cap outliers keeps its first outlier_cap (ascending k), is counted in overflow_rows, and its result is
+ * finite but not the law's: read cgpt_llm_act_stats and treat overflow_rows > 0 as an error (raise outlier_cap).
+ * Such a handle allocates no fp16 dequantisation scratch (the prefill runs the same int8 kernel), and cgpt_llm_weight_bytes says so. */
+typedef struct cgpt_llm_config_act {
+    cgpt_llm_config_gqa gqa;  /* gqa.base.struct_size = sizeof(cgpt_llm_config_act); gqa.reserved must be 0 */
+    int32_t act_format;       /* CGPT_LLM_A_F16 (0) | CGPT_LLM_A_INT8 (1)                          */
+    float   act_threshold;    /* 6.0 = HF's llm_int8_threshold default; <= 0: no outlier split     */
+    int32_t outlier_cap;      /* 1 .. 1024 outliers kept per row                                   */
+    int32_t reserved2;        /* must be 0                                                         */
+} cgpt_llm_config_act;
+#define CGPT_LLM_A_F16 0
+#define CGPT_LLM_A_INT8 1
+/* SYNCHRONISES the handle's device, then out_host[0..3] = rows quantised, outliers found, the largest outlier count of one row and
+ * overflow_rows, over every native call since the last read (or create); the counters are then reset.  All zeros on a handle with
+ * act_format = 0.  Not capturable (call it outside a capture; captured work counts when it replays). */
+cgpt_status cgpt_llm_act_stats(cgpt_llm_handle h, int64_t* out_host);
+
+/* The raw linear of the law above, without a handle: out = epilogue(law(A, q, s_w)) for A [M, K] fp16 (rows K apart), q [N, K] int8,
+ * s_w [N] fp16, on `stream`.  epilogue: 0 = fp16(v) -> out [M, N];  1 = fp16(fp16(v) + resid) -> out [M, N], resid [M, N] fp16 (may be
+ * out);  2 = SwiGLU -> out [M, N / 2], q / s_w holding gate / up rows interleaved in blocks of 16 as the engine's fused matrix does.
+ * out_bytes is the size of the buffer at out_dev and must cover the result; workspace_dev must be 256-byte aligned and hold
+ * cgpt_llm_linear_i8_workspace(M, N, K, outlier_cap, NULL) bytes.  CGPT_ERR_INVALID before any launch for: a null pointer, M < 1 or
+ * M > 2^24, N or K < 1, N % 64, K % 128, K > 65536, a cap outside 1..1024, an unknown epilogue, epilogue 1 without resid, a short
+ * out_bytes or workspace_bytes, a misaligned workspace.  Sets kernel attributes on the current device: call it outside a capture.
+ * cgpt_llm_linear_i8_workspace: the bytes needed (-1 for bad sizes); offsets_out (or NULL) receives the byte offsets of the five
+ * regions: [0] counters (4 x int64: rows, outliers, max per row, overflow rows -- zeroed by the call, then written by it),
+ * [1] int8 codes [round_up(M, 256)][K] (rows >= M are read by the GEMM, never written), [2] s_a fp32 [round_up(M, 256)],
+ * [3] outlier lists uint32 [round_up(M, 256)][cap + 1], [4] int32 slabs.
+ * cgpt_llm_linear_i8_slices: K slices a call of M <= 256 runs with (a function of N and K only; 1 for M > 256); -1 for bad sizes. */
+cgpt_status cgpt_llm_linear_i8(const void* A_dev, const void* q_dev, const void* sw_dev, int64_t M, int64_t N, int64_t K,
+                               float threshold, int32_t outlier_cap, int32_t epilogue, const void* resid_dev, void* out_dev,
+                               int64_t out_bytes, void* workspace_dev, int64_t workspace_bytes, void* stream);
+int64_t cgpt_llm_linear_i8_workspace(int64_t M, int64_t N, int64_t K, int32_t outlier_cap, int64_t* offsets_out);
+int32_t cgpt_llm_linear_i8_slices(int64_t N, int64_t K);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,8 @@ reads, over 6.3 TB/s (the copy rate the box reaches).
     parent      `plain` on another build of the library (--parent-lib PATH, e.g. the parent commit's libcgpt.so), loaded beside
                 the product in this process: the claim to check is that the plain path's time is unchanged
 
+--act-int8 adds a third engine to the weight-format leg below: weights="int8" with activations="int8" (quantise +
+int8-MFMA GEMM per layer linear, per-row outlier split), reported against both other engines.
 --int8 runs the weight-format leg instead (weights="int8"), same protocol, every engine decode="hip", prefill="hip":
     fp16        the engine's own fp16 copies (today's path)
     int8        row-wise absmax int8 layer linears: the int8-weight decode GEMM in the steps, a dequant pass before each prefill GEMM
@@ -199,6 +201,9 @@ def int8_leg(args, llm, embs, tok, lm):
     legs = ["fp16", "int8"]
     clfs = {("fp16", n): build(n) for n in (args.new, 1)}
     clfs.update({("int8", n): build(n, weights="int8") for n in (args.new, 1)})
+    if args.act_int8:                                                  # W8A8 with the outlier split beside W8A16 and fp16
+        clfs.update({("act_int8", n): build(n, weights="int8", activations="int8") for n in (args.new, 1)})
+        legs.append("act_int8")
     if args.parent_lib:
         with _other_library(args.parent_lib):
             clfs.update({("parent", n): build(n) for n in (args.new, 1)})
@@ -254,6 +259,13 @@ def int8_leg(args, llm, embs, tok, lm):
             "copy_rate_bytes_per_s": COPY_RATE,
             "int8_rows_with_fp16_tokens": int((tokens["int8"] == tokens["fp16"]).all(dim=1).sum()),
             "shader_clock_mhz_before_after": [clock_before, clock_after], "device": torch.cuda.get_device_name(0)}
+    if "act_int8" in res:
+        line["leg"] = "act_int8"
+        line["act_int8_over_fp16_median"] = {k: med("act_int8", k) / med("fp16", k) for k in keys}
+        line["act_int8_over_int8_median"] = {k: med("act_int8", k) / med("int8", k) for k in keys}
+        line["act_int8_and_int8_ranges_overlap"] = {k: overlap("act_int8", "int8", k) for k in keys}
+        line["act_int8_rows_with_int8_tokens"] = int((tokens["act_int8"] == tokens["int8"]).all(dim=1).sum())
+        line["act_stats_last_call"] = clfs[("act_int8", args.new)].last_act_stats()
     if "parent" in res:
         line["parent_lib"] = os.path.basename(args.parent_lib)
         line["fp16_and_parent_ranges_overlap"] = {k: overlap("fp16", "parent", k) for k in keys}
@@ -450,6 +462,8 @@ def main():
     ap.add_argument("--bucket-len", type=int, default=48)
     ap.add_argument("--ragged-min", type=int, default=38)
     ap.add_argument("--int8", action="store_true", help="the weight-format leg (see the module docstring)")
+    ap.add_argument("--act-int8", action="store_true",
+                    help='with the weight-format leg: a third engine, weights="int8" + activations="int8" (DESIGN.md 4.4.7)')
     ap.add_argument("--early-stop", action="store_true", help="the early-stop leg (see the module docstring)")
     ap.add_argument("--gqa", action="store_true", help="the grouped-query leg (see the module docstring)")
     ap.add_argument("--gqa-vocab", type=int, default=128256)
@@ -468,7 +482,7 @@ def main():
     tok, lm = WordHashTokenizer(32000), AnswerLabelMap(4, ())
     if args.ragged:
         return ragged_leg(args, llm, embs, tok, lm)
-    if args.int8:
+    if args.int8 or args.act_int8:
         return int8_leg(args, llm, embs, tok, lm)
     if args.early_stop:
         return early_stop_leg(args, llm, embs, tok, lm)
