@@ -127,6 +127,7 @@ SIGNATURES = {
     "cgpt_llm_linear_i8_workspace": (_I64, [_I64, _I64, _I64, _I32, C.POINTER(_I64)]),
     "cgpt_llm_linear_i8_slices": (_I32, [_I64, _I64]),
     "cgpt_llm_score": (_I32, [_P, _P, _I32, _I32, _P, _P, _I32, _I32, _F, _P, _P, _I64, _P, _P]),
+    "cgpt_llm_score_ragged": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _F, _P, _P, _I64, _P, _P]),
 }
 
 _lib = None

@@ -95,26 +95,34 @@ constexpr int SCORE_MAX_CANDS = 64;      // candidates of one call
 constexpr int SCORE_MAX_TAIL = 64;       // tail rows per prompt row (the attention kernel keeps their state in LDS)
 struct ScoreCands {                      // passed by value: nothing is copied to the device by the host
     int n;                               // C
-    int tmax;                            // row length of the token table [C, tmax]
+    int tmax;                            // row length of the token table [C, tmax] ([B, C, tmax] with per-row candidates)
     int off[SCORE_MAX_CANDS + 1];        // off[c] = sum of (T_c' - 1) over c' < c; off[n] = S.  T_c = off[c + 1] - off[c] + 1
 };
 // Sets the attention kernel's dynamic-LDS limit on the CURRENT device (once per device, outside any capture).
 hipError_t score_prepare();
-// h[r, :] = embed[token of tail row r, :]; a token outside the table reads row 0.
+// Per-row prompts and candidates (cgpt_llm_score_ragged): `starts` / `row_lens` / `per_row` below select the RAGGED instantiations;
+// null / false are the plain kernels, which read neither array.
+//   starts   (device, [B] int32): row b is left-padded by start[b] positions (clamped into 0 .. L-1), see launch_prefill_rope
+//   row_lens (device, [B, C] int32): row b's real length of candidate c (clamped into 1 .. T_c); the token table is then
+//            [B, C, tmax] and T_c of `t` the longest length of candidate c over the rows
+// h[r, :] = embed[token of tail row r, :]; a token outside the table reads row 0.  per_row: the table is [B, C, tmax].
 hipError_t launch_score_embed(const long long* cand_tokens, const ScoreCands& t, int B, const half_t* table, int vocab, int hidden,
-                              half_t* h, hipStream_t stream);
+                              half_t* h, hipStream_t stream, bool per_row = false);
 // Rotary + attention of the tail rows: out[r, head] = softmax(q_r . [K_prompt(b, 0..L-1); k_tail(b, c, 0..j)] / sqrt(128)) . V alike,
 // q / k / v from qkv [B S, 3 hidden] (not modified).  Kc / Vc are read (rows 0 .. L-1) and NEVER written.
+// starts: the prompt keys of row b are cache rows start[b] .. L-1 (rows below are never read), tail row j is rotated at L - start[b] + j.
 hipError_t launch_score_attention(const half_t* qkv, const ScoreCands& t, int B, int L, int hidden, int heads, int kv_heads, const half_t* Kc,
-                                  const half_t* Vc, int64_t len_stride, const half_t* rope, half_t* out, hipStream_t stream);
+                                  const half_t* Vc, int64_t len_stride, const half_t* rope, half_t* out, hipStream_t stream,
+                                  const int32_t* starts = nullptr);
 // ce[b, tok(c) + j] = label-smoothed cross-entropy of one logits row against token j of candidate c, tok(c) = off[c] + c, a row of
 // ce holding S + C values.  first: token 0 of every candidate on the fp32 rows first_logits[b] (B x C workgroups).  tail: `rows`
 // fp16 logits rows, the tail rows row0 .. row0 + rows - 1 (row r predicts token j + 1 of its candidate).
+// row_lens: ce[b, tok(c) + j] = 0 for j >= the row's length of candidate c.
 hipError_t launch_score_ce_first(const float* first_logits, int vocab, const long long* cand_tokens, const ScoreCands& t, int B,
-                                 float smoothing, float* ce, hipStream_t stream);
+                                 float smoothing, float* ce, hipStream_t stream, const int32_t* row_lens = nullptr);
 hipError_t launch_score_ce_tail(const half_t* logits, int vocab, const long long* cand_tokens, const ScoreCands& t, int64_t row0,
-                                int64_t rows, float smoothing, float* ce, hipStream_t stream);
-// out[b, c] = ce[b, tok(c)] + ... + ce[b, tok(c) + T_c - 1], added in token order.
-hipError_t launch_score_sum(const float* ce, const ScoreCands& t, int B, float* out, hipStream_t stream);
+                                int64_t rows, float smoothing, float* ce, hipStream_t stream, const int32_t* row_lens = nullptr);
+// out[b, c] = ce[b, tok(c)] + ... + ce[b, tok(c) + T_c - 1], added in token order.  row_lens: the row's own tokens only.
+hipError_t launch_score_sum(const float* ce, const ScoreCands& t, int B, float* out, hipStream_t stream, const int32_t* row_lens = nullptr);
 
 }  // namespace cgpt

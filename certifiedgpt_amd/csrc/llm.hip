@@ -730,21 +730,23 @@ constexpr int64_t SCORE_LOGIT_ROWS = 4096;                 // tail rows whose fp
 // All candidates of `t` on the prompt cache rows 0 .. L-1 of B prompt rows: out[b, c] = summed label-smoothed cross-entropy.
 // run_prefill's layer sequence on the R = B S tail rows with the tail attention in place of rotary + cache write + causal
 // attention; then lm_head and the cross-entropy in chunks of the reserved logits rows.  No cache row is written.
-cgpt_status run_score(cgpt_llm* m, const float* first_logits, int B, int L, const long long* cand_tokens, const ScoreCands& t, float eps,
-                      void* const* kp, void* const* vp, int64_t len_stride, float* out, hipStream_t st) {
+// starts / row_lens (device, or both null: the plain kernels): per-row left padding and per-row candidates [B, C, tmax], see llm.h.
+cgpt_status run_score(cgpt_llm* m, const float* first_logits, int B, int L, const int32_t* starts, const long long* cand_tokens,
+                      const int32_t* row_lens, const ScoreCands& t, float eps, void* const* kp, void* const* vp, int64_t len_stride,
+                      float* out, hipStream_t st) {
     const cgpt_llm_config& c = m->cfg;
     const int H = c.hidden, F = c.mlp, S = t.off[t.n];
     const int64_t R = (int64_t)B * S;
-    HIPCHK(launch_score_ce_first(first_logits, c.vocab, cand_tokens, t, B, eps, m->s_ce_buf, st));
+    HIPCHK(launch_score_ce_first(first_logits, c.vocab, cand_tokens, t, B, eps, m->s_ce_buf, st, row_lens));
     if (S > 0) {
-        HIPCHK(launch_score_embed(cand_tokens, t, B, m->embed, c.vocab, H, m->p_h, st));
+        HIPCHK(launch_score_embed(cand_tokens, t, B, m->embed, c.vocab, H, m->p_h, st, row_lens != nullptr));
         const half_t* pending = nullptr;
         for (int l = 0; l < c.layers; ++l) {
             const Layer& Lw = m->layers[l];
             HIPCHK(launch_prefill_addnorm(m->p_h, pending, 1, 0, Lw.ln1, H, c.rms_eps, m->p_h, m->p_xn, R, st));
             CGCHK(big_gemm(m, m->p_xn, H, Lw.wqkv, qkv_width(c), m->p_qkv, R, st));
             HIPCHK(launch_score_attention(m->p_qkv, t, B, L, H, c.heads, c.kv_heads, (const half_t*)kp[l], (const half_t*)vp[l], len_stride, m->rope,
-                                          m->p_attn, st));
+                                          m->p_attn, st, starts));
             CGCHK(big_gemm(m, m->p_attn, H, Lw.wo, H, m->p_proj, R, st));
             HIPCHK(launch_prefill_addnorm(m->p_h, m->p_proj, 1, 0, Lw.ln2, H, c.rms_eps, m->p_h, m->p_xn, R, st));
             CGCHK(big_gemm(m, m->p_xn, H, Lw.wgu, 2 * F, m->p_gu, R, st));
@@ -756,10 +758,10 @@ cgpt_status run_score(cgpt_llm* m, const float* first_logits, int B, int L, cons
         for (int64_t r0 = 0; r0 < R; r0 += m->s_rows) {        // chunks begin at multiples of 256 rows: whole GEMM row tiles
             const int64_t n = std::min(m->s_rows, R - r0);
             CGCHK(big_gemm(m, m->p_xn + r0 * H, H, Mat{m->lm_head}, c.vocab, m->s_logits, n, st));
-            HIPCHK(launch_score_ce_tail(m->s_logits, c.vocab, cand_tokens, t, r0, n, eps, m->s_ce_buf, st));
+            HIPCHK(launch_score_ce_tail(m->s_logits, c.vocab, cand_tokens, t, r0, n, eps, m->s_ce_buf, st, row_lens));
         }
     }
-    HIPCHK(launch_score_sum(m->s_ce_buf, t, B, out, st));
+    HIPCHK(launch_score_sum(m->s_ce_buf, t, B, out, st, row_lens));
     return CGPT_OK;
 }
 
@@ -1281,10 +1283,12 @@ cgpt_status cgpt_llm_score_reserve(cgpt_llm_handle h, int32_t max_rows, int32_t 
     return CGPT_OK;
 }
 
-cgpt_status cgpt_llm_score(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len, const int64_t* cand_tokens_dev,
-                           const int32_t* cand_lens_host, int32_t C, int32_t Tmax, float label_smoothing, void* const* k_ptrs_host,
-                           void* const* v_ptrs_host, int64_t kv_len_stride, float* out_dev, void* stream) {
-    const std::string who("cgpt_llm_score");
+// The plain and the _ragged entry share one body: `who_c` names the entry in messages, starts_dev == null is the plain one.
+static cgpt_status llm_score_entry(const char* who_c, cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len,
+                                   const int32_t* starts_dev, const int64_t* cand_tokens_dev, const int32_t* cand_lens_dev,
+                                   const int32_t* cand_lens_host, int32_t C, int32_t Tmax, float label_smoothing, void* const* k_ptrs_host,
+                                   void* const* v_ptrs_host, int64_t kv_len_stride, float* out_dev, void* stream) {
+    const std::string who(who_c);
     if (!h || !first_logits_dev || !cand_tokens_dev || !cand_lens_host || !out_dev) return cgpt_fail(CGPT_ERR_INVALID, who + ": null argument");
     if (C < 1 || C > SCORE_MAX_CANDS || Tmax < 1)
         return cgpt_fail(CGPT_ERR_INVALID, who + ": candidates outside 1.." + std::to_string(SCORE_MAX_CANDS) + " or Tmax < 1");
@@ -1301,15 +1305,31 @@ cgpt_status cgpt_llm_score(cgpt_llm_handle h, const float* first_logits_dev, int
     }
     if (prompt_len < 1 || (int64_t)prompt_len + Tmax - 1 > h->cfg.max_len)
         return cgpt_fail(CGPT_ERR_INVALID, who + ": prompt_len < 1 or prompt_len + Tmax - 1 > max_len (the rotary table)");
-    CGCHK(check_cache(h, "cgpt_llm_score", B, prompt_len - 1, k_ptrs_host, v_ptrs_host, kv_len_stride));
-    CGCHK(ready(h, "cgpt_llm_score"));
+    CGCHK(check_cache(h, who_c, B, prompt_len - 1, k_ptrs_host, v_ptrs_host, kv_len_stride));
+    CGCHK(ready(h, who_c));
     const int64_t R = (int64_t)B * t.off[C];
     if (R > h->p_rows || (R > 0 && h->s_rows < 1) || (int64_t)B * (t.off[C] + C) > h->s_ce)
         return cgpt_fail(CGPT_ERR_STATE, who + ": " + std::to_string(R) + " tail rows of " + std::to_string(C) +
                                              " candidates exceed the reserved workspace (call cgpt_llm_score_reserve outside any capture first)");
     HIPCHK(hipSetDevice(h->cfg.device));
-    return run_score(h, first_logits_dev, B, prompt_len, (const long long*)cand_tokens_dev, t, label_smoothing, k_ptrs_host, v_ptrs_host,
-                     kv_len_stride, out_dev, (hipStream_t)stream);
+    return run_score(h, first_logits_dev, B, prompt_len, starts_dev, (const long long*)cand_tokens_dev, cand_lens_dev, t, label_smoothing,
+                     k_ptrs_host, v_ptrs_host, kv_len_stride, out_dev, (hipStream_t)stream);
+}
+
+cgpt_status cgpt_llm_score(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len, const int64_t* cand_tokens_dev,
+                           const int32_t* cand_lens_host, int32_t C, int32_t Tmax, float label_smoothing, void* const* k_ptrs_host,
+                           void* const* v_ptrs_host, int64_t kv_len_stride, float* out_dev, void* stream) {
+    return llm_score_entry("cgpt_llm_score", h, first_logits_dev, B, prompt_len, nullptr, cand_tokens_dev, nullptr, cand_lens_host, C, Tmax,
+                           label_smoothing, k_ptrs_host, v_ptrs_host, kv_len_stride, out_dev, stream);
+}
+
+cgpt_status cgpt_llm_score_ragged(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len,
+                                  const int32_t* starts_dev, const int64_t* cand_tokens_dev, const int32_t* cand_lens_dev,
+                                  const int32_t* cand_lens_host, int32_t C, int32_t Tmax, float label_smoothing, void* const* k_ptrs_host,
+                                  void* const* v_ptrs_host, int64_t kv_len_stride, float* out_dev, void* stream) {
+    if (!starts_dev || !cand_lens_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_score_ragged: null starts_dev or cand_lens_dev");
+    return llm_score_entry("cgpt_llm_score_ragged", h, first_logits_dev, B, prompt_len, starts_dev, cand_tokens_dev, cand_lens_dev,
+                           cand_lens_host, C, Tmax, label_smoothing, k_ptrs_host, v_ptrs_host, kv_len_stride, out_dev, stream);
 }
 
 }  // extern "C"

@@ -11,6 +11,15 @@
 // Rounding follows the token step (llm.hip: llm_attn_kernel): rotary products and their sum in fp16, scores, probabilities and
 // sums in fp32.  Plain vector stores, no atomics, fixed summation orders: a (row, candidate) result depends on nothing but that
 // row's prompt cache and that candidate's tokens -- not on the batch, not on the other candidates, not on the launch.
+//
+// Per-row prompts and candidates (cgpt_llm_score_ragged): every kernel has a RAGGED instantiation.  Row b is left-padded by start[b]
+// positions (device array, clamped into 0 .. L-1 as the ragged prefill clamps it) and the attention works in row-relative coordinates:
+// the head's cache pointers move by start[b], the chunk walk runs over len[b] = L - start[b] keys and tail row j is rotated at
+// len[b] + j, so a padded row walks the keys of the row run alone in the same order.  The token table is [B, C, tmax] and a device
+// array len[B, C] holds each row's real length of each candidate (clamped into 1 .. T_c); the geometry `ScoreCands` stays uniform over
+// the rows, T_c being the longest length of candidate c.  A row shorter than T_c still runs its surplus tail rows (row-independent
+// work on finite inputs: their tokens are read through clamp_token); the cross-entropy of a token j >= len[b, c] is written as 0 and
+// the sum leaves it out.  The plain instantiations read neither array and compile to the code they were.
 #include <math.h>
 
 #include "llm.h"
@@ -41,12 +50,15 @@ __device__ __forceinline__ void slot_of(const ScoreCands& t, int s, int& c, int&
 __device__ __forceinline__ long long clamp_token(long long tok, int vocab) { return (tok < 0 || tok >= vocab) ? 0 : tok; }
 
 // h[r, :] = embed[token, :] for tail row r = b * S + s; one workgroup per row.
+// RAGGED: row b = blockIdx.x / S reads its own slice of the table [B, C, tmax].
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void llm_score_embed_kernel(const long long* __restrict__ cand_tokens, ScoreCands t,
                                                               const half_t* __restrict__ table, int vocab, int hidden,
                                                               half_t* __restrict__ h) {
     const int S = t.off[t.n];
     int c, j;
     slot_of(t, (int)(blockIdx.x % S), c, j);
+    if (RAGGED) cand_tokens += (int64_t)(blockIdx.x / S) * t.n * t.tmax;
     const long long tok = clamp_token(cand_tokens[(int64_t)c * t.tmax + j], vocab);
     const h16x8* src = reinterpret_cast<const h16x8*>(table + tok * hidden);
     h16x8* dst = reinterpret_cast<h16x8*>(h + (int64_t)blockIdx.x * hidden);
@@ -68,11 +80,15 @@ __global__ __launch_bounds__(256) void llm_score_embed_kernel(const long long* _
 // GROUPED (grouped-query attention): query head h reads K/V head kh = h / (heads / kv_heads) -- of the
 // [B, kv_heads, len_stride, 128] cache, and of the tail rows' k / v in a projection row hidden + 2 kv_heads 128 wide.  The G heads of a
 // group do not share a staged chunk here.  The plain instantiation never reads kv_heads.
-template <bool GROUPED>
+// RAGGED (left-padded rows): s = start[b] clamped into 0 .. L-1; the head's K / V pointers move by s (s * 128 halfs: the 16-byte loads
+// stay aligned) and L stands for len = L - s below -- the chunk walk covers the row's len real keys from its first one, tail row j
+// is rotated at len + j.  The chunk grid and the key order of a row depend on len alone; cache rows below s are never read.  LDS use
+// depends on S only.  The plain instantiation never reads starts.
+template <bool GROUPED, bool RAGGED>
 __global__ __launch_bounds__(256) void llm_score_attn_kernel(const half_t* __restrict__ qkv, ScoreCands t, int L, int hidden, int heads,
                                                              const half_t* __restrict__ Kc, const half_t* __restrict__ Vc,
                                                              int64_t len_stride, const half_t* __restrict__ rope,
-                                                             half_t* __restrict__ out, int kv_heads) {
+                                                             half_t* __restrict__ out, int kv_heads, const int* __restrict__ starts) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int S = t.off[t.n];
     half_t* ks = reinterpret_cast<half_t*>(smem);             // [KC][128] staged prompt keys
@@ -89,6 +105,12 @@ __global__ __launch_bounds__(256) void llm_score_attn_kernel(const half_t* __res
     const int64_t ldq = GROUPED ? hidden + 2 * kv_heads * HD : 3 * hidden;
     const half_t* Kh = Kc + (int64_t)(b * (GROUPED ? kv_heads : heads) + kh) * len_stride * HD;
     const half_t* Vh = Vc + (int64_t)(b * (GROUPED ? kv_heads : heads) + kh) * len_stride * HD;
+    if (RAGGED) {
+        const int s0 = min(max(starts[b], 0), L - 1);
+        Kh += (int64_t)s0 * HD;
+        Vh += (int64_t)s0 * HD;
+        L -= s0;
+    }
 
     for (int i = tid; i < S * 64; i += 256) {                 // thread (s, p) owns the rotary pair (p, p + 64) of tail row s
         const int s = i >> 6, p = i & 63;
@@ -226,10 +248,12 @@ __device__ __forceinline__ float block_sum(float v, float* wsum) {
 // row, two passes over it (the second one hits L2), all statistics in fp32, per-thread strided sums combined by block_sum.
 //   FIRST: workgroup (b, c) reads the fp32 row b and scores token 0 of candidate c
 //   else:  workgroup i reads fp16 row i of `logits`, which is tail row row0 + i = (b, c, j), and scores token j + 1
-template <typename T, bool FIRST>
+// RAGGED: the token comes from row b's slice of the table [B, C, tmax]; a token at or past the row's own length of the candidate
+// (cand_lens[b, c] clamped into 1 .. T_c) has its slot written as 0 and nothing else done -- uniform over the workgroup.
+template <typename T, bool FIRST, bool RAGGED>
 __global__ __launch_bounds__(256) void llm_score_ce_kernel(const T* __restrict__ logits, int vocab,
                                                            const long long* __restrict__ cand_tokens, ScoreCands t, int64_t row0,
-                                                           float eps, float* __restrict__ ce) {
+                                                           float eps, float* __restrict__ ce, const int* __restrict__ cand_lens) {
     __shared__ float wsum[4];
     const int S = t.off[t.n];
     int64_t b, src;
@@ -245,6 +269,14 @@ __global__ __launch_bounds__(256) void llm_score_ce_kernel(const T* __restrict__
         slot_of(t, (int)(r % S), c, j);
         j += 1;
         src = blockIdx.x;
+    }
+    if (RAGGED) {
+        const int Tc = t.off[c + 1] - t.off[c] + 1;
+        if (j >= min(max(cand_lens[b * t.n + c], 1), Tc)) {
+            if (threadIdx.x == 0) ce[b * (S + t.n) + t.off[c] + c + j] = 0.0f;
+            return;
+        }
+        cand_tokens += b * t.n * t.tmax;
     }
     const T* z = logits + src * vocab;
     float mx = -INFINITY, sz = 0.0f;
@@ -279,12 +311,15 @@ __global__ __launch_bounds__(256) void llm_score_ce_kernel(const T* __restrict__
     }
 }
 
-// out[b, c] = the candidate's per-token values added in token order; one thread per (b, c).
-__global__ __launch_bounds__(256) void llm_score_sum_kernel(const float* __restrict__ ce, ScoreCands t, int B, float* __restrict__ out) {
+// out[b, c] = the candidate's per-token values added in token order; one thread per (b, c).  RAGGED: the row's own tokens only.
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void llm_score_sum_kernel(const float* __restrict__ ce, ScoreCands t, int B, float* __restrict__ out,
+                                                            const int* __restrict__ cand_lens) {
     const int id = blockIdx.x * 256 + threadIdx.x;
     if (id >= B * t.n) return;
     const int b = id / t.n, c = id % t.n;
-    const int T = t.off[c + 1] - t.off[c] + 1;
+    int T = t.off[c + 1] - t.off[c] + 1;
+    if (RAGGED) T = min(max(cand_lens[id], 1), T);
     const float* src = ce + (int64_t)b * (t.off[t.n] + t.n) + t.off[c] + c;
     float s = 0.0f;
     for (int j = 0; j < T; ++j) s += src[j];
@@ -303,54 +338,85 @@ bool cands_ok(const ScoreCands& t) {
 }  // namespace
 
 hipError_t score_prepare() {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(llm_score_attn_kernel<false>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_lds_bytes(SCORE_MAX_TAIL));
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(llm_score_attn_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)attn_lds_bytes(SCORE_MAX_TAIL));
+    const void* kernels[4] = {reinterpret_cast<const void*>(llm_score_attn_kernel<false, false>),
+                              reinterpret_cast<const void*>(llm_score_attn_kernel<true, false>),
+                              reinterpret_cast<const void*>(llm_score_attn_kernel<false, true>),
+                              reinterpret_cast<const void*>(llm_score_attn_kernel<true, true>)};
+    for (const void* k : kernels) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_lds_bytes(SCORE_MAX_TAIL));
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t launch_score_embed(const long long* cand_tokens, const ScoreCands& t, int B, const half_t* table, int vocab, int hidden,
-                              half_t* h, hipStream_t stream) {
+                              half_t* h, hipStream_t stream, bool per_row) {
     if (!cands_ok(t) || t.off[t.n] < 1 || B < 1 || hidden < 8 || hidden % 8 || !cand_tokens || !table || !h) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(llm_score_embed_kernel, dim3((unsigned)(B * t.off[t.n])), dim3(256), 0, stream, cand_tokens, t, table, vocab, hidden, h);
+    if (per_row)
+        hipLaunchKernelGGL(llm_score_embed_kernel<true>, dim3((unsigned)(B * t.off[t.n])), dim3(256), 0, stream, cand_tokens, t, table, vocab,
+                           hidden, h);
+    else
+        hipLaunchKernelGGL(llm_score_embed_kernel<false>, dim3((unsigned)(B * t.off[t.n])), dim3(256), 0, stream, cand_tokens, t, table, vocab,
+                           hidden, h);
     return hipGetLastError();
 }
 
+template <bool GROUPED, bool RAGGED>
+static void score_attn_launch(const half_t* qkv, const ScoreCands& t, int B, int L, int hidden, int heads, int kv_heads, const half_t* Kc,
+                              const half_t* Vc, int64_t len_stride, const half_t* rope, half_t* out, const int32_t* starts, hipStream_t stream) {
+    hipLaunchKernelGGL((llm_score_attn_kernel<GROUPED, RAGGED>), dim3((unsigned)(B * heads)), dim3(256), attn_lds_bytes(t.off[t.n]), stream, qkv,
+                       t, L, hidden, heads, Kc, Vc, len_stride, rope, out, kv_heads, starts);
+}
+
 hipError_t launch_score_attention(const half_t* qkv, const ScoreCands& t, int B, int L, int hidden, int heads, int kv_heads, const half_t* Kc,
-                                  const half_t* Vc, int64_t len_stride, const half_t* rope, half_t* out, hipStream_t stream) {
+                                  const half_t* Vc, int64_t len_stride, const half_t* rope, half_t* out, hipStream_t stream,
+                                  const int32_t* starts) {
     if (!cands_ok(t) || t.off[t.n] < 1 || B < 1 || L < 1 || L > len_stride || hidden != heads * HD || kv_heads < 1 || kv_heads > heads ||
         heads % kv_heads || !qkv || !Kc || !Vc || !rope || !out)
         return hipErrorInvalidValue;
-    if (kv_heads != heads)
-        hipLaunchKernelGGL(llm_score_attn_kernel<true>, dim3((unsigned)(B * heads)), dim3(256), attn_lds_bytes(t.off[t.n]), stream, qkv, t, L,
-                           hidden, heads, Kc, Vc, len_stride, rope, out, kv_heads);
+    const bool grouped = kv_heads != heads;
+    if (grouped && starts)
+        score_attn_launch<true, true>(qkv, t, B, L, hidden, heads, kv_heads, Kc, Vc, len_stride, rope, out, starts, stream);
+    else if (grouped)
+        score_attn_launch<true, false>(qkv, t, B, L, hidden, heads, kv_heads, Kc, Vc, len_stride, rope, out, nullptr, stream);
+    else if (starts)
+        score_attn_launch<false, true>(qkv, t, B, L, hidden, heads, heads, Kc, Vc, len_stride, rope, out, starts, stream);
     else
-        hipLaunchKernelGGL(llm_score_attn_kernel<false>, dim3((unsigned)(B * heads)), dim3(256), attn_lds_bytes(t.off[t.n]), stream, qkv, t, L,
-                           hidden, heads, Kc, Vc, len_stride, rope, out, heads);
+        score_attn_launch<false, false>(qkv, t, B, L, hidden, heads, heads, Kc, Vc, len_stride, rope, out, nullptr, stream);
     return hipGetLastError();
 }
 
 hipError_t launch_score_ce_first(const float* first_logits, int vocab, const long long* cand_tokens, const ScoreCands& t, int B,
-                                 float smoothing, float* ce, hipStream_t stream) {
+                                 float smoothing, float* ce, hipStream_t stream, const int32_t* row_lens) {
     if (!cands_ok(t) || B < 1 || vocab < 8 || vocab % 8 || !first_logits || !cand_tokens || !ce) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((llm_score_ce_kernel<float, true>), dim3((unsigned)(B * t.n)), dim3(256), 0, stream, first_logits, vocab, cand_tokens,
-                       t, (int64_t)0, smoothing, ce);
+    if (row_lens)
+        hipLaunchKernelGGL((llm_score_ce_kernel<float, true, true>), dim3((unsigned)(B * t.n)), dim3(256), 0, stream, first_logits, vocab,
+                           cand_tokens, t, (int64_t)0, smoothing, ce, row_lens);
+    else
+        hipLaunchKernelGGL((llm_score_ce_kernel<float, true, false>), dim3((unsigned)(B * t.n)), dim3(256), 0, stream, first_logits, vocab,
+                           cand_tokens, t, (int64_t)0, smoothing, ce, row_lens);
     return hipGetLastError();
 }
 
 hipError_t launch_score_ce_tail(const half_t* logits, int vocab, const long long* cand_tokens, const ScoreCands& t, int64_t row0,
-                                int64_t rows, float smoothing, float* ce, hipStream_t stream) {
+                                int64_t rows, float smoothing, float* ce, hipStream_t stream, const int32_t* row_lens) {
     if (!cands_ok(t) || t.off[t.n] < 1 || rows < 1 || row0 < 0 || vocab < 8 || vocab % 8 || !logits || !cand_tokens || !ce)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL((llm_score_ce_kernel<half_t, false>), dim3((unsigned)rows), dim3(256), 0, stream, logits, vocab, cand_tokens, t, row0,
-                       smoothing, ce);
+    if (row_lens)
+        hipLaunchKernelGGL((llm_score_ce_kernel<half_t, false, true>), dim3((unsigned)rows), dim3(256), 0, stream, logits, vocab, cand_tokens, t,
+                           row0, smoothing, ce, row_lens);
+    else
+        hipLaunchKernelGGL((llm_score_ce_kernel<half_t, false, false>), dim3((unsigned)rows), dim3(256), 0, stream, logits, vocab, cand_tokens, t,
+                           row0, smoothing, ce, row_lens);
     return hipGetLastError();
 }
 
-hipError_t launch_score_sum(const float* ce, const ScoreCands& t, int B, float* out, hipStream_t stream) {
+hipError_t launch_score_sum(const float* ce, const ScoreCands& t, int B, float* out, hipStream_t stream, const int32_t* row_lens) {
     if (!cands_ok(t) || B < 1 || !ce || !out) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(llm_score_sum_kernel, dim3((unsigned)((B * t.n + 255) / 256)), dim3(256), 0, stream, ce, t, B, out);
+    if (row_lens)
+        hipLaunchKernelGGL(llm_score_sum_kernel<true>, dim3((unsigned)((B * t.n + 255) / 256)), dim3(256), 0, stream, ce, t, B, out, row_lens);
+    else
+        hipLaunchKernelGGL(llm_score_sum_kernel<false>, dim3((unsigned)((B * t.n + 255) / 256)), dim3(256), 0, stream, ce, t, B, out, row_lens);
     return hipGetLastError();
 }
 

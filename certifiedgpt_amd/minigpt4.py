@@ -116,6 +116,32 @@ def left_pad_embeds(batch_embs, bucket=None):
     return embs, attn_mask, starts
 
 
+def pack_row_candidates(cand_tokens):
+    """Per-row candidates for the native scoring pass (cgpt_llm_score_ragged): `cand_tokens[c][b]` = the token ids (a sequence of
+    ints or a 1-D tensor, at least one) of candidate c for row b -> (table [B, C, Tmax] int64 with zeros behind each real length,
+    lens [B, C] int32 = the real lengths, T = [T_c] = the longest length of candidate c over the rows (a list of ints), S = the
+    tail slots per row, sum of T_c - 1: a one-token candidate owns none).  Pure CPU arithmetic; the engine's limits (S <= 64,
+    C <= 64) are the caller's to compare against.  A candidate without a token, or rows that disagree in number, are a ValueError."""
+    if not cand_tokens:
+        raise ValueError("pack_row_candidates: no candidate")
+    rows = [[[int(v) for v in (ids.tolist() if hasattr(ids, "tolist") else ids)] for ids in cand] for cand in cand_tokens]
+    B = len(rows[0])
+    if B < 1 or any(len(cand) != B for cand in rows):
+        raise ValueError("pack_row_candidates: cand_tokens[c][b] needs one token list per candidate and row, at least one row")
+    for c, cand in enumerate(rows):
+        for b, ids in enumerate(cand):
+            if not ids:
+                raise ValueError(f"pack_row_candidates: candidate {c} of row {b} has no token")
+    T = [max(len(ids) for ids in cand) for cand in rows]
+    table = torch.zeros((B, len(rows), max(T)), dtype=torch.long)
+    lens = torch.empty((B, len(rows)), dtype=torch.int32)
+    for c, cand in enumerate(rows):
+        for b, ids in enumerate(cand):
+            table[b, c, :len(ids)] = torch.tensor(ids, dtype=torch.long)
+            lens[b, c] = len(ids)
+    return table, lens, T, sum(t - 1 for t in T)
+
+
 def greedy_decode_parity(hf_tokens, hf_scores, tokens, eps):
     """Compare a greedy decode `tokens` [B, n] with HF `generate`'s `hf_tokens` [B, <= n] row by row, given HF's per-step processed
     scores `hf_scores` [B, steps, V] (fp32).  Two greedy decoders of the SAME fp16 model can only part ways at a step where HF's own
@@ -641,27 +667,40 @@ class _HipDecoder:
 
     MAX_CANDS, MAX_TAIL = 64, 64                                       # SCORE_MAX_CANDS, SCORE_MAX_TAIL (csrc/llm.h)
 
-    def score(self, first_logits, prompt_len, cand_tokens, cand_lens, label_smoothing, k_bufs, v_bufs):
+    def score(self, first_logits, prompt_len, cand_tokens, cand_lens, label_smoothing, k_bufs, v_bufs, starts=None, row_lens=None):
         """Every candidate on the prompt cache a prefill left (cgpt_llm_score): first_logits [B, vocab] fp32 = that prefill's result,
         cand_tokens [C, Tmax] int64 on the device, cand_lens = the C token counts (host) -> [B, C] fp32, the SUM over each
         candidate's tokens of the label-smoothed cross-entropy.  Reads cache rows 0 .. prompt_len-1 and writes none.  The workspace is
-        reserved here (outside any capture), for `max_batch` rows of this call's tail rows."""
+        reserved here (outside any capture), for `max_batch` rows of this call's tail rows.
+        starts and row_lens (both, or both None: the plain entry) -- per-row prompts and candidates (cgpt_llm_score_ragged): starts
+        [B] int32 = the ragged prefill's left padding, `prompt_len` the padded length; cand_tokens [B, C, Tmax], row_lens [B, C] int32 on
+        the device = each row's real length of each candidate, cand_lens = the longest length of each candidate over the rows
+        (`pack_row_candidates`).  Reads cache rows starts[b] .. prompt_len-1 only; sums each row's own tokens."""
         C = self._C
         B, V = first_logits.shape
-        n, tmax = cand_tokens.shape
+        assert (starts is None) == (row_lens is None), "starts and row_lens travel together"
+        n, tmax = cand_tokens.shape[-2:]
         lens = [int(t) for t in cand_lens]
         assert (first_logits.dtype == torch.float32 and first_logits.device == self.device and first_logits.is_contiguous()
                 and V == self.vocab and 1 <= B <= self.max_batch)
         assert (cand_tokens.dtype == torch.int64 and cand_tokens.device == self.device and cand_tokens.is_contiguous()
-                and len(lens) == n)
+                and len(lens) == n and tuple(cand_tokens.shape) == ((n, tmax) if starts is None else (B, n, tmax)))
+        if row_lens is not None:
+            assert (row_lens.dtype == torch.int32 and row_lens.device == self.device and row_lens.is_contiguous()
+                    and tuple(row_lens.shape) == (B, n)), (tuple(row_lens.shape), row_lens.dtype, row_lens.device)
         kp, vp, stride = self._cache_tables(k_bufs, v_bufs, B, int(prompt_len))
         if not torch.cuda.is_current_stream_capturing():
             self._lib_mod.check(self.L.cgpt_llm_score_reserve(self.handle, self.max_batch, max(1, sum(t - 1 for t in lens))))
         out = torch.empty((B, n), dtype=torch.float32, device=self.device)
         st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._lib_mod.check(self.L.cgpt_llm_score(self.handle, C.c_void_p(first_logits.data_ptr()), B, int(prompt_len),
-                                                  C.c_void_p(cand_tokens.data_ptr()), (C.c_int32 * n)(*lens), n, int(tmax),
-                                                  float(label_smoothing), kp, vp, stride, C.c_void_p(out.data_ptr()), st))
+        tail = ((C.c_int32 * n)(*lens), n, int(tmax), float(label_smoothing), kp, vp, stride, C.c_void_p(out.data_ptr()), st)
+        if starts is None:
+            self._lib_mod.check(self.L.cgpt_llm_score(self.handle, C.c_void_p(first_logits.data_ptr()), B, int(prompt_len),
+                                                      C.c_void_p(cand_tokens.data_ptr()), *tail))
+        else:
+            self._lib_mod.check(self.L.cgpt_llm_score_ragged(self.handle, C.c_void_p(first_logits.data_ptr()), B, int(prompt_len),
+                                                             self._starts_ptr(starts, B), C.c_void_p(cand_tokens.data_ptr()),
+                                                             C.c_void_p(row_lens.data_ptr()), *tail))
         return out
 
 
@@ -773,7 +812,15 @@ class MiniGPT4Classifier:
         #   prompt keys + fused label-smoothed cross-entropy); counted in decode_stats["hip_scores"].  Taken when the call is on the
         #   device, every row shares one text and every row gets the same candidate list (the smoothing case); any other call takes the
         #   "hf" path and is counted in decode_stats["hf_score_fallbacks"] -- the policy ragged = "hf" has for `generate`.  Works with
-        #   weights = "int8"; prompt_bucket does not apply (left-padded scoring does not exist).  Parity: tests/test_gpu_llm_score.py.
+        #   weights = "int8".  Parity: tests/test_gpu_llm_score.py.
+        #   With ragged = "hip" a call whose rows carry different texts or different candidates (`answers[c][b]`, the reference's
+        #   `multi_select` interface), or any call under prompt_bucket, stays on the engine too: the prompts are left-padded as for
+        #   `generate`, prefilled by cgpt_llm_prefill_ragged and scored by cgpt_llm_score_ragged on a per-row candidate table
+        #   (`pack_row_candidates`); counted in decode_stats["hip_ragged_scores"].  A padded row's sums are bit for bit those of the
+        #   row scored alone (tests/test_gpu_llm_score_ragged.py); candidate c is divided by (longest prompt + longest answer c - 1),
+        #   the reference's right-padded length.  Still the "hf" path, counted as a fallback: off the device, beyond the engine's
+        #   limits (rows, 64 candidates, 64 tail rows, max_len), an answer token equal to the pad id.  With ragged = "hf" nothing
+        #   changes: per-row calls take the model's forward.
         # classify = "multi_select": `__call__`, `sample_counts` and `sample_counts_pair` score `candidates` (default: the label map's
         #   answers, in class-id order; at least 2, at most num_classes - 1) instead of generating: logits [B, num_classes] hold -loss in
         #   column i for candidate i and -inf in column `other_id`, so every row votes for a known class.  classify = "generate"
@@ -869,6 +916,7 @@ class MiniGPT4Classifier:
                              "hip_prefills": 0,                   # native prefills enqueued (prefill = "hip"), counted alike
                              "hf_score_forwards": 0,              # model forwards of score = "hf": one per candidate and call
                              "hip_scores": 0,                     # native scoring passes (score = "hip"): one per call
+                             "hip_ragged_scores": 0,              # native per-row scoring passes (score = "hip", ragged = "hip")
                              "hf_score_fallbacks": 0,             # score = "hip" calls that took the "hf" path (see __init__)
                              # bytes the native engine holds for weights, scales and scratch (None without one)
                              "weight_bytes": self._hip.weight_bytes if self._hip is not None else None}
@@ -1259,12 +1307,15 @@ class MiniGPT4Classifier:
 
     def _native_losses(self, img_embeds, prompts, answers):
         """score="hip": [B, C] losses from one native prefill and one native scoring pass, or None where the call is not the native
-        path's (off the device, per-row texts or candidates, more rows / candidates / tokens than the engine takes, an answer token
-        equal to the pad id, which the reference masks out)."""
+        path's (off the device, per-row texts or candidates without ragged="hip", more rows / candidates / tokens than the engine
+        takes, an answer token equal to the pad id, which the reference masks out)."""
         B = img_embeds.shape[0]
         hip = self._hip
-        if not img_embeds.is_cuda or len(set(prompts)) != 1 or any(len(set(a)) != 1 for a in answers):
+        if not img_embeds.is_cuda:
             return None
+        shared = len(set(prompts)) == 1 and all(len(set(a)) == 1 for a in answers)
+        if not shared or self.prompt_bucket:
+            return self._native_losses_ragged(img_embeds, prompts, answers) if self.ragged == "hip" else None
         toks = [self._answer_tokens(a[0]) for a in answers]
         lens = [int(t.numel()) for t in toks]
         pad_id = getattr(self.llama_tokenizer, "pad_token_id", None)
@@ -1287,6 +1338,47 @@ class MiniGPT4Classifier:
             self.last_act_stats()
         # the reference runs one forward per candidate, so each candidate's divisor is its own sequence length - 1
         return sums / torch.tensor([float(L + t - 1) for t in lens], device=sums.device)
+
+    def _native_losses_ragged(self, img_embeds, prompts, answers):
+        """ragged="hip", score="hip": per-row prompts and per-row candidates on the engine -- the prompts left-padded as the reference
+        pads them for `generate` (prompt_bucket honoured), one ragged prefill, one ragged scoring pass (cgpt_llm_score_ragged) on the
+        table `pack_row_candidates` builds.  None under `_native_losses`' rules."""
+        B = img_embeds.shape[0]
+        hip = self._hip
+        texts = {a: self._answer_tokens(a) for cand in answers for a in set(cand)}     # every distinct answer tokenised once
+        pad_id = getattr(self.llama_tokenizer, "pad_token_id", None)
+        if pad_id is not None and any(bool((t == pad_id).any()) for t in texts.values()):
+            return None
+        table, row_lens, T, S = pack_row_candidates([[texts[a] for a in cand] for cand in answers])
+        groups = {}                                                    # distinct prompt -> its rows, in first-seen order
+        for b, p in enumerate(prompts):
+            groups.setdefault(p, []).append(b)
+        order = [b for rows in groups.values() for b in rows]
+        batch_embs = [self._prompt_embeds(p, img_embeds[rows]) for p, rows in groups.items()]
+        Lmax = max(int(e.shape[1]) for e in batch_embs)                # the longest prompt, bos included: the reference's padded length
+        Lpad = -(-Lmax // self.prompt_bucket) * self.prompt_bucket if self.prompt_bucket else Lmax
+        if B > self.max_batch or len(T) > hip.MAX_CANDS or S > hip.MAX_TAIL or Lpad + max(T) - 1 > hip.MAX_LEN:
+            return None
+        embs, _, starts = left_pad_embeds(batch_embs, self.prompt_bucket)
+        if order != list(range(B)):                                    # left_pad_embeds stacks the groups: back to the call's row order
+            inv = torch.empty(B, dtype=torch.long)
+            inv[torch.tensor(order)] = torch.arange(B)
+            inv = inv.to(embs.device)
+            embs, starts = embs[inv].contiguous(), starts[inv].contiguous()
+        L = int(embs.shape[1])
+        shape = (B, hip.kv_heads, L, 128)
+        k_bufs = [embs.new_empty(shape) for _ in range(hip.layers)]
+        v_bufs = [embs.new_empty(shape) for _ in range(hip.layers)]
+        first = hip.prefill(embs, k_bufs, v_bufs, starts=starts)
+        sums = hip.score(first, L, table.to(embs.device), T, self.label_smoothing, k_bufs, v_bufs, starts=starts,
+                         row_lens=row_lens.to(embs.device))
+        self.decode_stats["hip_prefills"] += 1
+        self.decode_stats["hip_ragged_scores"] += 1
+        if self.activations == "int8":                                  # the losses are read next: the same sync
+            self.last_act_stats()
+        # the reference pads prompts and answers on the right and runs one forward per candidate: candidate c's divisor is the longest
+        # prompt + the longest answer c over the rows - 1, for every row (answer_losses_from_embeds' docstring)
+        return sums / torch.tensor([float(Lmax + t - 1) for t in T], device=sums.device)
 
     @torch.no_grad()
     def multi_select(self, images, texts, answers, num_cand=None):

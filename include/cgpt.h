@@ -522,6 +522,35 @@ cgpt_status cgpt_llm_score(cgpt_llm_handle h, const float* first_logits_dev, int
                            const int64_t* cand_tokens_dev, const int32_t* cand_lens_host, int32_t C, int32_t Tmax, float label_smoothing,
                            void* const* k_ptrs_host, void* const* v_ptrs_host, int64_t kv_len_stride, float* out_dev, void* stream);
 
+/* ---- Answer scoring with per-row prompts and per-row candidates: cgpt_llm_score on left-padded rows ----
+ * The reference's `multi_select` gives every row its own question and its own candidate answers (`answers[c][b]`).  This entry scores
+ * them on the cache cgpt_llm_prefill_ragged left: prompt_len is the PADDED length L and starts_dev the DEVICE array of B int32 that
+ * prefill saw -- row b has start[b] pad positions and len[b] = L - start[b] >= 1 real ones.  The kernels clamp start[b] into
+ * 0 .. L-1 (the host cannot check device contents without a sync) and work in row-relative coordinates: the row's K / V pointers moved
+ * by start[b], the walk over the prompt's keys on len[b] keys from the row's first real one, tail row j rotated at len[b] + j.
+ * cand_tokens_dev: DEVICE int64 [B, C, Tmax], row (b, c) holding row b's tokens of candidate c.  cand_lens_dev: DEVICE int32 [B, C],
+ * row b's real length of candidate c.  cand_lens_host: HOST int32 [C], read when the call enqueues: T_c = the LONGEST length of
+ * candidate c over the rows.  The T_c define the tail rows, which are the same for every row (sum over c of T_c - 1, at most 64);
+ * a device length is clamped into 1 .. T_c.  A row whose candidate is shorter than T_c still runs its surplus tail rows: they read
+ * the table entries behind the real length like any other token (an id outside 0 .. vocab-1 reads as 0; keep them finite ids, e.g.
+ * 0), nothing of them reaches a result: a token j >= the row's length is left out of out_dev[b, c].
+ * out_dev[b, c] (fp32 [B, C]): the SUM over row b's own tokens of candidate c, the law of cgpt_llm_score.  It is bit for bit what
+ * cgpt_llm_prefill + cgpt_llm_score give for row b run alone and unpadded with its own tokens and lengths, and depends on nothing but
+ * that row's cache rows start[b] .., its tokens of that candidate and its length -- not on B, C, L, the padding, the other rows'
+ * candidates, or T_c beyond the row's own length; fixed summation orders, no atomics.
+ * Reads cache rows start[b] .. L-1 of row b of k_ptrs_host[l] / v_ptrs_host[l]; rows below start[b] are NEVER read, and NO cache
+ * row is written.  Layouts as cgpt_llm_score ([B, kv_heads, kv_len_stride, 128] on a grouped_kv = 1 handle); works with
+ * CGPT_LLM_W_INT8 and act_format = 1 like it.
+ * starts_dev, cand_tokens_dev and cand_lens_dev are read when the kernels RUN, not when the call enqueues.
+ * Same contracts as cgpt_llm_score (enqueues only: no host sync, no allocation, no host->device copy; the workspace is
+ * cgpt_llm_score_reserve's, for B x sum (T_c - 1) tail rows; its CGPT_ERR_INVALID / CGPT_ERR_STATE rules, all checked before the
+ * first launch), plus CGPT_ERR_INVALID for a null starts_dev or cand_lens_dev. */
+cgpt_status cgpt_llm_score_ragged(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len,
+                                  const int32_t* starts_dev, const int64_t* cand_tokens_dev /* [B, C, Tmax] */,
+                                  const int32_t* cand_lens_dev /* [B, C] */, const int32_t* cand_lens_host /* [C] = T_c */,
+                                  int32_t C, int32_t Tmax, float label_smoothing, void* const* k_ptrs_host,
+                                  void* const* v_ptrs_host, int64_t kv_len_stride, float* out_dev, void* stream);
+
 /* ---- int8 activations: the LLM.int8() forward on the native engine (W8A8 with a per-row outlier split) ----
  * Replaces: the `load_in_8bit=True` decoder the reference's configs select (`low_resource: true`, base_model.py:196-213): row-wise
  * int8 weights, row-wise int8 activations, int32 accumulation, outlier features above a threshold multiplied in higher precision.
