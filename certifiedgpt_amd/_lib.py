@@ -121,6 +121,7 @@ SIGNATURES = {
     "cgpt_llm_greedy_ragged": (_I32, [_P, _P, _I32, _I32, _P, _I32, _I32, _P, _I32, _I64, _P, _P, _I64, _P, _P, _P]),
     "cgpt_llm_set_early_stop": (_I32, [_P, _I32]),
     "cgpt_llm_live_steps": (_I32, [_P, C.POINTER(_I32), _P]),
+    "cgpt_llm_set_stop_sequences": (_I32, [_P, C.POINTER(_I64), C.POINTER(_I32), _I32]),
     "cgpt_llm_score_reserve": (_I32, [_P, _I32, _I32]),
     "cgpt_llm_act_stats": (_I32, [_P, C.POINTER(_I64)]),
     "cgpt_llm_linear_i8": (_I32, [_P, _P, _P, _I64, _I64, _I64, _F, _I32, _I32, _P, _P, _I64, _P, _I64, _P]),

@@ -25,6 +25,9 @@ Config (a plain dict or any mapping; the reference's YAMLs define no smoothing k
             #          also: classify: "generate" | "multi_select" (rank the answers by their teacher-forced loss instead of generating:
             #          every noisy copy votes for one of `answers`, never for "other"), score: "hf" | "hip" (who computes those losses;
             #          "hip" needs decode and prefill "hip"), end_sym: "\\n" (appended to every answer; the reference's VQA configs: "###")
+            #          also: stop_words_ids: null | [[ids], ...] (any decode: a row of the greedy decode finishes when its answer ends in
+            #          one of up to 8 token-id sequences of 1..8 tokens, as on an EOS; with early_stop such rows count as finished),
+            #          stop_text: null | "###" (every decoded answer is cut at its first occurrence)
             mode: vit_head | encode_img, weights: <path to a torch state_dict saved with torch.save> | null, dims: {...},
             partial_weights: false}   # true: load what the checkpoint has on top of the synthetic initialisation
     data:  {num_images: 10, seed: 1234}      # synthetic CLIP-normalised images unless `dataset` is passed to the agent
@@ -206,7 +209,9 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
                   activations with a per-row outlier split at int8_threshold (6.0), at most outlier_cap (64) outliers per row; needs
                   decode and prefill "hip" and weights "int8"); classify: "generate" | "multi_select" (the base classifier ranks `answers` by their answer loss,
                   MiniGPTBase.multi_select, instead of generating), score: "hf" | "hip" (the model's own forward per candidate | one
-                  native prefill + the native scoring pass; needs decode and prefill "hip"), end_sym: "\\n" (appended to every answer)"""
+                  native prefill + the native scoring pass; needs decode and prefill "hip"), end_sym: "\\n" (appended to every answer);
+                  stop_words_ids: None | [[ids], ...] (per-row stop sequences of the greedy decode, any decode), stop_text: None | str
+                  (every decoded answer is cut at its first occurrence: "###" for checkpoints tuned with end_sym "###")"""
     from ..minigpt4 import MiniGPT4Classifier
     from .label_adapter import AnswerLabelMap
     if llama_model is None:
@@ -239,7 +244,8 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
                               early_stop=gen_cfg.get("early_stop", False), grouped_kv=gen_cfg.get("grouped_kv", False),
                               classify=gen_cfg.get("classify", "generate"), score=gen_cfg.get("score", "hf"),
                               end_sym=gen_cfg.get("end_sym", "\n"), activations=gen_cfg.get("activations", "fp16"),
-                              int8_threshold=gen_cfg.get("int8_threshold", 6.0), outlier_cap=gen_cfg.get("outlier_cap", 64))
+                              int8_threshold=gen_cfg.get("int8_threshold", 6.0), outlier_cap=gen_cfg.get("outlier_cap", 64),
+                              stop_words_ids=gen_cfg.get("stop_words_ids"), stop_text=gen_cfg.get("stop_text"))
 
 
 def build_classifier(model_cfg, num_classes, max_batch, device_index, tokenizer=None, llama_model=None):

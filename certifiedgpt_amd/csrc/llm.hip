@@ -28,6 +28,7 @@
 
 #include <set>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/cgpt.h"
@@ -444,6 +445,12 @@ __global__ __launch_bounds__(256) void llm_dequant_kernel(const signed char* __r
 }
 
 struct EosIds { long long id[MAX_EOS]; int n; };
+// Stop sequences (cgpt_llm_set_stop_sequences), by value like EosIds: sequence s is id[s][0 .. len[s]).  `col` is the
+// select's index i, which the greedy entry fills in per launch.  A select without them takes the empty NoStop.
+constexpr int MAX_STOP = 8, MAX_STOP_LEN = 8;
+struct StopSeqs { long long id[MAX_STOP][MAX_STOP_LEN]; int len[MAX_STOP]; int n; int col; };
+struct NoStop {};
+template <bool STOP> using StopArg = std::conditional_t<STOP, StopSeqs, NoStop>;
 
 // Greedy bookkeeping of one step, one workgroup per row (greedy_tokens in minigpt4.py): EOS columns read as -inf while
 // `mask_eos` (the first min_new_tokens steps), first-max arg-max, pad once the row has produced an EOS.
@@ -452,11 +459,16 @@ struct EosIds { long long id[MAX_EOS]; int n; };
 // GUARD (early stop): a select other than the first that reads *live == 0 -- every row has produced an EOS -- is a dead select: no
 // vocabulary scan, no logits copy, `unfinished` left as it is (all zeros); it writes the pad id, which is what the scan would have
 // ended in.  The first select never reads `live` (it holds the previous call's value until llm_live_kernel has run).
-template <bool GUARD>
+// STOP (stop sequences): a still-unfinished row also finishes when its tokens up to and including this one end in one of the
+// sequences.  The row's earlier tokens are read back from tokens_out (columns col - 1, col - 2, ..., written by the earlier selects
+// of the call on the same stream); a sequence longer than col + 1 is skipped, so nothing left of column 0 -- the previous row's last
+// tokens -- is ever read.  STOP = false is the kernel as it was.
+template <bool GUARD, bool STOP = false>
 __global__ __launch_bounds__(256) void llm_select_kernel(const float* src, int64_t lds, float* dst, int64_t ldd, int vocab,
                                                          int mask_eos, EosIds eos, long long pad, int first, int* __restrict__ unfinished,
                                                          long long* __restrict__ tokens_out, int64_t ld_tokens,
-                                                         long long* __restrict__ next_tok, const int* __restrict__ live) {
+                                                         long long* __restrict__ next_tok, const int* __restrict__ live,
+                                                         StopArg<STOP> stop) {
     __shared__ float bv[4];
     __shared__ int bi[4];
     const int row = blockIdx.x;
@@ -496,6 +508,21 @@ __global__ __launch_bounds__(256) void llm_select_kernel(const float* src, int64
         const long long tok = u ? (long long)idx : pad;
         for (int e = 0; e < eos.n; ++e)
             if (tok == eos.id[e]) u = 0;
+        if constexpr (STOP) {
+            if (u) {
+                const long long* t = tokens_out + (int64_t)row * ld_tokens;      // column `col` of this row; t[-j] is column col - j
+#pragma unroll
+                for (int q = 0; q < MAX_STOP; ++q) {
+                    const int len = q < stop.n ? stop.len[q] : 0;
+                    if (len < 1 || len > stop.col + 1) continue;
+                    bool match = true;
+#pragma unroll
+                    for (int k = 0; k < MAX_STOP_LEN; ++k)                  // element k sits len - 1 - k columns back
+                        if (k < len) match = match && (k == len - 1 ? tok : t[k - (len - 1)]) == stop.id[q][k];
+                    if (match) u = 0;
+                }
+            }
+        }
         unfinished[row] = u;
         tokens_out[(int64_t)row * ld_tokens] = tok;
         next_tok[row] = tok;
@@ -550,6 +577,7 @@ struct cgpt_llm {
     // them: the last call's count (num_new - 1, every step runs) is kept in `off_steps`, and `last_on` says which of the two holds.
     int *live = nullptr, *live_steps = nullptr;
     int early_stop = 0, last_on = 0, off_steps = 0;
+    StopSeqs stop{};                       // cgpt_llm_set_stop_sequences: n = 0 (none) after create; read when a greedy call enqueues
     std::set<std::string> loaded;
     size_t expected = 0;
     std::vector<void*> allocs;
@@ -1104,6 +1132,7 @@ static cgpt_status llm_greedy_entry(const char* who_c, cgpt_llm_handle h, const 
     const int V = h->cfg.vocab;
     const int64_t ld_out = (int64_t)num_new * V;
     const bool early = h->early_stop != 0;                 // read now: a captured call keeps the setting it was captured under
+    StopSeqs stop = h->stop;                               // likewise; `col` is set per select below
     h->last_on = early ? 1 : 0;
     h->off_steps = num_new - 1;
     for (int i = 0; i < num_new; ++i) {
@@ -1115,15 +1144,26 @@ static cgpt_status llm_greedy_entry(const char* who_c, cgpt_llm_handle h, const 
         const int mask = (i < min_new && num_eos > 0) ? 1 : 0;
         float* dst = nullptr;
         if (step_logits_out_dev && (i == 0 || mask)) dst = step_logits_out_dev + (int64_t)i * V;
+        stop.col = i;
         if (early) {
-            hipLaunchKernelGGL(llm_select_kernel<true>, dim3(B), dim3(256), 0, st, src, lds, dst, ld_out, V, mask, eos, (long long)pad_id,
-                               i == 0 ? 1 : 0, h->unfinished, (long long*)tokens_out_dev + i, (int64_t)num_new, h->tok, h->live);
+            if (stop.n > 0)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(llm_select_kernel<true, true>), dim3(B), dim3(256), 0, st, src, lds, dst, ld_out, V, mask,
+                                   eos, (long long)pad_id, i == 0 ? 1 : 0, h->unfinished, (long long*)tokens_out_dev + i, (int64_t)num_new,
+                                   h->tok, h->live, stop);
+            else
+                hipLaunchKernelGGL(llm_select_kernel<true>, dim3(B), dim3(256), 0, st, src, lds, dst, ld_out, V, mask, eos,
+                                   (long long)pad_id, i == 0 ? 1 : 0, h->unfinished, (long long*)tokens_out_dev + i, (int64_t)num_new,
+                                   h->tok, h->live, NoStop{});
             LAUNCHED();
             hipLaunchKernelGGL(llm_live_kernel, dim3(1), dim3(256), 0, st, h->unfinished, B, i == 0 ? 1 : 0, i + 1 < num_new ? 1 : 0,
                                h->live, h->live_steps);
+        } else if (stop.n > 0) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(llm_select_kernel<false, true>), dim3(B), dim3(256), 0, st, src, lds, dst, ld_out, V, mask,
+                               eos, (long long)pad_id, i == 0 ? 1 : 0, h->unfinished, (long long*)tokens_out_dev + i, (int64_t)num_new,
+                               h->tok, nullptr, stop);
         } else {
             hipLaunchKernelGGL(llm_select_kernel<false>, dim3(B), dim3(256), 0, st, src, lds, dst, ld_out, V, mask, eos, (long long)pad_id,
-                               i == 0 ? 1 : 0, h->unfinished, (long long*)tokens_out_dev + i, (int64_t)num_new, h->tok, nullptr);
+                               i == 0 ? 1 : 0, h->unfinished, (long long*)tokens_out_dev + i, (int64_t)num_new, h->tok, nullptr, NoStop{});
         }
         LAUNCHED();
         if (i + 1 == num_new) break;
@@ -1160,6 +1200,31 @@ cgpt_status cgpt_llm_set_early_stop(cgpt_llm_handle h, int32_t on) {
     if (!h) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_set_early_stop: null handle");
     if (on != 0 && on != 1) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_set_early_stop: the value must be 0 or 1");
     h->early_stop = on;
+    return CGPT_OK;
+}
+
+cgpt_status cgpt_llm_set_stop_sequences(cgpt_llm_handle h, const int64_t* ids_host, const int32_t* lens_host, int32_t n) {
+    const std::string who = "cgpt_llm_set_stop_sequences";            // the arrays are checked first: it takes no device to refuse them
+    if (n < 0 || n > MAX_STOP) return cgpt_fail(CGPT_ERR_INVALID, who + ": " + std::to_string(n) + " sequences (0.." + std::to_string(MAX_STOP) + ")");
+    if (n > 0 && (!ids_host || !lens_host)) return cgpt_fail(CGPT_ERR_INVALID, who + ": null ids_host / lens_host with n > 0");
+    StopSeqs t{};
+    int64_t at = 0;
+    for (int q = 0; q < n; ++q) {
+        const int len = lens_host[q];
+        if (len < 1 || len > MAX_STOP_LEN)
+            return cgpt_fail(CGPT_ERR_INVALID, who + ": sequence " + std::to_string(q) + " has " + std::to_string(len) + " tokens (1.." +
+                                                   std::to_string(MAX_STOP_LEN) + ")");
+        for (int j = 0; j < len; ++j) {
+            if (ids_host[at + j] < 0)
+                return cgpt_fail(CGPT_ERR_INVALID, who + ": sequence " + std::to_string(q) + " holds a negative token id");
+            t.id[q][j] = ids_host[at + j];
+        }
+        t.len[q] = len;
+        at += len;
+    }
+    t.n = n;
+    if (!h) return cgpt_fail(CGPT_ERR_INVALID, who + ": null handle");
+    h->stop = t;                                           // complete or not at all: a refused call leaves the handle as it was
     return CGPT_OK;
 }
 

@@ -39,6 +39,91 @@ def clean_answer(text: str) -> str:
     return text.split(r"[/INST]")[-1].strip()
 
 
+MAX_STOP_SEQS, MAX_STOP_LEN = 8, 8                                    # MAX_STOP, MAX_STOP_LEN of csrc/llm.hip
+
+
+def _as_rows(table):
+    return [[int(t) for t in row] for row in (table.tolist() if hasattr(table, "tolist") else table)]
+
+
+def stop_finish_columns(tokens, eos_ids, stop_seqs):
+    """The finishing rule of the greedy decode, stated once: for a [B, n] table of GENERATED tokens (tensor or
+    nested lists) the first column i at which each row finishes -- token i is an EOS id, or tokens i-len+1 .. i equal a stop sequence
+    of length len <= i + 1 (the prompt is embeddings and has no ids, so a longer sequence cannot match at select i).  len(row) for a
+    row that never finishes.  min_length masks EOS logits, as in HF; it never suppresses a match."""
+    eos = set(int(e) for e in (eos_ids.tolist() if hasattr(eos_ids, "tolist") else eos_ids))
+    seqs = [s for s in _as_rows(stop_seqs if stop_seqs is not None else [])]
+    cols = []
+    for row in _as_rows(tokens):
+        first = len(row)
+        for i, t in enumerate(row):
+            if t in eos or any(len(s) <= i + 1 and row[i + 1 - len(s):i + 1] == s for s in seqs):
+                first = i
+                break
+        cols.append(first)
+    return cols
+
+
+def apply_stop_sequences(tokens, eos_ids, stop_seqs, pad):
+    """`tokens` with every column after a row's finishing column (`stop_finish_columns`) replaced by `pad`; the finishing tokens
+    stay, as HF keeps them.  Greedy rows are independent, so this applied to a decode WITHOUT stop sequences is, bit for bit, the
+    decode with them.  A tensor gives a new tensor, nested lists a new list."""
+    cols = stop_finish_columns(tokens, eos_ids, stop_seqs)
+    if hasattr(tokens, "clone"):
+        out = tokens.clone()
+        for b, f in enumerate(cols):
+            out[b, f + 1:] = int(pad)
+        return out
+    return [row[:f + 1] + [int(pad)] * (len(row) - f - 1) for row, f in zip(_as_rows(tokens), cols)]
+
+
+def check_stop_words_ids(stop_words_ids):
+    """The `stop_words_ids` keyword (the reference's name, minigpt_base.py:387) -> a tuple of token-id tuples: a list of token-id
+    lists (or 1-d tensors, as conversation.py builds them), an int entry read as a one-token sequence, as the reference's `[2]` is.
+    None -> ().  ValueError naming the offending entry for more than 8 sequences, a sequence outside 1..8 tokens or a negative id."""
+    if stop_words_ids is None:
+        return ()
+    if isinstance(stop_words_ids, (str, bytes)) or not hasattr(stop_words_ids, "__iter__"):
+        raise ValueError(f"stop_words_ids={stop_words_ids!r}: expected None or a list of token-id lists (a text goes to stop_text)")
+    entries = stop_words_ids.tolist() if hasattr(stop_words_ids, "tolist") else list(stop_words_ids)
+    if len(entries) > MAX_STOP_SEQS:
+        raise ValueError(f"stop_words_ids: {len(entries)} sequences (at most {MAX_STOP_SEQS})")
+    out = []
+    for k, entry in enumerate(entries):
+        entry = entry.tolist() if hasattr(entry, "tolist") else entry
+        ids = [entry] if isinstance(entry, int) and not isinstance(entry, bool) else entry
+        if isinstance(ids, (str, bytes)) or not isinstance(ids, (list, tuple)) or \
+                any(isinstance(t, bool) or not isinstance(t, int) for t in ids):
+            raise ValueError(f"stop_words_ids[{k}]={entry!r}: expected a list of token ids or one token id")
+        if not 1 <= len(ids) <= MAX_STOP_LEN:
+            raise ValueError(f"stop_words_ids[{k}]={entry!r}: {len(ids)} tokens (a sequence has 1..{MAX_STOP_LEN})")
+        if min(ids) < 0:
+            raise ValueError(f"stop_words_ids[{k}]={entry!r}: a negative token id")
+        out.append(tuple(ids))
+    return tuple(out)
+
+
+def stop_sequences_criteria(stop_seqs):
+    """The rule as a transformers StoppingCriteria for the HF path: a bool [B] per step, True for the rows whose generated tokens end
+    in a sequence; `generate` marks such rows finished and pads them, as it does for an EOS.  With `inputs_embeds` and no input ids
+    the ids `generate` hands over are the generated tokens only, which is what the rule compares."""
+    from transformers import StoppingCriteria, StoppingCriteriaList
+
+    class StopSequences(StoppingCriteria):
+        def __init__(self, seqs):
+            self.seqs = [list(s) for s in seqs]
+
+        def __call__(self, input_ids, scores, **kwargs):
+            done = torch.zeros(input_ids.shape[0], dtype=torch.bool, device=input_ids.device)
+            for s in self.seqs:
+                if len(s) <= input_ids.shape[1]:
+                    want = torch.tensor(s, dtype=input_ids.dtype, device=input_ids.device)
+                    done = done | (input_ids[:, input_ids.shape[1] - len(s):] == want).all(dim=1)
+            return done
+
+    return StoppingCriteriaList([StopSequences(stop_seqs)])
+
+
 class WordHashTokenizer:
     """Stand-in for LlamaTokenizer where no tokenizer model file exists (the container has no Vicuna directory and nothing is
     ever downloaded): words map to ids by a stable hash into [3, vocab_size), id k decodes to the word "w<k>" (token-id strings
@@ -480,6 +565,7 @@ class _HipDecoder:
         self._act_stats = None
         self.early_stop = bool(early_stop)
         self._greedy_ran = False                                       # live_steps has nothing to report before the first `greedy`
+        self.stop_sequences = ()                                       # none is the handle's state at create
         self.grouped_kv = bool(grouped_kv)
         bad = hip_decode_unsupported(llama_model, max_batch, grouped_kv=self.grouped_kv, activations=activations)
         if bad:
@@ -653,6 +739,17 @@ class _HipDecoder:
         self._lib_mod.check(self.L.cgpt_llm_set_early_stop(self.handle, int(bool(on))))
         self.early_stop = bool(on)
 
+    def set_stop_sequences(self, seqs):
+        """cgpt_llm_set_stop_sequences: token-id sequences (`check_stop_words_ids`; () or None clears them) at which a row of the next
+        `greedy` finishes besides its EOS ids; read when it enqueues, a captured call keeps what it was captured under."""
+        C = self._C
+        seqs = check_stop_words_ids(seqs)
+        flat = [t for s in seqs for t in s]
+        ids = (C.c_int64 * max(1, len(flat)))(*flat)
+        lens = (C.c_int32 * max(1, len(seqs)))(*[len(s) for s in seqs])
+        self._lib_mod.check(self.L.cgpt_llm_set_stop_sequences(self.handle, ids, lens, len(seqs)))
+        self.stop_sequences = seqs
+
     def live_steps(self):
         """cgpt_llm_live_steps after the last `greedy` (or the last replay of a graph that captured it): the token steps that ran.
         Synchronises the CURRENT stream -- the one the call was enqueued or the graph replayed on; RuntimeError when no greedy has
@@ -720,6 +817,8 @@ class MiniGPT4Classifier:
        :param outlier_cap: outliers kept per activation row under activations="int8" (1..1024; more in a row is a RuntimeError)
        :param early_stop: False (default) | True (with decode="hip") -- the native token steps do no work once every row has its EOS
        :param grouped_kv: False (default) | True (with decode="hip") -- the native engine takes a grouped-query decoder; see __init__
+       :param stop_words_ids: None (default) | up to 8 token-id sequences of 1..8 tokens -- a row finishes when its answer ends in one
+       :param stop_text: None (default) | str -- every decoded answer is cut at its first occurrence (the reference's "###")
        :param end_sym: text appended to every candidate answer of `multi_select` ("\n": the reference's default; its VQA configs: "###")
        :param label_smoothing: of the answer loss (0.1: modeling_llama.py:105)
        :param score: "hf" (default) | "hip" -- who computes the answer losses of `multi_select`; see __init__
@@ -736,7 +835,8 @@ class MiniGPT4Classifier:
     def __init__(self, encoder, llama_model, llama_tokenizer, prompt, label_map, max_new_tokens=20, max_batch=None,
                  generate_kwargs=None, decode="hf", prefill_linear="torch", prefill="model", ragged="hf", prompt_bucket=None,
                  weights="fp16", end_sym="\n", label_smoothing=0.1, score="hf", classify="generate", candidates=None,
-                 early_stop=False, grouped_kv=False, activations="fp16", int8_threshold=6.0, outlier_cap=64):
+                 early_stop=False, grouped_kv=False, activations="fp16", int8_threshold=6.0, outlier_cap=64, stop_words_ids=None,
+                 stop_text=None):
         self.encoder = encoder
         self.llama_model = llama_model
         self.llama_tokenizer = llama_tokenizer
@@ -805,6 +905,16 @@ class MiniGPT4Classifier:
         #   the un-repeated heads too), ragged = "hip", prompt_bucket, weights = "int8", early_stop and score = "hip".  Every result is
         #   what the engine gives on the multi-head twin `expand_kv_state_dict(llama_model)` (tests/test_gpu_llm_gqa.py).
         #   grouped_kv = False (default): as before, a grouped-query decoder is a ValueError.
+        # stop_words_ids = [[ids], ...] (any decode): PER-ROW stop sequences of the greedy decode (the reference's
+        #   argument, minigpt_base.py:387-394, whose criterion conversation.py:96-107 fires only when all rows stop at once): a row
+        #   finishes at the first generated token that is an EOS id or completes one of the sequences; the finishing tokens stay and
+        #   pad ids follow, as after an EOS (`stop_finish_columns` is the rule, and every engine gives `apply_stop_sequences` of its
+        #   own decode without them, bit for bit).  decode = "hip": handed to the engine once, here (cgpt_llm_set_stop_sequences: the
+        #   select kernel looks back in its own token table), and a finished row counts for early_stop; decode = "graph": the same
+        #   rule in tensor ops on the loop's step tokens; decode = "hf" and every HF fallback: a StoppingCriteria that answers per row.
+        #   An int entry is a one-token sequence.  None (default): every path is what it was.
+        # stop_text = "###": `_decode_outputs` cuts every decoded text at its first occurrence before `clean_answer`
+        #   (`Chat.answer`'s `split('###')[0]`) -- at the text level because "###" tokenises differently after different words.
         # score = "hf" (default): `multi_select` / `answer_losses_from_embeds` run the model's own forward once per candidate over the
         #   concatenated prompt + answer embeds, as the reference does (works on the CPU); counted in decode_stats["hf_score_forwards"].
         # score = "hip" (with decode = "hip" AND prefill = "hip" only; anything else is a ValueError, never another engine): ONE native
@@ -859,6 +969,9 @@ class MiniGPT4Classifier:
         if early_stop and decode != "hip":
             raise ValueError(f'early_stop=True needs decode="hip" (got decode={decode!r}): only the native token steps can be switched '
                              "off on the device")
+        stops = check_stop_words_ids(stop_words_ids)
+        if stop_text is not None and (not isinstance(stop_text, str) or not stop_text):
+            raise ValueError(f"stop_text={stop_text!r}: expected None or a non-empty str")
         if not isinstance(grouped_kv, bool):
             raise ValueError(f"grouped_kv={grouped_kv!r}: expected False or True")
         if grouped_kv and decode != "hip":
@@ -898,6 +1011,8 @@ class MiniGPT4Classifier:
         self.prefill_linear = prefill_linear
         self.weights = weights
         self.early_stop = early_stop
+        self.stop_words_ids = stops or None                 # the validated tuple of tuples; None when there is none
+        self.stop_text = stop_text
         self.grouped_kv = grouped_kv
         # the keyword reaches the engine only when it is set (as `law` reaches an encoder)
         gqa = {"grouped_kv": True} if grouped_kv else {}
@@ -905,6 +1020,8 @@ class MiniGPT4Classifier:
         if activations == "int8":
             gqa.update(activations="int8", int8_threshold=self.int8_threshold, outlier_cap=self.outlier_cap)
         self._hip = _HipDecoder(llama_model, self.max_batch, weights=weights, early_stop=early_stop, **gqa) if decode == "hip" else None
+        if self._hip is not None and stops:                 # none is the handle's state at create: nothing is called for it
+            self._hip.set_stop_sequences(stops)
         self.routed_linears = (_LinearRoute.install(llama_model)
                                if (decode in ("graph", "hip") and prefill_linear == "cgpt" and prefill == "model") else 0)
         import collections
@@ -1000,7 +1117,10 @@ class MiniGPT4Classifier:
         for output_token in outputs:
             if output_token[0] == 0:
                 output_token = output_token[1:]
-            answers.append(clean_answer(self.llama_tokenizer.decode(output_token, skip_special_tokens=True)))
+            text = self.llama_tokenizer.decode(output_token, skip_special_tokens=True)
+            if self.stop_text is not None:                             # Chat.answer: output_text.split('###')[0]
+                text = text.split(self.stop_text)[0]
+            answers.append(clean_answer(text))
         return answers
 
     # ---- greedy decode without host round trips (decode = "graph")
@@ -1062,6 +1182,10 @@ class MiniGPT4Classifier:
         # never SILENT on min_length: where the call says nothing `generate` applies the checkpoint's own generation_config.min_length,
         # which the greedy loop (min_new_tokens() above) would not see -- the two decode paths of one classifier would then differ
         kw["min_length"] = 0
+        if self.stop_words_ids:                                        # the per-row rule on the HF path (see __init__)
+            from transformers import StoppingCriteriaList
+            kw["stopping_criteria"] = StoppingCriteriaList(list(kw.get("stopping_criteria") or []) +
+                                                           list(stop_sequences_criteria(self.stop_words_ids)))
         return kw
 
     def greedy_tokens(self, embs, return_logits=False, starts=None):
@@ -1145,6 +1269,12 @@ class MiniGPT4Classifier:
             tokens.append(nxt)
             for e in eos_ids:
                 unfinished = unfinished * (nxt != e).long()
+            for seq in self.stop_words_ids or ():                      # the row's last len(seq) step tokens against the sequence
+                if len(seq) <= i + 1:
+                    hit = tokens[i + 1 - len(seq)] == seq[0]
+                    for k in range(1, len(seq)):
+                        hit = hit & (tokens[i + 1 - len(seq) + k] == seq[k])
+                    unfinished = unfinished * (~hit).long()
             if i + 1 == self.max_new_tokens:
                 break
             pos = torch.full((1, 1), L + i, device=embs.device, dtype=torch.long)
@@ -1159,7 +1289,8 @@ class MiniGPT4Classifier:
                self.prefill)
         key = key + ("ragged",) if ragged else key                    # a graph of the _ragged entries is never an unpadded one's
         key = key + ("grouped_kv",) if self.grouped_kv else key
-        return key + ("early_stop",) if self.early_stop else key      # nor is one captured with early stop on one captured without
+        key = key + ("early_stop",) if self.early_stop else key       # nor is one captured with early stop on one captured without
+        return key + ("stop", self.stop_words_ids) if self.stop_words_ids else key     # nor under one set of stop sequences another's
 
     def last_live_steps(self):
         """Token steps of the most recent native greedy decode (eager, or the last graph replay) that actually ran: max_new_tokens - 1
@@ -1199,8 +1330,19 @@ class MiniGPT4Classifier:
                     self.greedy_tokens(static_in, starts=static_starts)
                 torch.cuda.current_stream().wait_stream(side)
                 graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    static_out = self.greedy_tokens(static_in, starts=static_starts)
+                # No cyclic garbage may be finalised INSIDE the capture: a dropped classifier that sits in a reference cycle still owns
+                # its engine and its graphs' private pools, and the device frees of their finalisers abort the process when they run
+                # while a stream is capturing.  The model's own prefill allocates enough Python objects to start a collection there.
+                import gc
+                gc.collect()
+                gc_was_on = gc.isenabled()
+                gc.disable()
+                try:
+                    with torch.cuda.graph(graph):
+                        static_out = self.greedy_tokens(static_in, starts=static_starts)
+                finally:
+                    if gc_was_on:
+                        gc.enable()
             self.decode_stats["hip_steps"] = hip_steps
             self.decode_stats["hip_prefills"] = hip_prefills
             entry = (graph, static_in, static_out, static_starts)

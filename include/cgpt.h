@@ -487,6 +487,26 @@ cgpt_status cgpt_llm_greedy_ragged(cgpt_llm_handle h, const float* first_logits_
 cgpt_status cgpt_llm_set_early_stop(cgpt_llm_handle h, int32_t on);
 cgpt_status cgpt_llm_live_steps(cgpt_llm_handle h, int32_t* out_host, void* stream);
 
+/* ---- Stop sequences: a row of the greedy entries also finishes when its generated tokens end in one of them ----
+ * Replaces: `StoppingCriteriaSub` (conversation.py:96-107) behind `MiniGPTBase.generate(..., stop_words_ids=...)`
+ * (minigpt_base.py:387-394), with one deviation: the reference's criterion fires only when ALL rows end in a sequence at the same
+ * step; here every row finishes on its own, as it does on an EOS id.
+ * cgpt_llm_set_stop_sequences(h, ids_host, lens_host, n): n sequences, sequence s of lens_host[s] token ids, the ids of all
+ * sequences one after the other in ids_host (sum of lens_host entries).  Handle state, read when cgpt_llm_greedy /
+ * cgpt_llm_greedy_ragged ENQUEUE (as cgpt_llm_set_early_stop is): the arrays are copied by this call, the sequences travel to the
+ * select kernel by value, and a captured graph keeps the set it was captured under.  n = 0 clears the set, which is the state after
+ * cgpt_llm_create; with it both entries launch exactly what they launched before this entry existed.
+ * The rule: row b finishes at select i when token i is an EOS id (as before) or when, for a sequence s of length len <= i + 1,
+ * tokens i-len+1 .. i of the row equal s.  Only tokens the call generated are compared (the prompt is embeddings), so a sequence
+ * longer than i + 1 cannot match at select i.  min_new masks the EOS logits only: it never suppresses a match.  The finishing
+ * tokens stay in tokens_out_dev; later columns hold pad_id.  The tokens are, bit for bit, those of the same call without sequences
+ * with everything after each row's finishing column replaced by pad_id, and the step logits of every select up to a row's
+ * finishing column are that call's.  A finished row counts as finished for early stop and cgpt_llm_live_steps.
+ * cgpt_llm_step, cgpt_llm_step_ragged, the prefill entries and the scoring entries never see the sequences.
+ * CGPT_ERR_INVALID, before any device call and leaving the handle's set as it was: a null handle, n outside 0..8, a length outside
+ * 1..8, a negative id, null arrays with n > 0. */
+cgpt_status cgpt_llm_set_stop_sequences(cgpt_llm_handle h, const int64_t* ids_host, const int32_t* lens_host, int32_t n);
+
 /* ---- Answer scoring: all candidates of a multiple-choice question on ONE prefilled prompt ----
  * Replaces: `MiniGPTBase.multi_select` (minigpt_base.py:451-467), i.e. `forward(..., reduction='none')` (minigpt_base.py:320-363;
  * modeling_llama.py:101-123) once per candidate: a whole forward over prompt + answer and

@@ -37,6 +37,13 @@ logit is 0, the select picks token 1 while EOS is masked (min_length = F generat
 The order of the legs is rotated from one repetition to the next.  dead_step_ms = the live step minus the saving per skipped step,
 (generate(on_never) - generate(on_fF)) / (19 - F).
 
+--stop runs the stop-sequence leg instead (stop_words_ids), same protocol with the rotated leg order, every engine
+decode="hip", prefill="hip".  lm_head is zeroed and there is no EOS id, so every logit is 0 and every token is 0:
+    off         no stop sequences, early stop off (today's path)
+    never       8 sequences of 8 ids beyond the vocabulary, which no row can produce: what the comparisons in the select cost
+    on_k1/on_k3 early stop on and the sequence "k zeros": every row finishes at select k - 1, 19 / 17 of the 19 steps are dead
+    parent      `off` on another build of the library (--parent-lib PATH), as under --ragged
+
 --gqa runs the grouped-query leg instead (grouped_kv=True), same protocol with the rotated leg order, on a
 Llama-3-8B-shaped random-init decoder (hidden 4096, 32 query / 8 K/V heads, MLP 14336, rope_theta 500000, --gqa-vocab tokens):
     gqa         decode="hip", prefill="hip", grouped_kv=True: prefill and steps in this library, caches of 8 heads
@@ -367,6 +374,90 @@ def early_stop_leg(args, llm, embs, tok, lm):
     print(json.dumps(line))
 
 
+def stop_leg(args, llm, embs, tok, lm):
+    from certifiedgpt_amd.minigpt4 import apply_stop_sequences
+    rows, new = args.rows, args.new
+    with torch.no_grad():
+        llm.lm_head.weight.zero_()
+    llm.config.eos_token_id = llm.generation_config.eos_token_id = []
+    llm.config.pad_token_id = llm.generation_config.pad_token_id = 0
+
+    def build(n, **kw):
+        return MiniGPT4Classifier(_Rows(rows), llm, tok, "<ImageHere>", lm, max_new_tokens=n, max_batch=rows, decode="hip", prefill="hip",
+                                  generate_kwargs=dict(min_length=0), **kw)
+
+    never = [[32000 + 8 * q + j for j in range(8)] for q in range(8)]
+    how = {"off": {}, "never": dict(stop_words_ids=never), "on_k1": dict(early_stop=True, stop_words_ids=[[0]]),
+           "on_k3": dict(early_stop=True, stop_words_ids=[[0] * 3])}
+    legs = list(how)
+    clfs = {(e, new): build(new, **how[e]) for e in legs}
+    prefill = build(1)                                                   # one select, no step: the same call on every leg of this build
+    for e in legs:
+        clfs[(e, 1)] = prefill
+    if args.parent_lib:
+        with _other_library(args.parent_lib):
+            clfs.update({("parent", n): build(n) for n in (new, 1)})
+        legs.append("parent")
+
+    def timed(leg, n):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = clfs[(leg, n)]._generate_graph(embs)
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b), out
+
+    clock_before = _clock()
+    res = {e: {"generate_ms": [], "prefill_ms": [], "order": []} for e in legs}
+    tokens, live = {}, {}
+    with torch.no_grad():
+        for rep_i in range(args.warmup + args.reps):                   # interleaved, and rotated: every leg takes every place in turn
+            k = rep_i % len(legs)
+            for place, e in enumerate(legs[k:] + legs[:k]):
+                t, out = timed(e, new)
+                if e != "parent":
+                    live[e] = clfs[(e, new)].last_live_steps()         # after the timed region: it synchronises
+                tp = timed(e, 1)[0]
+                print(f"decode_step_bench: repetition {rep_i} {e} generate {t:.1f} ms prefill {tp:.1f} ms", file=sys.stderr, flush=True)
+                if rep_i >= args.warmup:
+                    res[e]["generate_ms"].append(t)
+                    res[e]["prefill_ms"].append(tp)
+                    res[e]["order"].append(place)
+                    tokens[e] = out
+    clock_after = _clock()
+    steps = new - 1
+    for r in res.values():
+        r["step_ms"] = [(gm - pm) / steps for gm, pm in zip(r["generate_ms"], r["prefill_ms"])]
+        for k in ("generate_ms", "prefill_ms", "step_ms"):
+            r[k + "_min_max"] = [min(r[k]), max(r[k])]
+
+    def overlap(a, b, k):
+        (a0, a1), (b0, b1) = res[a][k + "_min_max"], res[b][k + "_min_max"]
+        return a0 <= b1 and b0 <= a1
+
+    def med(e, k):
+        return sorted(res[e][k])[len(res[e][k]) // 2]
+
+    keys = ("prefill_ms", "step_ms", "generate_ms")
+    rule = lambda e: apply_stop_sequences(tokens["off"], [], how[e]["stop_words_ids"], 0)  # noqa: E731
+    line = {"tool": "decode_step_bench", "leg": "stop", "rows": rows, "prompt": args.prompt, "new_tokens": new, "layers": args.layers,
+            "reps": args.reps, "warmup": args.warmup, "leg_order": "rotated by one place per repetition", "engines": res,
+            "live_steps": live,
+            "never_over_off_median": {k: med("never", k) / med("off", k) for k in keys},
+            "never_and_off_ranges_overlap": {k: overlap("never", "off", k) for k in keys},
+            "on_over_off_generate_median": {e: med(e, "generate_ms") / med("off", "generate_ms") for e in ("on_k1", "on_k3")},
+            "rows_with_the_rule_on_off_tokens": {e: int((tokens[e] == rule(e)).all(dim=1).sum()) for e in ("never", "on_k1", "on_k3")},
+            "shader_clock_mhz_before_after": [clock_before, clock_after], "device": torch.cuda.get_device_name(0)}
+    if "parent" in res:
+        line["parent_lib"] = os.path.basename(args.parent_lib)
+        line["off_and_parent_ranges_overlap"] = {k: overlap("off", "parent", k) for k in keys}
+        line["never_and_parent_ranges_overlap"] = {k: overlap("never", "parent", k) for k in keys}
+        line["off_over_parent_median"] = {k: med("off", k) / med("parent", k) for k in keys}
+        line["never_over_parent_median"] = {k: med("never", k) / med("parent", k) for k in keys}
+        line["off_rows_with_parent_tokens"] = int((tokens["off"] == tokens["parent"]).all(dim=1).sum())
+    print(json.dumps(line))
+
+
 def gqa_leg(args, dev):
     rows, new = args.rows, args.new
     lm = AnswerLabelMap(4, ())
@@ -465,10 +556,11 @@ def main():
     ap.add_argument("--act-int8", action="store_true",
                     help='with the weight-format leg: a third engine, weights="int8" + activations="int8" (DESIGN.md 4.4.7)')
     ap.add_argument("--early-stop", action="store_true", help="the early-stop leg (see the module docstring)")
+    ap.add_argument("--stop", action="store_true", help="the stop-sequence leg (see the module docstring)")
     ap.add_argument("--gqa", action="store_true", help="the grouped-query leg (see the module docstring)")
     ap.add_argument("--gqa-vocab", type=int, default=128256)
     ap.add_argument("--parent-lib", default=None,
-                    help="another build of libcgpt.so for the plain-path A/B of --ragged / --int8 / --early-stop / --gqa")
+                    help="another build of libcgpt.so for the plain-path A/B of --ragged / --int8 / --early-stop / --stop / --gqa")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "this benchmark measures device time: it needs the GPU"
     assert 1 <= args.rows <= 256 and args.new >= 2 and args.prompt >= 1
@@ -486,6 +578,8 @@ def main():
         return int8_leg(args, llm, embs, tok, lm)
     if args.early_stop:
         return early_stop_leg(args, llm, embs, tok, lm)
+    if args.stop:
+        return stop_leg(args, llm, embs, tok, lm)
     how = {"graph": dict(decode="graph"), "hip": dict(decode="hip", prefill="model"), "hip_native": dict(decode="hip", prefill="hip")}
     clfs = {(e, n): MiniGPT4Classifier(_Rows(args.rows), llm, tok, "<ImageHere>", lm, max_new_tokens=n, max_batch=args.rows,
                                        prefill_linear="cgpt", **how[e]) for e in engines for n in (args.new, 1)}
