@@ -55,6 +55,17 @@ class LlmConfigAct(C.Structure):
                 ("reserved2", C.c_int32)]
 
 
+class LlmSampleParams(C.Structure):
+    """struct cgpt_llm_sample_params (include/cgpt.h), passed BY VALUE to the sampling entries -- field order is ABI."""
+    _fields_ = [("struct_size", C.c_int32), ("do_sample", C.c_int32), ("temperature", C.c_float), ("top_k", C.c_int32),
+                ("top_p", C.c_float), ("repetition_penalty", C.c_float)]
+
+
+def sample_params(do_sample, temperature, top_k, top_p, repetition_penalty):
+    return LlmSampleParams(struct_size=C.sizeof(LlmSampleParams), do_sample=int(bool(do_sample)), temperature=float(temperature),
+                           top_k=int(top_k), top_p=float(top_p), repetition_penalty=float(repetition_penalty))
+
+
 LLM_ACT_FORMATS = {"fp16": 0, "int8": 1}      # CGPT_LLM_A_F16, CGPT_LLM_A_INT8
 LLM_WEIGHT_FORMATS = {"fp16": 0, "int8": 1}   # CGPT_LLM_W_F16, CGPT_LLM_W_INT8
 # sizeof(cgpt_llm_config) before weight_format existed: still accepted by cgpt_llm_create (fp16), and what older builds expect
@@ -129,6 +140,11 @@ SIGNATURES = {
     "cgpt_llm_linear_i8_slices": (_I32, [_I64, _I64]),
     "cgpt_llm_score": (_I32, [_P, _P, _I32, _I32, _P, _P, _I32, _I32, _F, _P, _P, _I64, _P, _P]),
     "cgpt_llm_score_ragged": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _P, _I32, _I32, _F, _P, _P, _I64, _P, _P]),
+    "cgpt_llm_sample": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _P, _I32, _I64, _P, _P, _I64, _P, _P, LlmSampleParams, _P, _P, _P]),
+    "cgpt_llm_sample_ragged": (_I32, [_P, _P, _I32, _I32, _P, _I32, _I32, _P, _I32, _I64, _P, _P, _I64, _P, _P, LlmSampleParams, _P, _P,
+                                      _P]),
+    "cgpt_llm_sample_logits": (_I32, [_P, _I64, _I32, _I32, _P, _I64, _I32, _I32, _I32, _P, _I32, _I64, _P, LlmSampleParams, _P, _P, _P,
+                                      _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -28,6 +28,9 @@ Config (a plain dict or any mapping; the reference's YAMLs define no smoothing k
             #          also: stop_words_ids: null | [[ids], ...] (any decode: a row of the greedy decode finishes when its answer ends in
             #          one of up to 8 token-id sequences of 1..8 tokens, as on an EOS; with early_stop such rows count as finished),
             #          stop_text: null | "###" (every decoded answer is cut at its first occurrence)
+            #          also: sample: "hf" | "hip" (with decode "hip": a sampled decode -- do_sample, temperature, top_k, top_p,
+            #          repetition_penalty, the five generation fields that may be given beside it -- stays on the native engine and draws
+            #          from a counter-based stream: votes are a function of (image, seed, sample index), whatever the batch size or rank)
             mode: vit_head | encode_img, weights: <path to a torch state_dict saved with torch.save> | null, dims: {...},
             partial_weights: false}   # true: load what the checkpoint has on top of the synthetic initialisation
     data:  {num_images: 10, seed: 1234}      # synthetic CLIP-normalised images unless `dataset` is passed to the agent
@@ -211,7 +214,10 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
                   MiniGPTBase.multi_select, instead of generating), score: "hf" | "hip" (the model's own forward per candidate | one
                   native prefill + the native scoring pass; needs decode and prefill "hip"), end_sym: "\\n" (appended to every answer);
                   stop_words_ids: None | [[ids], ...] (per-row stop sequences of the greedy decode, any decode), stop_text: None | str
-                  (every decoded answer is cut at its first occurrence: "###" for checkpoints tuned with end_sym "###")"""
+                  (every decoded answer is cut at its first occurrence: "###" for checkpoints tuned with end_sym "###");
+                  sample: "hf" | "hip" (who decodes a sampled call; "hip" needs decode "hip") and the generation fields do_sample,
+                  temperature, top_k, top_p, repetition_penalty (handed to the classifier's generate_kwargs where present;
+                  `Chat.answer`: do_sample True, top_p 0.9, repetition_penalty 1.05, temperature 1.0)"""
     from ..minigpt4 import MiniGPT4Classifier
     from .label_adapter import AnswerLabelMap
     if llama_model is None:
@@ -236,6 +242,7 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
                          f"{num_classes} leaves room for {num_classes - 1} (the last class id is \"other\"): raise num_classes "
                          "or shorten the vocabulary -- truncating it would move real answers into the non-certifiable bucket")
     label_map = AnswerLabelMap(num_classes, answers, frozen=True)
+    fields = {k: gen_cfg[k] for k in ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty") if k in gen_cfg}
     return MiniGPT4Classifier(encoder, llama_model, tokenizer, prompt, label_map,
                               max_new_tokens=int(gen_cfg.get("max_new_tokens", 20)), max_batch=encoder.max_batch,
                               decode=gen_cfg.get("decode", "hf"), prefill_linear=gen_cfg.get("prefill_linear", "torch"),
@@ -245,7 +252,8 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
                               classify=gen_cfg.get("classify", "generate"), score=gen_cfg.get("score", "hf"),
                               end_sym=gen_cfg.get("end_sym", "\n"), activations=gen_cfg.get("activations", "fp16"),
                               int8_threshold=gen_cfg.get("int8_threshold", 6.0), outlier_cap=gen_cfg.get("outlier_cap", 64),
-                              stop_words_ids=gen_cfg.get("stop_words_ids"), stop_text=gen_cfg.get("stop_text"))
+                              stop_words_ids=gen_cfg.get("stop_words_ids"), stop_text=gen_cfg.get("stop_text"),
+                              sample=gen_cfg.get("sample", "hf"), generate_kwargs=fields or None)
 
 
 def build_classifier(model_cfg, num_classes, max_batch, device_index, tokenizer=None, llama_model=None):

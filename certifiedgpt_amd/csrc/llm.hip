@@ -34,6 +34,7 @@
 #include "../../include/cgpt.h"
 #include "common_host.h"
 #include "llm.h"
+#include "llm_select.h"
 
 using namespace cgpt;
 
@@ -54,7 +55,6 @@ namespace {
 typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 constexpr int HD = 128;                // head size the attention kernel is written for
 constexpr int MAX_ROWS = 256;          // one GEMM row tile
-constexpr int MAX_EOS = 8;
 
 __device__ __forceinline__ float rf16(float v) { return (float)(half_t)v; }
 // fp16(a * b) as a value of its own: without the barrier the compiler contracts fp16(a * b) + c into one v_fma_f16, which skips
@@ -444,13 +444,7 @@ __global__ __launch_bounds__(256) void llm_dequant_kernel(const signed char* __r
     reinterpret_cast<h16x8*>(out)[2 * id + 1] = hi;
 }
 
-struct EosIds { long long id[MAX_EOS]; int n; };
-// Stop sequences (cgpt_llm_set_stop_sequences), by value like EosIds: sequence s is id[s][0 .. len[s]).  `col` is the
-// select's index i, which the greedy entry fills in per launch.  A select without them takes the empty NoStop.
-constexpr int MAX_STOP = 8, MAX_STOP_LEN = 8;
-struct StopSeqs { long long id[MAX_STOP][MAX_STOP_LEN]; int len[MAX_STOP]; int n; int col; };
-struct NoStop {};
-template <bool STOP> using StopArg = std::conditional_t<STOP, StopSeqs, NoStop>;
+// EosIds, StopSeqs and the bookkeeping tail of a select (CGPT_SELECT_TAIL) are llm_select.h's: the sampled select (llm_sample.hip) shares them.
 
 // Greedy bookkeeping of one step, one workgroup per row (greedy_tokens in minigpt4.py): EOS columns read as -inf while
 // `mask_eos` (the first min_new_tokens steps), first-max arg-max, pad once the row has produced an EOS.
@@ -504,28 +498,7 @@ __global__ __launch_bounds__(256) void llm_select_kernel(const float* src, int64
     if (threadIdx.x == 0) {
         for (int w = 1; w < 4; ++w)
             if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
-        int u = first ? 1 : unfinished[row];
-        const long long tok = u ? (long long)idx : pad;
-        for (int e = 0; e < eos.n; ++e)
-            if (tok == eos.id[e]) u = 0;
-        if constexpr (STOP) {
-            if (u) {
-                const long long* t = tokens_out + (int64_t)row * ld_tokens;      // column `col` of this row; t[-j] is column col - j
-#pragma unroll
-                for (int q = 0; q < MAX_STOP; ++q) {
-                    const int len = q < stop.n ? stop.len[q] : 0;
-                    if (len < 1 || len > stop.col + 1) continue;
-                    bool match = true;
-#pragma unroll
-                    for (int k = 0; k < MAX_STOP_LEN; ++k)                  // element k sits len - 1 - k columns back
-                        if (k < len) match = match && (k == len - 1 ? tok : t[k - (len - 1)]) == stop.id[q][k];
-                    if (match) u = 0;
-                }
-            }
-        }
-        unfinished[row] = u;
-        tokens_out[(int64_t)row * ld_tokens] = tok;
-        next_tok[row] = tok;
+        CGPT_SELECT_TAIL(STOP, row, idx, first, eos, pad, unfinished, tokens_out, ld_tokens, next_tok, stop);
     }
 }
 
@@ -1115,9 +1088,16 @@ cgpt_status cgpt_llm_step_ragged(cgpt_llm_handle h, const int64_t* tokens_dev, i
 static cgpt_status llm_greedy_entry(const char* who_c, cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len,
                                     const int32_t* starts_dev, int32_t num_new, int32_t min_new, const int64_t* eos_ids_host,
                                     int32_t num_eos, int64_t pad_id, void* const* k_ptrs_host, void* const* v_ptrs_host,
-                                    int64_t kv_len_stride, int64_t* tokens_out_dev, float* step_logits_out_dev, void* stream) {
+                                    int64_t kv_len_stride, int64_t* tokens_out_dev, float* step_logits_out_dev, void* stream,
+                                    const cgpt_llm_sample_params* sample = nullptr, const int64_t* draw_ids_dev = nullptr,
+                                    const uint64_t* seed_dev = nullptr) {
     const std::string who(who_c);
     if (!h || !first_logits_dev || !tokens_out_dev) return cgpt_fail(CGPT_ERR_INVALID, who + ": null argument");
+    SampleLaw law{};                                       // the sampling entries (sample != null): only the select launch differs
+    if (sample) {
+        if (!draw_ids_dev || !seed_dev) return cgpt_fail(CGPT_ERR_INVALID, who + ": null draw_ids_dev or seed_dev");
+        CGCHK(check_sample_params(who, *sample, h->cfg.vocab, num_new > 0 ? num_new - 1 : 0, num_eos > 0 ? num_eos : 0, &law));
+    }
     if (num_new < 1 || prompt_len < 1 || min_new < 0 || num_eos < 0 || num_eos > MAX_EOS || (num_eos > 0 && !eos_ids_host))
         return cgpt_fail(CGPT_ERR_INVALID, who + ": bad lengths (num_new, prompt_len >= 1; at most 8 EOS ids)");
     CGCHK(ready(h, who_c));
@@ -1145,7 +1125,16 @@ static cgpt_status llm_greedy_entry(const char* who_c, cgpt_llm_handle h, const 
         float* dst = nullptr;
         if (step_logits_out_dev && (i == 0 || mask)) dst = step_logits_out_dev + (int64_t)i * V;
         stop.col = i;
-        if (early) {
+        if (sample) {
+            SelectArgs a{src, lds, dst, ld_out, V, mask, eos, (long long)pad_id, i == 0 ? 1 : 0, h->unfinished,
+                         (long long*)tokens_out_dev + i, (int64_t)num_new, h->tok, early ? h->live : nullptr};
+            SampleIo io{(const long long*)tokens_out_dev, (int64_t)num_new, i, i, (const long long*)draw_ids_dev,
+                        (const unsigned long long*)seed_dev, nullptr, nullptr, nullptr, nullptr};
+            HIPCHK(launch_llm_sample(early, stop.n > 0 ? &stop : nullptr, a, law, io, B, st));
+            if (early)
+                hipLaunchKernelGGL(llm_live_kernel, dim3(1), dim3(256), 0, st, h->unfinished, B, i == 0 ? 1 : 0, i + 1 < num_new ? 1 : 0,
+                                   h->live, h->live_steps);
+        } else if (early) {
             if (stop.n > 0)
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(llm_select_kernel<true, true>), dim3(B), dim3(256), 0, st, src, lds, dst, ld_out, V, mask,
                                    eos, (long long)pad_id, i == 0 ? 1 : 0, h->unfinished, (long long*)tokens_out_dev + i, (int64_t)num_new,
@@ -1194,6 +1183,26 @@ cgpt_status cgpt_llm_greedy_ragged(cgpt_llm_handle h, const float* first_logits_
     if (!starts_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_greedy_ragged: null starts_dev");
     return llm_greedy_entry("cgpt_llm_greedy_ragged", h, first_logits_dev, B, prompt_len, starts_dev, num_new, min_new, eos_ids_host,
                             num_eos, pad_id, k_ptrs_host, v_ptrs_host, kv_len_stride, tokens_out_dev, step_logits_out_dev, stream);
+}
+
+cgpt_status cgpt_llm_sample(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len, int32_t num_new,
+                            int32_t min_new, const int64_t* eos_ids_host, int32_t num_eos, int64_t pad_id, void* const* k_ptrs_host,
+                            void* const* v_ptrs_host, int64_t kv_len_stride, int64_t* tokens_out_dev, float* step_logits_out_dev,
+                            cgpt_llm_sample_params params, const int64_t* draw_ids_dev, const uint64_t* seed_dev, void* stream) {
+    return llm_greedy_entry("cgpt_llm_sample", h, first_logits_dev, B, prompt_len, nullptr, num_new, min_new, eos_ids_host, num_eos, pad_id,
+                            k_ptrs_host, v_ptrs_host, kv_len_stride, tokens_out_dev, step_logits_out_dev, stream, &params, draw_ids_dev,
+                            seed_dev);
+}
+
+cgpt_status cgpt_llm_sample_ragged(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len,
+                                   const int32_t* starts_dev, int32_t num_new, int32_t min_new, const int64_t* eos_ids_host,
+                                   int32_t num_eos, int64_t pad_id, void* const* k_ptrs_host, void* const* v_ptrs_host,
+                                   int64_t kv_len_stride, int64_t* tokens_out_dev, float* step_logits_out_dev,
+                                   cgpt_llm_sample_params params, const int64_t* draw_ids_dev, const uint64_t* seed_dev, void* stream) {
+    if (!starts_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_sample_ragged: null starts_dev");
+    return llm_greedy_entry("cgpt_llm_sample_ragged", h, first_logits_dev, B, prompt_len, starts_dev, num_new, min_new, eos_ids_host,
+                            num_eos, pad_id, k_ptrs_host, v_ptrs_host, kv_len_stride, tokens_out_dev, step_logits_out_dev, stream, &params,
+                            draw_ids_dev, seed_dev);
 }
 
 cgpt_status cgpt_llm_set_early_stop(cgpt_llm_handle h, int32_t on) {

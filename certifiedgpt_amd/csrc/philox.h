@@ -12,6 +12,13 @@ namespace cgpt {
 
 struct u32x4 { uint32_t x, y, z, w; };
 
+// Counter word 1 (`hi_word`) names the stream, so that no two uses of one (seed, id) share a draw:
+//   0  the Monte-Carlo noise of a sample (cgpt_sample_counts, cgpt_noise_batch, ...)
+//   1  the synthetic weights (cgpt_init_synthetic_weights)
+//   2  the processor noise
+//   3  the sampled decode: counter = (step, 3, draw id lo, draw id hi), word 0 -> one uniform per row and step (llm_sample.hip)
+constexpr uint32_t PHILOX_WORD_NOISE = 0, PHILOX_WORD_WEIGHTS = 1, PHILOX_WORD_PROCESSOR = 2, PHILOX_WORD_SAMPLE = 3;
+
 __host__ __device__ inline u32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                                uint32_t k0, uint32_t k1) {
 #pragma unroll

@@ -77,6 +77,99 @@ def apply_stop_sequences(tokens, eos_ids, stop_seqs, pad):
     return [row[:f + 1] + [int(pad)] * (len(row) - f - 1) for row, f in zip(_as_rows(tokens), cols)]
 
 
+# ---- the sampling law of sample="hip" (csrc/llm_sample.hip; include/cgpt.h: "Sampled decoding"), stated once: the oracle
+PHILOX_WORD_SAMPLE = 3                                                # counter word 1 of the sampled decode's stream (csrc/philox.h)
+SAMPLE_FIELDS = ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty")
+SAMPLE_HF_DEFAULTS = {"do_sample": False, "temperature": 1.0, "top_k": 50, "top_p": 1.0, "repetition_penalty": 1.0}   # GenerationConfig's
+
+
+def _philox4x32_10(counter, key):
+    c0, c1, c2, c3 = (int(c) & 0xFFFFFFFF for c in counter)
+    k0, k1 = (int(k) & 0xFFFFFFFF for k in key)
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & 0xFFFFFFFF, (p0 >> 32) ^ c3 ^ k1, p0 & 0xFFFFFFFF
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c0, c1, c2, c3
+
+
+def sample_uniform(seed, draw_id, step):
+    """The uniform of draw `draw_id` at select `step` under `seed`: word 0 of Philox4x32-10(counter = (step, 3, id_lo, id_hi), key =
+    (seed_lo, seed_hi)), its top 24 bits times 2^-24 -- in [0, 1), exact in fp32, a function of the three numbers alone."""
+    seed, draw_id = int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw_id) & 0xFFFFFFFFFFFFFFFF
+    word = _philox4x32_10((int(step), PHILOX_WORD_SAMPLE, draw_id & 0xFFFFFFFF, draw_id >> 32), (seed & 0xFFFFFFFF, seed >> 32))[0]
+    return (word >> 8) * 2.0 ** -24
+
+
+def sample_token_law(logits, prev_tokens, u, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, mask_eos_ids=(),
+                     do_sample=True, dtype=torch.float64, details=False):
+    """One sampled select on one logits row [V], in HF's processor order, evaluated in `dtype` (float64: the oracle of the kernel):
+      1. the columns `mask_eos_ids` read as -inf;  2. every DISTINCT id of `prev_tokens` (the row's generated tokens so far) is
+      penalised once, l > 0 ? l / pen : l * pen;  3. l / temperature;  4. top_k: keep l >= the k-th largest value (0 or >= V: off);
+      5. softmax over what is kept;  6. top_p < 1: n = the smallest count whose descending cumulative mass is >= top_p, keep
+      p >= p_(n);  7. the token is the first kept column, in index order, whose cumulative kept mass exceeds u * kept_mass.
+    Both cuts keep the WHOLE group of equal values at their boundary (HF splits it by torch.sort's tie order), so the law does not
+    depend on the order of the columns; a column at -inf is never kept.  do_sample=False: steps 1-2, then the first maximum.
+    Returns (token, kept) -- kept a bool [V] -- or, with details=True, a dict with token, kept, p (the step-5 probabilities),
+    kept_mass and, for the top-p cut, sorted_p / cum (the descending probabilities and their cumulative masses) and n (None without
+    a cut)."""
+    l = torch.as_tensor(logits).detach().cpu().to(dtype).clone().reshape(-1)
+    V = l.numel()
+    for e in mask_eos_ids:
+        if 0 <= int(e) < V:
+            l[int(e)] = float("-inf")
+    pen = torch.tensor(float(repetition_penalty), dtype=dtype)
+    if float(repetition_penalty) != 1.0:
+        for t in sorted(set(int(t) for t in (prev_tokens.tolist() if hasattr(prev_tokens, "tolist") else prev_tokens))):
+            if 0 <= t < V:
+                l[t] = l[t] / pen if l[t] > 0 else l[t] * pen
+    if not do_sample:
+        token = int(torch.nonzero(l == l.max())[0])                            # the first maximum
+        kept = torch.zeros(V, dtype=torch.bool)
+        kept[token] = True
+        if details:
+            return {"token": token, "kept": kept, "p": kept.to(dtype), "kept_mass": 1.0, "sorted_p": None, "cum": None, "n": None}
+        return token, kept
+    l = l / torch.tensor(float(temperature), dtype=dtype)
+    kept = l > float("-inf")
+    if 0 < int(top_k) < V:
+        kept &= l >= torch.sort(l, descending=True).values[int(top_k) - 1]
+    w = torch.where(kept, torch.exp(l - l.max()), torch.zeros((), dtype=dtype))
+    p = w / w.sum()
+    srt = cum = n = None
+    if float(top_p) < 1.0:
+        srt = torch.sort(p, descending=True).values
+        cum = torch.cumsum(srt, dim=0)
+        hit = torch.nonzero(cum >= torch.tensor(float(top_p), dtype=dtype))
+        n = int(hit[0]) + 1 if hit.numel() else int(kept.sum())
+        kept &= p >= srt[n - 1]
+    pk = torch.where(kept, p, torch.zeros((), dtype=dtype))
+    cdf = torch.cumsum(pk, dim=0)
+    mass = pk.sum()
+    over = torch.nonzero(kept & (cdf > torch.tensor(float(u), dtype=dtype) * mass))
+    token = int(over[0]) if over.numel() else int(torch.nonzero(kept)[-1])
+    if details:
+        return {"token": token, "kept": kept, "p": p, "kept_mass": float(mass), "sorted_p": srt, "cum": cum, "n": n}
+    return token, kept
+
+
+def check_sample_settings(settings):
+    """(do_sample, temperature, top_k, top_p, repetition_penalty) as the native sampler takes them; ValueError naming the field for
+    temperature <= 0, top_p outside (0, 1], top_k < 0 or repetition_penalty <= 0 (what cgpt_llm_sample refuses)."""
+    do_sample, temperature, top_k, top_p, pen = settings
+    if not isinstance(do_sample, (bool, int)):
+        raise ValueError(f"do_sample={do_sample!r}: expected False or True")
+    if not float(temperature) > 0 or float(temperature) == float("inf"):
+        raise ValueError(f"temperature={temperature!r}: expected a finite value > 0")
+    if isinstance(top_k, bool) or int(top_k) != top_k or int(top_k) < 0:
+        raise ValueError(f"top_k={top_k!r}: expected an int >= 0 (0: off)")
+    if not 0.0 < float(top_p) <= 1.0:
+        raise ValueError(f"top_p={top_p!r}: expected a value in (0, 1]")
+    if not float(pen) > 0 or float(pen) == float("inf"):
+        raise ValueError(f"repetition_penalty={pen!r}: expected a finite value > 0")
+    return bool(do_sample), float(temperature), int(top_k), float(top_p), float(pen)
+
+
 def check_stop_words_ids(stop_words_ids):
     """The `stop_words_ids` keyword (the reference's name, minigpt_base.py:387) -> a tuple of token-id tuples: a list of token-id
     lists (or 1-d tensors, as conversation.py builds them), an int entry read as a one-token sequence, as the reference's `[2]` is.
@@ -734,6 +827,35 @@ class _HipDecoder:
                                                               self._starts_ptr(starts, B), *tail))
         return (tokens, steps) if return_logits else tokens
 
+    def sample(self, first_logits, prompt_len, num_new, min_new, eos_ids, pad_id, k_bufs, v_bufs, settings, draw_ids, seed,
+               return_logits=False, starts=None):
+        """`greedy` with the sampling law in the place of the arg-max (cgpt_llm_sample / cgpt_llm_sample_ragged; `sample_token_law`).
+        settings = (do_sample, temperature, top_k, top_p, repetition_penalty); draw_ids [B] int64 and seed [1] int64 (the 64 bits of
+        the seed) live on the device and are read when the kernels run, so a captured call draws whatever they hold at each replay."""
+        C = self._C
+        B, V = first_logits.shape
+        assert (first_logits.dtype == torch.float32 and first_logits.device == self.device and first_logits.is_contiguous()
+                and V == self.vocab and 1 <= B <= self.max_batch and num_new >= 1 and len(eos_ids) <= 8)
+        assert (draw_ids.dtype == torch.int64 and draw_ids.device == self.device and draw_ids.is_contiguous()
+                and tuple(draw_ids.shape) == (B,)), (tuple(draw_ids.shape), draw_ids.dtype, draw_ids.device)
+        assert seed.dtype == torch.int64 and seed.device == self.device and seed.numel() == 1, (seed.dtype, seed.device)
+        params = self._lib_mod.sample_params(*check_sample_settings(settings))
+        kp, vp, stride = self._cache_tables(k_bufs, v_bufs, B, prompt_len + num_new - 1)
+        tokens = torch.empty((B, num_new), dtype=torch.int64, device=self.device)
+        steps = torch.empty((B, num_new, V), dtype=torch.float32, device=self.device) if return_logits else None
+        eos = (C.c_int64 * max(1, len(eos_ids)))(*[int(e) for e in eos_ids])
+        self._greedy_ran = True
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        tail = (int(num_new), int(min_new), eos, len(eos_ids), int(pad_id), kp, vp, stride, C.c_void_p(tokens.data_ptr()),
+                C.c_void_p(steps.data_ptr()) if return_logits else None, params, C.c_void_p(draw_ids.data_ptr()),
+                C.c_void_p(seed.data_ptr()), st)
+        if starts is None:
+            self._lib_mod.check(self.L.cgpt_llm_sample(self.handle, C.c_void_p(first_logits.data_ptr()), B, int(prompt_len), *tail))
+        else:
+            self._lib_mod.check(self.L.cgpt_llm_sample_ragged(self.handle, C.c_void_p(first_logits.data_ptr()), B, int(prompt_len),
+                                                              self._starts_ptr(starts, B), *tail))
+        return (tokens, steps) if return_logits else tokens
+
     def set_early_stop(self, on):
         """cgpt_llm_set_early_stop: read by the next `greedy` when it enqueues; a captured call keeps what it was captured under."""
         self._lib_mod.check(self.L.cgpt_llm_set_early_stop(self.handle, int(bool(on))))
@@ -817,6 +939,7 @@ class MiniGPT4Classifier:
        :param outlier_cap: outliers kept per activation row under activations="int8" (1..1024; more in a row is a RuntimeError)
        :param early_stop: False (default) | True (with decode="hip") -- the native token steps do no work once every row has its EOS
        :param grouped_kv: False (default) | True (with decode="hip") -- the native engine takes a grouped-query decoder; see __init__
+       :param sample: "hf" (default) | "hip" (with decode="hip") -- who decodes a call with do_sample / a repetition penalty; see __init__
        :param stop_words_ids: None (default) | up to 8 token-id sequences of 1..8 tokens -- a row finishes when its answer ends in one
        :param stop_text: None (default) | str -- every decoded answer is cut at its first occurrence (the reference's "###")
        :param end_sym: text appended to every candidate answer of `multi_select` ("\n": the reference's default; its VQA configs: "###")
@@ -836,7 +959,7 @@ class MiniGPT4Classifier:
                  generate_kwargs=None, decode="hf", prefill_linear="torch", prefill="model", ragged="hf", prompt_bucket=None,
                  weights="fp16", end_sym="\n", label_smoothing=0.1, score="hf", classify="generate", candidates=None,
                  early_stop=False, grouped_kv=False, activations="fp16", int8_threshold=6.0, outlier_cap=64, stop_words_ids=None,
-                 stop_text=None):
+                 stop_text=None, sample="hf"):
         self.encoder = encoder
         self.llama_model = llama_model
         self.llama_tokenizer = llama_tokenizer
@@ -913,6 +1036,15 @@ class MiniGPT4Classifier:
         #   select kernel looks back in its own token table), and a finished row counts for early_stop; decode = "graph": the same
         #   rule in tensor ops on the loop's step tokens; decode = "hf" and every HF fallback: a StoppingCriteria that answers per row.
         #   An int entry is a one-token sequence.  None (default): every path is what it was.
+        # sample = "hip" (with decode = "hip" only; anything else is a ValueError): a call whose generation arguments differ from the
+        #   greedy ones ONLY in do_sample, temperature, top_k, top_p and repetition_penalty -- `Chat.answer`'s do_sample=True,
+        #   top_p=0.9, repetition_penalty=1.05, temperature=1.0 with HF's default top_k=50 -- stays on the native engine: the select
+        #   kernel is replaced by a sampler (csrc/llm_sample.hip; `sample_token_law` is the law) whose uniform is a
+        #   function of (seed, draw id, step) alone.  `sample_counts` / `sample_counts_pair` give row r of sample index i the draw id
+        #   i and the call's seed, so a row's answer is a function of (image, seed, sample index) and counts do not depend on the
+        #   batch size or on how the range is split; `generate` / `__call__` take ids from a running counter (`reset_draws`).  Works
+        #   with either prefill, ragged = "hip", weights / activations = "int8", grouped_kv, early_stop and stop_words_ids; counted in
+        #   decode_stats["hip_sampled"].  sample = "hf" (default): such calls take HF `generate` and torch's generator, as before.
         # stop_text = "###": `_decode_outputs` cuts every decoded text at its first occurrence before `clean_answer`
         #   (`Chat.answer`'s `split('###')[0]`) -- at the text level because "###" tokenises differently after different words.
         # score = "hf" (default): `multi_select` / `answer_losses_from_embeds` run the model's own forward once per candidate over the
@@ -969,6 +1101,11 @@ class MiniGPT4Classifier:
         if early_stop and decode != "hip":
             raise ValueError(f'early_stop=True needs decode="hip" (got decode={decode!r}): only the native token steps can be switched '
                              "off on the device")
+        if sample not in ("hf", "hip"):
+            raise ValueError(f'sample={sample!r}: expected "hf" or "hip"')
+        if sample == "hip" and decode != "hip":
+            raise ValueError(f'sample="hip" needs decode="hip" (got decode={decode!r}): the sampler takes the place of the native '
+                             "engine's token select")
         stops = check_stop_words_ids(stop_words_ids)
         if stop_text is not None and (not isinstance(stop_text, str) or not stop_text):
             raise ValueError(f"stop_text={stop_text!r}: expected None or a non-empty str")
@@ -1014,6 +1151,11 @@ class MiniGPT4Classifier:
         self.stop_words_ids = stops or None                 # the validated tuple of tuples; None when there is none
         self.stop_text = stop_text
         self.grouped_kv = grouped_kv
+        self.sample = sample
+        self._draw_next, self._draw_seed = 0, 0             # `reset_draws`: the ids and the seed of calls that name no sample index
+        self._draw_bufs = None                              # (ids [max_batch] int64, seed [1] int64) on the device, made at first use
+        if sample == "hip":
+            self._sample_settings()                         # a ValueError for a setting the sampler refuses comes now
         # the keyword reaches the engine only when it is set (as `law` reaches an encoder)
         gqa = {"grouped_kv": True} if grouped_kv else {}
         self.activations, self.int8_threshold, self.outlier_cap = activations, float(int8_threshold), int(outlier_cap)
@@ -1035,6 +1177,7 @@ class MiniGPT4Classifier:
                              "hip_scores": 0,                     # native scoring passes (score = "hip"): one per call
                              "hip_ragged_scores": 0,              # native per-row scoring passes (score = "hip", ragged = "hip")
                              "hf_score_fallbacks": 0,             # score = "hip" calls that took the "hf" path (see __init__)
+                             "hip_sampled": 0,                    # decodes of the native sampler (sample = "hip"): one per call
                              # bytes the native engine holds for weights, scales and scratch (None without one)
                              "weight_bytes": self._hip.weight_bytes if self._hip is not None else None}
 
@@ -1074,8 +1217,9 @@ class MiniGPT4Classifier:
 
     # ---- minigpt_base.py:374-448 with encode_img's output given
     @torch.no_grad()
-    def generate_from_embeds(self, img_embeds, texts):
-        """img_embeds [B, queries, hidden] (any float dtype) + one prompt per row (or ONE str shared by all rows) -> list[str]."""
+    def generate_from_embeds(self, img_embeds, texts, draws=None):
+        """img_embeds [B, queries, hidden] (any float dtype) + one prompt per row (or ONE str shared by all rows) -> list[str].
+        draws (sample = "hip" only): (first draw id, seed) -- row r draws stream first + r; None: the running counter (`reset_draws`)."""
         dtype = self.embed_tokens(torch.zeros(1, 1, dtype=torch.long, device=img_embeds.device)).dtype
         img_embeds = img_embeds.to(dtype)
         B = img_embeds.shape[0]
@@ -1100,6 +1244,9 @@ class MiniGPT4Classifier:
             if not native_pad:
                 starts = None
         if self.decode in ("graph", "hip") and (shared or native_pad) and embs.is_cuda and self._greedy_defaults():
+            if self._sample_settings() is not None:                     # written before the replay: the kernels read them when they run
+                self._write_draws(B, draws, embs.device)
+                self.decode_stats["hip_sampled"] += 1
             outputs = self._generate_graph(embs, starts)
             if self.activations == "int8":                              # the tokens are read next: the same sync
                 self.last_act_stats()
@@ -1148,20 +1295,71 @@ class MiniGPT4Classifier:
         for key, val in self.generate_kwargs.items():
             if key not in self._GREEDY_NEUTRAL:
                 return False
+            if self.sample == "hip" and key in SAMPLE_FIELDS:         # the native sampler takes these at any value it accepts
+                continue
             want = self._GREEDY_NEUTRAL[key]
             if want is not None and val != want:
                 return False
         gen = getattr(self.llama_model, "generation_config", None)
         if gen is not None:
             for key, neutral in self._CONFIG_NEUTRAL.items():
-                if key in self.generate_kwargs:                        # the call's argument wins over the checkpoint's field
-                    continue
+                if key in self.generate_kwargs or (self.sample == "hip" and key in SAMPLE_FIELDS):
+                    continue                                           # the call's argument wins over the checkpoint's field
                 val = getattr(gen, key, None)
                 if isinstance(val, (list, tuple, dict)) and len(val) == 0:
                     val = None
                 if val not in neutral:
                     return False
         return True
+
+    def _sample_settings(self):
+        """sample = "hip": (do_sample, temperature, top_k, top_p, repetition_penalty) as `generate` would resolve them -- the call's
+        argument, else the checkpoint's generation_config, else GenerationConfig's default -- or None when they amount to the plain
+        arg-max (no sampling, no penalty), which stays on the greedy entries.  None under sample = "hf"."""
+        if self.sample != "hip":
+            return None
+        gen = getattr(self.llama_model, "generation_config", None)
+        vals = []
+        for key in SAMPLE_FIELDS:
+            val = self.generate_kwargs.get(key)
+            val = getattr(gen, key, None) if val is None else val
+            vals.append(SAMPLE_HF_DEFAULTS[key] if val is None else val)
+        settings = check_sample_settings(vals)
+        return settings if settings[0] or settings[4] != 1.0 else None
+
+    def reset_draws(self, next=0, seed=None):
+        """sample = "hip": calls that name no sample index (`generate`, `__call__`) draw streams next, next + 1, ... in row order, one
+        per row, under `seed` (None: unchanged; 0 at construction).  A reset to the same values reproduces the calls that follow."""
+        self._draw_next = int(next)
+        if seed is not None:
+            self._draw_seed = int(seed)
+
+    def _write_draws(self, B, draws, device):
+        """The persistent draw-id and seed tensors of the native sampler, set for the next decode of B rows."""
+        if self._draw_bufs is None or self._draw_bufs[0].device != device:
+            self._draw_bufs = (torch.zeros(self.max_batch, dtype=torch.int64, device=device),
+                               torch.zeros(1, dtype=torch.int64, device=device))
+        if draws is None:
+            first, seed = self._draw_next, self._draw_seed
+            self._draw_next += B
+        else:
+            first, seed = int(draws[0]), int(draws[1])
+        seed &= 0xFFFFFFFFFFFFFFFF
+        self._draw_bufs[0][:B].copy_(torch.arange(first, first + B, dtype=torch.int64, device=device))
+        self._draw_bufs[1].fill_(seed - (1 << 64) if seed >= 1 << 63 else seed)     # the 64 bits, as int64
+        return self._draw_bufs
+
+    def _select(self, logits, L, min_new, eos_ids, pad, k_bufs, v_bufs, return_logits, starts=None):
+        """The native loop after the prefill: the sampler under sample = "hip" when the settings ask for it, the arg-max otherwise."""
+        settings = self._sample_settings()
+        if settings is None:
+            return self._hip.greedy(logits, L, self.max_new_tokens, min_new, eos_ids, pad, k_bufs, v_bufs, return_logits=return_logits,
+                                    starts=starts)
+        if self._draw_bufs is None or self._draw_bufs[0].device != logits.device:
+            self._write_draws(logits.shape[0], None, logits.device)
+        ids, seed = self._draw_bufs
+        return self._hip.sample(logits, L, self.max_new_tokens, min_new, eos_ids, pad, k_bufs, v_bufs, settings, ids[:logits.shape[0]],
+                                seed, return_logits=return_logits, starts=starts)
 
     def min_new_tokens(self):
         """Generated tokens before which EOS is suppressed.  The reference passes `min_length = 1` with `inputs_embeds`
@@ -1238,8 +1436,7 @@ class MiniGPT4Classifier:
             logits = self._hip.prefill(embs.contiguous(), k_bufs, v_bufs, starts=starts)
             self.decode_stats["hip_prefills"] += 1
             self.decode_stats["hip_steps"] += self.max_new_tokens - 1
-            return self._hip.greedy(logits, L, self.max_new_tokens, self.min_new_tokens() if eos_ids else 0, eos_ids, pad,
-                                    k_bufs, v_bufs, return_logits=return_logits, starts=starts)
+            return self._select(logits, L, self.min_new_tokens() if eos_ids else 0, eos_ids, pad, k_bufs, v_bufs, return_logits, starts)
         cache = DynamicCache(config=llm.config)
         cache.layers = [PreallocLayer(L + self.max_new_tokens) for _ in cache.layers] or cache.layers
         pos = torch.arange(L, device=embs.device).unsqueeze(0)
@@ -1255,8 +1452,8 @@ class MiniGPT4Classifier:
         if self._hip is not None:                                      # decode = "hip": the loop below, in this library's kernels
             assert B <= self.max_batch, f"{B} rows > max_batch {self.max_batch} (the native decoder's workspace)"
             self.decode_stats["hip_steps"] += self.max_new_tokens - 1
-            return self._hip.greedy(logits.contiguous(), L, self.max_new_tokens, min_new, eos_ids, pad,
-                                    [l.buf_k for l in cache.layers], [l.buf_v for l in cache.layers], return_logits=return_logits)
+            return self._select(logits.contiguous(), L, min_new, eos_ids, pad, [l.buf_k for l in cache.layers],
+                                [l.buf_v for l in cache.layers], return_logits)
         unfinished = torch.ones(B, dtype=torch.long, device=embs.device)
         tokens, step_logits = [], []
         for i in range(self.max_new_tokens):
@@ -1290,7 +1487,9 @@ class MiniGPT4Classifier:
         key = key + ("ragged",) if ragged else key                    # a graph of the _ragged entries is never an unpadded one's
         key = key + ("grouped_kv",) if self.grouped_kv else key
         key = key + ("early_stop",) if self.early_stop else key       # nor is one captured with early stop on one captured without
-        return key + ("stop", self.stop_words_ids) if self.stop_words_ids else key     # nor under one set of stop sequences another's
+        key = key + ("stop", self.stop_words_ids) if self.stop_words_ids else key      # nor under one set of stop sequences another's
+        settings = self._sample_settings()
+        return key + ("sample", settings) if settings is not None else key             # nor the sampler under one law another's
 
     def last_live_steps(self):
         """Token steps of the most recent native greedy decode (eager, or the last graph replay) that actually ran: max_new_tokens - 1
@@ -1539,12 +1738,14 @@ class MiniGPT4Classifier:
         self.last_answers = answers
         return self.label_map.one_hot_logits(answers, device)
 
-    def _classify_embeds(self, emb, device):
+    def _classify_embeds(self, emb, device, draws=None):
         """One classifier batch from encode_img's output -> (logits [B, num_classes] on `device`, the rows' answer texts).
         classify="generate": one-hot of the generated answer's class.  classify="multi_select": -loss of candidate i in column i,
         -inf in column `other_id` (and in unused columns), so the top class is always a candidate."""
         if self.classify == "generate":
-            answers = self.generate_from_embeds(emb, self.prompt)
+            # the keyword travels only where it says something (sample = "hip"): subclasses that replace generate_from_embeds keep working
+            kw = {"draws": draws} if draws is not None and self.sample == "hip" else {}
+            answers = self.generate_from_embeds(emb, self.prompt, **kw)
             return self.label_map.one_hot_logits(answers, device), answers
         losses = self.answer_losses_from_embeds(emb, self.prompt, self.candidates)
         logits = torch.full((losses.shape[0], self.num_classes), float("-inf"), dtype=torch.float32, device=losses.device)
@@ -1576,7 +1777,7 @@ class MiniGPT4Classifier:
         while done < total:
             nb = min(bs, total - done)
             emb = self._encode_noisy(x, first_a + done, nb, sigma, seed, law)
-            logits, batch_answers = self._classify_embeds(emb, x.device)
+            logits, batch_answers = self._classify_embeds(emb, x.device, draws=(first_a + done, seed))
             na = max(0, min(nb, num_a - done))                         # rows of this batch that belong to the selection range
             if na > 0:
                 vote(logits[:na], counts[0])
@@ -1601,7 +1802,7 @@ class MiniGPT4Classifier:
         while done < num:
             nb = min(bs, num - done)
             emb = self._encode_noisy(x, first_sample + done, nb, sigma, seed, law)
-            logits, self.last_answers = self._classify_embeds(emb, x.device)
+            logits, self.last_answers = self._classify_embeds(emb, x.device, draws=(first_sample + done, seed))
             vote(logits, counts)
             done += nb
         return counts

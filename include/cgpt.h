@@ -622,6 +622,60 @@ cgpt_status cgpt_llm_linear_i8(const void* A_dev, const void* q_dev, const void*
 int64_t cgpt_llm_linear_i8_workspace(int64_t M, int64_t N, int64_t K, int32_t outlier_cap, int64_t* offsets_out);
 int32_t cgpt_llm_linear_i8_slices(int64_t N, int64_t K);
 
+/* ---- Sampled decoding: the greedy entries with a sampling law in the place of the arg-max ----
+ * Replaces: HF `generate(do_sample=True, temperature, top_k, top_p, repetition_penalty)` as `Chat.answer_prepare` calls it
+ * (do_sample=True, top_p=0.9, repetition_penalty=1.05, temperature=1.0, and HF's default top_k=50), whose draws come from torch's
+ * device-global generator.  Here the uniform of row b at select i is word 0 of
+ *   Philox4x32-10(counter = (i, 3, id_lo, id_hi), key = (seed_lo, seed_hi)),  u = (word >> 8) * 2^-24,
+ * id = draw_ids_dev[b], seed = *seed_dev: a function of (seed, draw id, select) alone, so a row's tokens do not depend on the batch it
+ * runs in.  Both are DEVICE memory read when the kernels RUN (as starts_dev is): a captured graph replayed after
+ * the buffers were rewritten draws the new stream.
+ * The law of one select on one fp32 logits row, in HF's processor order (`sample_token_law` in minigpt4.py is the float64 oracle):
+ *   1. the EOS columns read as -inf on the first min_new tokens (as in the greedy select);
+ *   2. every DISTINCT id among the row's tokens generated so far is penalised once: l > 0 ? l / pen : l * pen (the prompt is embeddings
+ *      and has no ids);                       3. l / temperature;
+ *   4. top_k: keep l >= the k-th largest value (0 or >= vocab: off);        5. softmax over what is kept;
+ *   6. top_p: n = the smallest count whose descending cumulative mass is >= top_p, keep p >= p_(n) (1: off);
+ *   7. the token is the first kept column, in vocabulary order, whose cumulative kept mass exceeds u * kept_mass.
+ * Both cuts keep a whole group of equal values at their boundary, where HF splits it by torch.sort's unspecified tie order.
+ * do_sample = 0: steps 1-2, then the first-max arg-max (greedy with a repetition penalty); no draw is made.
+ * Finished rows, EOS, stop sequences, early stop, pad_id, tokens_out_dev, step_logits_out_dev (the EOS-masked logits each select saw)
+ * and every contract of cgpt_llm_greedy / cgpt_llm_greedy_ragged hold unchanged; cgpt_llm_live_steps reports these calls too.  The
+ * greedy entries themselves launch exactly what they launched before these existed.
+ * CGPT_ERR_INVALID before any launch, besides the greedy entries' rules: a wrong struct_size, do_sample not 0 / 1, temperature <= 0,
+ * top_p outside (0, 1], top_k < 0, repetition_penalty <= 0, a null draw_ids_dev or seed_dev, vocab > 131072, num_new + num_eos > 1024. */
+typedef struct cgpt_llm_sample_params {
+    int32_t struct_size;              /* = sizeof(cgpt_llm_sample_params) */
+    int32_t do_sample;
+    float temperature;
+    int32_t top_k;
+    float top_p;
+    float repetition_penalty;
+} cgpt_llm_sample_params;
+cgpt_status cgpt_llm_sample(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len, int32_t num_new,
+                            int32_t min_new, const int64_t* eos_ids_host, int32_t num_eos, int64_t pad_id, void* const* k_ptrs_host,
+                            void* const* v_ptrs_host, int64_t kv_len_stride, int64_t* tokens_out_dev, float* step_logits_out_dev,
+                            cgpt_llm_sample_params params, const int64_t* draw_ids_dev, const uint64_t* seed_dev, void* stream);
+cgpt_status cgpt_llm_sample_ragged(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len,
+                                   const int32_t* starts_dev, int32_t num_new, int32_t min_new, const int64_t* eos_ids_host,
+                                   int32_t num_eos, int64_t pad_id, void* const* k_ptrs_host, void* const* v_ptrs_host,
+                                   int64_t kv_len_stride, int64_t* tokens_out_dev, float* step_logits_out_dev,
+                                   cgpt_llm_sample_params params, const int64_t* draw_ids_dev, const uint64_t* seed_dev, void* stream);
+/* One sampled select alone, without a handle, on the current device: logits_dev [B, V] fp32 (rows ld apart; not modified), row b's
+ * earlier tokens prev_tokens_dev[b * ld_prev + 0 .. num_prev) (NULL with num_prev = 0), `step` = Philox counter word 0.  mask_eos != 0
+ * applies step 1 to the num_eos ids of eos_ids_host.  unfinished_dev: [B] int32, read and written as the engine's own flags are -- a row
+ * holding 0 gets pad_id; a row that draws an EOS id is set to 0.  uniforms_in_dev (or NULL): [B] fp32 taken in the place of the Philox
+ * draw, so that the law can be tested apart from the stream; draw_ids_dev / seed_dev may then be NULL.  tokens_out_dev: [B] int64.
+ * uniforms_out_dev, kept_count_out_dev, kept_mass_out_dev (each [B], or NULL): the uniform used, the number of kept columns and the
+ * kept probability mass (kept weight sum / softmax denominator).  CGPT_ERR_INVALID before the launch as above, and for B < 1, V outside
+ * 1..131072, ld < V, ld_prev < num_prev, num_prev + num_eos > 1024 or a null logits / tokens / unfinished pointer. */
+cgpt_status cgpt_llm_sample_logits(const float* logits_dev, int64_t ld, int32_t B, int32_t V, const int64_t* prev_tokens_dev,
+                                   int64_t ld_prev, int32_t num_prev, int32_t step, int32_t mask_eos, const int64_t* eos_ids_host,
+                                   int32_t num_eos, int64_t pad_id, int32_t* unfinished_dev, cgpt_llm_sample_params params,
+                                   const int64_t* draw_ids_dev, const uint64_t* seed_dev, const float* uniforms_in_dev,
+                                   int64_t* tokens_out_dev, float* uniforms_out_dev, int32_t* kept_count_out_dev,
+                                   float* kept_mass_out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,7 +50,15 @@ Llama-3-8B-shaped random-init decoder (hidden 4096, 32 query / 8 K/V heads, MLP 
     graph       decode="graph" on the same model (PyTorch-ROCm steps replayed from one graph)
     plain       with --parent-lib: the DEFAULT path (no keyword) on the Vicuna-7B-shaped decoder of the other legs, this build
     parent      the same on another build of the library (--parent-lib PATH): the claim to check is that the default path is unchanged
-and reports the grouped engine's K/V pool bytes and weight_bytes beside the times."""
+and reports the grouped engine's K/V pool bytes and weight_bytes beside the times.
+
+--sample runs the sampled-decode leg instead (sample="hip"), same protocol with the rotated leg order, every engine
+decode="hip", prefill="hip", no EOS id (every row runs every step):
+    greedy      the arg-max select (today's path)
+    sampled     `Chat.answer`'s settings on the native sampler: do_sample, top_p 0.9, repetition_penalty 1.05, temperature 1.0 and
+                HF's default top_k 50; draw ids 0 .. rows - 1, seed 0
+    parent      `greedy` on another build of the library (--parent-lib PATH), as under --ragged
+sampler_ms_per_select = (generate(sampled) - generate(greedy)) / --new, from the medians: what the sampler costs beyond the arg-max."""
 import argparse
 import json
 import os
@@ -458,6 +466,83 @@ def stop_leg(args, llm, embs, tok, lm):
     print(json.dumps(line))
 
 
+def sample_leg(args, llm, embs, tok, lm):
+    rows, new = args.rows, args.new
+    llm.config.eos_token_id = llm.generation_config.eos_token_id = []
+    llm.config.pad_token_id = llm.generation_config.pad_token_id = 0
+    chat = dict(do_sample=True, top_p=0.9, repetition_penalty=1.05, temperature=1.0, min_length=0)
+
+    def build(n, **kw):
+        return MiniGPT4Classifier(_Rows(rows), llm, tok, "<ImageHere>", lm, max_new_tokens=n, max_batch=rows, decode="hip", prefill="hip",
+                                  **kw)
+
+    how = {"greedy": dict(generate_kwargs=dict(min_length=0)), "sampled": dict(sample="hip", generate_kwargs=chat)}
+    legs = list(how)
+    clfs = {(e, n): build(n, **how[e]) for e in legs for n in (new, 1)}
+    if args.parent_lib:
+        with _other_library(args.parent_lib):
+            clfs.update({("parent", n): build(n, **how["greedy"]) for n in (new, 1)})
+        legs.append("parent")
+
+    def timed(leg, n):
+        clf = clfs[(leg, n)]
+        if leg == "sampled":                                           # the ids and the seed, written before the timed region
+            clf._write_draws(rows, (0, 0), embs.device)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = clf._generate_graph(embs)
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b), out
+
+    clock_before = _clock()
+    res = {e: {"generate_ms": [], "prefill_ms": [], "order": []} for e in legs}
+    tokens = {}
+    with torch.no_grad():
+        for rep_i in range(args.warmup + args.reps):                   # interleaved, and rotated: every leg takes every place in turn
+            k = rep_i % len(legs)
+            for place, e in enumerate(legs[k:] + legs[:k]):
+                t, out = timed(e, new)
+                tp = timed(e, 1)[0]
+                print(f"decode_step_bench: repetition {rep_i} {e} generate {t:.1f} ms prefill+select {tp:.1f} ms", file=sys.stderr, flush=True)
+                if rep_i >= args.warmup:
+                    res[e]["generate_ms"].append(t)
+                    res[e]["prefill_ms"].append(tp)
+                    res[e]["order"].append(place)
+                    assert e not in tokens or torch.equal(tokens[e], out), f"{e}: a replay gave other tokens"
+                    tokens[e] = out
+    clock_after = _clock()
+    steps = new - 1
+    for r in res.values():
+        r["step_ms"] = [(gm - pm) / steps for gm, pm in zip(r["generate_ms"], r["prefill_ms"])]
+        for k in ("generate_ms", "prefill_ms", "step_ms"):
+            r[k + "_min_max"] = [min(r[k]), max(r[k])]
+
+    def overlap(a, b, k):
+        (a0, a1), (b0, b1) = res[a][k + "_min_max"], res[b][k + "_min_max"]
+        return a0 <= b1 and b0 <= a1
+
+    def med(e, k):
+        return sorted(res[e][k])[len(res[e][k]) // 2]
+
+    keys = ("prefill_ms", "step_ms", "generate_ms")
+    line = {"tool": "decode_step_bench", "leg": "sample", "rows": rows, "prompt": args.prompt, "new_tokens": new, "layers": args.layers,
+            "reps": args.reps, "warmup": args.warmup, "leg_order": "rotated by one place per repetition", "engines": res,
+            "settings": {k: v for k, v in chat.items() if k != "min_length"}, "top_k": 50,
+            "sampled_over_greedy_median": {k: med("sampled", k) / med("greedy", k) for k in keys},
+            "sampler_ms_per_select": (med("sampled", "generate_ms") - med("greedy", "generate_ms")) / new,
+            "sampler_ms_per_step": med("sampled", "step_ms") - med("greedy", "step_ms"),
+            "distinct_sampled_tokens": int(tokens["sampled"].unique().numel()),
+            "rows_where_sampled_differs_from_greedy": int((tokens["sampled"] != tokens["greedy"]).any(dim=1).sum()),
+            "shader_clock_mhz_before_after": [clock_before, clock_after], "device": torch.cuda.get_device_name(0)}
+    if "parent" in res:
+        line["parent_lib"] = os.path.basename(args.parent_lib)
+        line["greedy_and_parent_ranges_overlap"] = {k: overlap("greedy", "parent", k) for k in keys}
+        line["greedy_over_parent_median"] = {k: med("greedy", k) / med("parent", k) for k in keys}
+        line["greedy_rows_with_parent_tokens"] = int((tokens["greedy"] == tokens["parent"]).all(dim=1).sum())
+    print(json.dumps(line))
+
+
 def gqa_leg(args, dev):
     rows, new = args.rows, args.new
     lm = AnswerLabelMap(4, ())
@@ -558,9 +643,10 @@ def main():
     ap.add_argument("--early-stop", action="store_true", help="the early-stop leg (see the module docstring)")
     ap.add_argument("--stop", action="store_true", help="the stop-sequence leg (see the module docstring)")
     ap.add_argument("--gqa", action="store_true", help="the grouped-query leg (see the module docstring)")
+    ap.add_argument("--sample", action="store_true", help="the sampled-decode leg (see the module docstring)")
     ap.add_argument("--gqa-vocab", type=int, default=128256)
     ap.add_argument("--parent-lib", default=None,
-                    help="another build of libcgpt.so for the plain-path A/B of --ragged / --int8 / --early-stop / --stop / --gqa")
+                    help="another build of libcgpt.so for the plain-path A/B of --ragged / --int8 / --early-stop / --stop / --gqa / --sample")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "this benchmark measures device time: it needs the GPU"
     assert 1 <= args.rows <= 256 and args.new >= 2 and args.prompt >= 1
@@ -580,6 +666,8 @@ def main():
         return early_stop_leg(args, llm, embs, tok, lm)
     if args.stop:
         return stop_leg(args, llm, embs, tok, lm)
+    if args.sample:
+        return sample_leg(args, llm, embs, tok, lm)
     how = {"graph": dict(decode="graph"), "hip": dict(decode="hip", prefill="model"), "hip_native": dict(decode="hip", prefill="hip")}
     clfs = {(e, n): MiniGPT4Classifier(_Rows(args.rows), llm, tok, "<ImageHere>", lm, max_new_tokens=n, max_batch=args.rows,
                                        prefill_linear="cgpt", **how[e]) for e in engines for n in (args.new, 1)}
