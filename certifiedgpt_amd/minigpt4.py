@@ -18,10 +18,21 @@ embedded once per call and broadcast, and because every row then has the same le
 mask is all ones (identical to what the reference's left-padding produces for equal lengths).
 
 `Smooth` sees the engine interface (`sample_counts`), so noise generation stays fused into the patch-embed operand.
+
+What the LLaMA path is specified to compute (stop rule, sampling law, int8 laws, the grouped-query twin, padding) is stated in
+llm_laws.py; the ctypes binding of the native engine (`_HipDecoder`, `_LinearRoute`) is llm_engine.py.  Their names stay importable
+from this module, and the classifier resolves `_HipDecoder`, `_LinearRoute` and `vote` through this module's globals.
 """
 import torch
 
 from .classifier import vote
+from .llm_engine import _HipDecoder, _LinearRoute, _rope_theta, hip_decode_unsupported    # noqa: F401  (resolved through this module's globals)
+from .llm_laws import (GQA_RATIOS, LAYER_LINEARS, MAX_STOP_LEN, MAX_STOP_SEQS, PHILOX_WORD_SAMPLE, SAMPLE_FIELDS,    # noqa: F401
+                       SAMPLE_HF_DEFAULTS, _ActInt8Linear, _as_rows, _philox4x32_10, act_int8_twin, apply_stop_sequences,
+                       check_sample_settings, check_stop_words_ids, dequantize_rows_int8, expand_kv_state_dict, fp16_ulp,
+                       greedy_decode_parity, int8_state_dict, left_pad_embeds, llm_int8_linear, pack_row_candidates,
+                       quantize_act_rows_int8, quantize_rows_int8, sample_token_law, sample_uniform, stop_finish_columns,
+                       stop_sequences_criteria)
 
 IMAGE_PLACEHOLDER = "<ImageHere>"
 
@@ -37,184 +48,6 @@ def clean_answer(text: str) -> str:
     text = text.split("</s>")[0]
     text = text.replace("<s>", "")
     return text.split(r"[/INST]")[-1].strip()
-
-
-MAX_STOP_SEQS, MAX_STOP_LEN = 8, 8                                    # MAX_STOP, MAX_STOP_LEN of csrc/llm.hip
-
-
-def _as_rows(table):
-    return [[int(t) for t in row] for row in (table.tolist() if hasattr(table, "tolist") else table)]
-
-
-def stop_finish_columns(tokens, eos_ids, stop_seqs):
-    """The finishing rule of the greedy decode, stated once: for a [B, n] table of GENERATED tokens (tensor or
-    nested lists) the first column i at which each row finishes -- token i is an EOS id, or tokens i-len+1 .. i equal a stop sequence
-    of length len <= i + 1 (the prompt is embeddings and has no ids, so a longer sequence cannot match at select i).  len(row) for a
-    row that never finishes.  min_length masks EOS logits, as in HF; it never suppresses a match."""
-    eos = set(int(e) for e in (eos_ids.tolist() if hasattr(eos_ids, "tolist") else eos_ids))
-    seqs = [s for s in _as_rows(stop_seqs if stop_seqs is not None else [])]
-    cols = []
-    for row in _as_rows(tokens):
-        first = len(row)
-        for i, t in enumerate(row):
-            if t in eos or any(len(s) <= i + 1 and row[i + 1 - len(s):i + 1] == s for s in seqs):
-                first = i
-                break
-        cols.append(first)
-    return cols
-
-
-def apply_stop_sequences(tokens, eos_ids, stop_seqs, pad):
-    """`tokens` with every column after a row's finishing column (`stop_finish_columns`) replaced by `pad`; the finishing tokens
-    stay, as HF keeps them.  Greedy rows are independent, so this applied to a decode WITHOUT stop sequences is, bit for bit, the
-    decode with them.  A tensor gives a new tensor, nested lists a new list."""
-    cols = stop_finish_columns(tokens, eos_ids, stop_seqs)
-    if hasattr(tokens, "clone"):
-        out = tokens.clone()
-        for b, f in enumerate(cols):
-            out[b, f + 1:] = int(pad)
-        return out
-    return [row[:f + 1] + [int(pad)] * (len(row) - f - 1) for row, f in zip(_as_rows(tokens), cols)]
-
-
-# ---- the sampling law of sample="hip" (csrc/llm_sample.hip; include/cgpt.h: "Sampled decoding"; DESIGN.md 4.4.10), stated once: the oracle
-PHILOX_WORD_SAMPLE = 3                                                # counter word 1 of the sampled decode's stream (csrc/philox.h)
-SAMPLE_FIELDS = ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty")
-SAMPLE_HF_DEFAULTS = {"do_sample": False, "temperature": 1.0, "top_k": 50, "top_p": 1.0, "repetition_penalty": 1.0}   # GenerationConfig's
-
-
-def _philox4x32_10(counter, key):
-    c0, c1, c2, c3 = (int(c) & 0xFFFFFFFF for c in counter)
-    k0, k1 = (int(k) & 0xFFFFFFFF for k in key)
-    for _ in range(10):
-        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
-        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & 0xFFFFFFFF, (p0 >> 32) ^ c3 ^ k1, p0 & 0xFFFFFFFF
-        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
-    return c0, c1, c2, c3
-
-
-def sample_uniform(seed, draw_id, step):
-    """The uniform of draw `draw_id` at select `step` under `seed`: word 0 of Philox4x32-10(counter = (step, 3, id_lo, id_hi), key =
-    (seed_lo, seed_hi)), its top 24 bits times 2^-24 -- in [0, 1), exact in fp32, a function of the three numbers alone."""
-    seed, draw_id = int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw_id) & 0xFFFFFFFFFFFFFFFF
-    word = _philox4x32_10((int(step), PHILOX_WORD_SAMPLE, draw_id & 0xFFFFFFFF, draw_id >> 32), (seed & 0xFFFFFFFF, seed >> 32))[0]
-    return (word >> 8) * 2.0 ** -24
-
-
-def sample_token_law(logits, prev_tokens, u, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, mask_eos_ids=(),
-                     do_sample=True, dtype=torch.float64, details=False):
-    """One sampled select on one logits row [V], in HF's processor order, evaluated in `dtype` (float64: the oracle of the kernel):
-      1. the columns `mask_eos_ids` read as -inf;  2. every DISTINCT id of `prev_tokens` (the row's generated tokens so far) is
-      penalised once, l > 0 ? l / pen : l * pen;  3. l / temperature;  4. top_k: keep l >= the k-th largest value (0 or >= V: off);
-      5. softmax over what is kept;  6. top_p < 1: n = the smallest count whose descending cumulative mass is >= top_p, keep
-      p >= p_(n);  7. the token is the first kept column, in index order, whose cumulative kept mass exceeds u * kept_mass.
-    Both cuts keep the WHOLE group of equal values at their boundary (HF splits it by torch.sort's tie order), so the law does not
-    depend on the order of the columns; a column at -inf is never kept.  do_sample=False: steps 1-2, then the first maximum.
-    Returns (token, kept) -- kept a bool [V] -- or, with details=True, a dict with token, kept, p (the step-5 probabilities),
-    kept_mass and, for the top-p cut, sorted_p / cum (the descending probabilities and their cumulative masses) and n (None without
-    a cut)."""
-    l = torch.as_tensor(logits).detach().cpu().to(dtype).clone().reshape(-1)
-    V = l.numel()
-    for e in mask_eos_ids:
-        if 0 <= int(e) < V:
-            l[int(e)] = float("-inf")
-    pen = torch.tensor(float(repetition_penalty), dtype=dtype)
-    if float(repetition_penalty) != 1.0:
-        for t in sorted(set(int(t) for t in (prev_tokens.tolist() if hasattr(prev_tokens, "tolist") else prev_tokens))):
-            if 0 <= t < V:
-                l[t] = l[t] / pen if l[t] > 0 else l[t] * pen
-    if not do_sample:
-        token = int(torch.nonzero(l == l.max())[0])                            # the first maximum
-        kept = torch.zeros(V, dtype=torch.bool)
-        kept[token] = True
-        if details:
-            return {"token": token, "kept": kept, "p": kept.to(dtype), "kept_mass": 1.0, "sorted_p": None, "cum": None, "n": None}
-        return token, kept
-    l = l / torch.tensor(float(temperature), dtype=dtype)
-    kept = l > float("-inf")
-    if 0 < int(top_k) < V:
-        kept &= l >= torch.sort(l, descending=True).values[int(top_k) - 1]
-    w = torch.where(kept, torch.exp(l - l.max()), torch.zeros((), dtype=dtype))
-    p = w / w.sum()
-    srt = cum = n = None
-    if float(top_p) < 1.0:
-        srt = torch.sort(p, descending=True).values
-        cum = torch.cumsum(srt, dim=0)
-        hit = torch.nonzero(cum >= torch.tensor(float(top_p), dtype=dtype))
-        n = int(hit[0]) + 1 if hit.numel() else int(kept.sum())
-        kept &= p >= srt[n - 1]
-    pk = torch.where(kept, p, torch.zeros((), dtype=dtype))
-    cdf = torch.cumsum(pk, dim=0)
-    mass = pk.sum()
-    over = torch.nonzero(kept & (cdf > torch.tensor(float(u), dtype=dtype) * mass))
-    token = int(over[0]) if over.numel() else int(torch.nonzero(kept)[-1])
-    if details:
-        return {"token": token, "kept": kept, "p": p, "kept_mass": float(mass), "sorted_p": srt, "cum": cum, "n": n}
-    return token, kept
-
-
-def check_sample_settings(settings):
-    """(do_sample, temperature, top_k, top_p, repetition_penalty) as the native sampler takes them; ValueError naming the field for
-    temperature <= 0, top_p outside (0, 1], top_k < 0 or repetition_penalty <= 0 (what cgpt_llm_sample refuses)."""
-    do_sample, temperature, top_k, top_p, pen = settings
-    if not isinstance(do_sample, (bool, int)):
-        raise ValueError(f"do_sample={do_sample!r}: expected False or True")
-    if not float(temperature) > 0 or float(temperature) == float("inf"):
-        raise ValueError(f"temperature={temperature!r}: expected a finite value > 0")
-    if isinstance(top_k, bool) or int(top_k) != top_k or int(top_k) < 0:
-        raise ValueError(f"top_k={top_k!r}: expected an int >= 0 (0: off)")
-    if not 0.0 < float(top_p) <= 1.0:
-        raise ValueError(f"top_p={top_p!r}: expected a value in (0, 1]")
-    if not float(pen) > 0 or float(pen) == float("inf"):
-        raise ValueError(f"repetition_penalty={pen!r}: expected a finite value > 0")
-    return bool(do_sample), float(temperature), int(top_k), float(top_p), float(pen)
-
-
-def check_stop_words_ids(stop_words_ids):
-    """The `stop_words_ids` keyword (the reference's name, minigpt_base.py:387) -> a tuple of token-id tuples: a list of token-id
-    lists (or 1-d tensors, as conversation.py builds them), an int entry read as a one-token sequence, as the reference's `[2]` is.
-    None -> ().  ValueError naming the offending entry for more than 8 sequences, a sequence outside 1..8 tokens or a negative id."""
-    if stop_words_ids is None:
-        return ()
-    if isinstance(stop_words_ids, (str, bytes)) or not hasattr(stop_words_ids, "__iter__"):
-        raise ValueError(f"stop_words_ids={stop_words_ids!r}: expected None or a list of token-id lists (a text goes to stop_text)")
-    entries = stop_words_ids.tolist() if hasattr(stop_words_ids, "tolist") else list(stop_words_ids)
-    if len(entries) > MAX_STOP_SEQS:
-        raise ValueError(f"stop_words_ids: {len(entries)} sequences (at most {MAX_STOP_SEQS})")
-    out = []
-    for k, entry in enumerate(entries):
-        entry = entry.tolist() if hasattr(entry, "tolist") else entry
-        ids = [entry] if isinstance(entry, int) and not isinstance(entry, bool) else entry
-        if isinstance(ids, (str, bytes)) or not isinstance(ids, (list, tuple)) or \
-                any(isinstance(t, bool) or not isinstance(t, int) for t in ids):
-            raise ValueError(f"stop_words_ids[{k}]={entry!r}: expected a list of token ids or one token id")
-        if not 1 <= len(ids) <= MAX_STOP_LEN:
-            raise ValueError(f"stop_words_ids[{k}]={entry!r}: {len(ids)} tokens (a sequence has 1..{MAX_STOP_LEN})")
-        if min(ids) < 0:
-            raise ValueError(f"stop_words_ids[{k}]={entry!r}: a negative token id")
-        out.append(tuple(ids))
-    return tuple(out)
-
-
-def stop_sequences_criteria(stop_seqs):
-    """The rule as a transformers StoppingCriteria for the HF path: a bool [B] per step, True for the rows whose generated tokens end
-    in a sequence; `generate` marks such rows finished and pads them, as it does for an EOS.  With `inputs_embeds` and no input ids
-    the ids `generate` hands over are the generated tokens only, which is what the rule compares."""
-    from transformers import StoppingCriteria, StoppingCriteriaList
-
-    class StopSequences(StoppingCriteria):
-        def __init__(self, seqs):
-            self.seqs = [list(s) for s in seqs]
-
-        def __call__(self, input_ids, scores, **kwargs):
-            done = torch.zeros(input_ids.shape[0], dtype=torch.bool, device=input_ids.device)
-            for s in self.seqs:
-                if len(s) <= input_ids.shape[1]:
-                    want = torch.tensor(s, dtype=input_ids.dtype, device=input_ids.device)
-                    done = done | (input_ids[:, input_ids.shape[1] - len(s):] == want).all(dim=1)
-            return done
-
-    return StoppingCriteriaList([StopSequences(stop_seqs)])
 
 
 class WordHashTokenizer:
@@ -261,666 +94,6 @@ class WordHashTokenizer:
             else:
                 out.append(f"w{t}")
         return " ".join(out)
-
-
-def left_pad_embeds(batch_embs, bucket=None):
-    """Left padding of prompts of different lengths (minigpt_base.py:407-416): `batch_embs` is a list of tensors [n_i, len_i, hidden]
-    (n_i rows that share one length; the reference's loop has n_i = 1) -> (embeds [B, L, hidden] with zeros on the pad positions,
-    attention mask [B, L] int, starts [B] int32 = pad positions per row), B = sum n_i, L = the longest length, rounded up to a
-    multiple of `bucket` when that is set.  Row b's real tokens sit at positions starts[b] .. L-1.  Pure tensor arithmetic on the
-    inputs' device (CPU tensors work); a row with no real token is a ValueError."""
-    if bucket is not None and (isinstance(bucket, bool) or not isinstance(bucket, int) or bucket < 1):
-        raise ValueError(f"bucket={bucket!r}: expected None or an int >= 1")
-    if not batch_embs:
-        raise ValueError("left_pad_embeds: no rows")
-    lens = [int(e.shape[1]) for e in batch_embs]
-    if min(lens) < 1:
-        raise ValueError(f"left_pad_embeds: row group {lens.index(min(lens))} has no real token (length 0)")
-    L = max(lens)
-    if bucket:
-        L = (L + bucket - 1) // bucket * bucket
-    first = batch_embs[0]
-    B = sum(int(e.shape[0]) for e in batch_embs)
-    embs = torch.zeros([B, L, first.shape[2]], dtype=first.dtype, device=first.device)
-    attn_mask = torch.zeros([B, L], dtype=torch.int, device=first.device)
-    starts = torch.empty([B], dtype=torch.int32, device=first.device)
-    row = 0
-    for emb, n in zip(batch_embs, lens):
-        rows = int(emb.shape[0])
-        embs[row:row + rows, L - n:] = emb
-        attn_mask[row:row + rows, L - n:] = 1
-        starts[row:row + rows] = L - n
-        row += rows
-    return embs, attn_mask, starts
-
-
-def pack_row_candidates(cand_tokens):
-    """Per-row candidates for the native scoring pass (cgpt_llm_score_ragged): `cand_tokens[c][b]` = the token ids (a sequence of
-    ints or a 1-D tensor, at least one) of candidate c for row b -> (table [B, C, Tmax] int64 with zeros behind each real length,
-    lens [B, C] int32 = the real lengths, T = [T_c] = the longest length of candidate c over the rows (a list of ints), S = the
-    tail slots per row, sum of T_c - 1: a one-token candidate owns none).  Pure CPU arithmetic; the engine's limits (S <= 64,
-    C <= 64) are the caller's to compare against.  A candidate without a token, or rows that disagree in number, are a ValueError."""
-    if not cand_tokens:
-        raise ValueError("pack_row_candidates: no candidate")
-    rows = [[[int(v) for v in (ids.tolist() if hasattr(ids, "tolist") else ids)] for ids in cand] for cand in cand_tokens]
-    B = len(rows[0])
-    if B < 1 or any(len(cand) != B for cand in rows):
-        raise ValueError("pack_row_candidates: cand_tokens[c][b] needs one token list per candidate and row, at least one row")
-    for c, cand in enumerate(rows):
-        for b, ids in enumerate(cand):
-            if not ids:
-                raise ValueError(f"pack_row_candidates: candidate {c} of row {b} has no token")
-    T = [max(len(ids) for ids in cand) for cand in rows]
-    table = torch.zeros((B, len(rows), max(T)), dtype=torch.long)
-    lens = torch.empty((B, len(rows)), dtype=torch.int32)
-    for c, cand in enumerate(rows):
-        for b, ids in enumerate(cand):
-            table[b, c, :len(ids)] = torch.tensor(ids, dtype=torch.long)
-            lens[b, c] = len(ids)
-    return table, lens, T, sum(t - 1 for t in T)
-
-
-def greedy_decode_parity(hf_tokens, hf_scores, tokens, eps):
-    """Compare a greedy decode `tokens` [B, n] with HF `generate`'s `hf_tokens` [B, <= n] row by row, given HF's per-step processed
-    scores `hf_scores` [B, steps, V] (fp32).  Two greedy decoders of the SAME fp16 model can only part ways at a step where HF's own
-    top-2 margin is within the logit noise of the two paths (another GEMM / attention kernel rounds the fp16 logits differently), after
-    which the contexts differ and nothing more can be said about that row.  Returns a dict: `identical` rows, `decisive` rows (every
-    step's margin > eps: these MUST be identical), `violations` = rows whose first divergence sits at a step with margin > eps."""
-    B = hf_tokens.shape[0]
-    S = min(hf_tokens.shape[1], tokens.shape[1], hf_scores.shape[1])
-    top2 = hf_scores[:, :S].float().topk(2, dim=-1).values
-    margin = top2[..., 0] - top2[..., 1]                                  # [B, S]; inf where only one candidate is finite
-    margin = torch.nan_to_num(margin, nan=float("inf"))
-    neq = tokens[:, :S] != hf_tokens[:, :S]
-    diverged = neq.any(dim=1)
-    first = torch.where(diverged, neq.float().argmax(dim=1), torch.zeros(B, dtype=torch.long, device=neq.device))
-    m_at = margin.gather(1, first[:, None])[:, 0]
-    violations = (diverged & (m_at > eps)).nonzero().flatten().tolist()
-    decisive = (margin > eps).all(dim=1)
-    return {"identical": int((~diverged).sum()), "diverged": int(diverged.sum()), "decisive": int(decisive.sum()),
-            "decisive_identical": int((decisive & ~diverged).sum()), "violations": violations,
-            "max_margin_at_divergence": float(m_at[diverged].max()) if bool(diverged.any()) else 0.0}
-
-
-def fp16_ulp(x):
-    """Spacing of fp16 at magnitude x (normal range)."""
-    import math
-    return 2.0 ** (math.floor(math.log2(max(float(x), 6.2e-5))) - 10)
-
-
-# ---- the weight law of weights="int8" (csrc/llm.hip: llm_quant_rows_kernel; include/cgpt.h: CGPT_LLM_W_INT8), in plain torch
-LAYER_LINEARS = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj",
-                 "mlp.down_proj")
-
-
-def quantize_rows_int8(w):
-    """Row-wise absmax int8 of an fp16 `nn.Linear.weight` [N, K] -> (q int8 [N, K], s fp16 [N]):
-        s_n  = fp16(absmax_k |w_nk| / 127)                     the division in fp32, then one rounding to fp16
-        q_nk = clamp(rint(fp32(w_nk) / fp32(s_n)), -127, 127)  fp32 division, round to nearest even; q = 0 where s_n = 0
-    (a zero row, or an absmax so small that absmax / 127 underflows fp16).  Works on CPU tensors."""
-    if w.dtype != torch.float16 or w.dim() != 2:
-        raise ValueError(f"quantize_rows_int8: expected an fp16 matrix [N, K], got {w.dtype} {tuple(w.shape)}")
-    s = (w.abs().amax(dim=1).float() / 127.0).to(torch.float16)
-    sf = s.float()[:, None]
-    live = sf != 0
-    q = torch.round(w.float() / torch.where(live, sf, torch.ones_like(sf))).clamp_(-127, 127)
-    return torch.where(live, q, torch.zeros_like(q)).to(torch.int8), s
-
-
-def dequantize_rows_int8(q, s):
-    """W'_nk = fp16(q_nk) * s_n as ONE fp16 multiply (q is exact in fp16): what an int8 handle multiplies by."""
-    if q.dtype != torch.int8 or s.dtype != torch.float16 or q.dim() != 2 or tuple(s.shape) != (q.shape[0],):
-        raise ValueError("dequantize_rows_int8: expected q int8 [N, K] and s fp16 [N]")
-    return q.to(torch.float16) * s[:, None]
-
-
-def int8_state_dict(llama_model, device=None):
-    """The state dict of `llama_model` with the seven linears of every layer replaced by W' = dequantize(quantize(W)); everything else
-    (embed_tokens, lm_head, the RMSNorm weights) as it is.  Loadable into an HF twin of the model: by the definition of
-    weights="int8" the native engine on `llama_model` computes, bit for bit, what the fp16 native engine computes on that twin.
-    device: where the law is evaluated (default: where each weight lives; "cpu" for the reference evaluation); the results go back to
-    the weight's own device."""
-    out = {}
-    for name, w in llama_model.state_dict().items():
-        if name.startswith("model.layers.") and name.endswith(".weight") and name.split(".", 3)[3][:-len(".weight")] in LAYER_LINEARS:
-            src = w.detach().to(device or w.device)
-            out[name] = dequantize_rows_int8(*quantize_rows_int8(src)).to(w.device)
-        else:
-            out[name] = w.detach().clone()
-    return out
-
-
-# ---- the activation law of activations="int8" (csrc/llm_gemm_i8.hip; include/cgpt.h: cgpt_llm_config_act), in plain torch: the oracle
-def quantize_act_rows_int8(x, threshold=6.0):
-    """Row-wise int8 codes of fp16 activations x [M, K] with a per-row outlier split -> (a int8 [M, K], s_a fp32 [M], outlier bool [M, K]):
-        outlier_mk = threshold > 0 and |x_mk| >= threshold
-        s_a[m]     = max over the row's non-outliers |x_mk| / 127        fp32 division; kept in fp32
-        a_mk       = clamp(rint(fp32(x_mk) / s_a[m]), -127, 127)          round to nearest even; 0 for outliers; the row 0 where s_a = 0
-    Every row is a function of that row alone.  Works on CPU tensors."""
-    if x.dtype != torch.float16 or x.dim() != 2:
-        raise ValueError(f"quantize_act_rows_int8: expected an fp16 matrix [M, K], got {x.dtype} {tuple(x.shape)}")
-    xf = x.float()
-    t = float(threshold)
-    out = (xf.abs() >= t) if t > 0 else torch.zeros_like(xf, dtype=torch.bool)
-    amax = torch.where(out, torch.zeros_like(xf), xf.abs()).amax(dim=1)
-    s = amax / torch.full_like(amax, 127.0)                            # tensor / tensor: a true division on every device
-    sf = s[:, None]
-    live = (sf != 0) & ~out
-    a = torch.round(xf / torch.where(sf != 0, sf, torch.ones_like(sf))).clamp_(-127, 127)
-    return torch.where(live, a, torch.zeros_like(a)).to(torch.int8), s, out
-
-
-def llm_int8_linear(x, q, s_w, threshold=6.0):
-    """The linear of an activations-int8 handle on fp16 rows x [M, K] against int8 weights q [N, K] with fp16 row scales s_w [N]
-    (`quantize_rows_int8`) -> v fp32 [M, N], before the epilogue's rounding:
-        acc = a . q^T in integers (exact);   y = fp32(acc) * (s_a * fp32(s_w));
-        o   = sum over the row's outliers in ascending k of fp32(x_k) * fp32(W'_nk), sequential fp32 from 0, W' = fp16(q) * s_w;
-        v   = y + o.
-    Plain torch on the tensors' device; the integer product runs in int64 on the CPU and in fp64 elsewhere (|acc| < 2^31: exact)."""
-    if q.dtype != torch.int8 or s_w.dtype != torch.float16 or q.dim() != 2 or tuple(s_w.shape) != (q.shape[0],) or x.shape[-1] != q.shape[1]:
-        raise ValueError("llm_int8_linear: expected x fp16 [M, K], q int8 [N, K] and s_w fp16 [N]")
-    a, s_a, out = quantize_act_rows_int8(x, threshold)
-    if x.is_cuda:
-        acc = (a.double() @ q.double().t()).to(torch.int32)
-    else:
-        acc = (a.long() @ q.long().t()).to(torch.int32)
-    y = acc.to(torch.float32) * (s_a[:, None] * s_w.float()[None, :])
-    o = torch.zeros_like(y)
-    cnt = out.sum(dim=1)
-    most = int(cnt.max()) if out.numel() else 0
-    if most:
-        wp = dequantize_rows_int8(q, s_w).float()                      # [N, K]
-        xf = x.float()
-        # the j-th outlier of every row at once: a stable sort lists a row's outlier positions first, in ascending k
-        order = torch.sort(out.to(torch.uint8), dim=1, descending=True, stable=True).indices[:, :most]
-        for j in range(most):                                          # sequential fp32, ascending k; every product is exact in fp32
-            kj = order[:, j]
-            term = xf.gather(1, kj[:, None]) * wp[:, kj].t()
-            o = torch.where((cnt > j)[:, None], o + term, o)
-    return y + o
-
-
-class _ActInt8Linear(torch.nn.Module):
-    """A bias-free linear evaluated by the activation law: input cast to fp16, `llm_int8_linear`, fp16 of v, in the input's dtype."""
-
-    def __init__(self, weight, threshold):
-        super().__init__()
-        q, s = quantize_rows_int8(weight.detach().to(torch.float16).cpu())      # the weight law's reference evaluation (as int8_state_dict's)
-        self.register_buffer("q", q.to(weight.device), persistent=False)
-        self.register_buffer("s_w", s.to(weight.device), persistent=False)
-        self.weight = weight                                            # the parameter stays: the state dict is unchanged
-        self.threshold = float(threshold)
-        self.in_features, self.out_features, self.bias = weight.shape[1], weight.shape[0], None
-
-    def forward(self, x):
-        x2 = x.reshape(-1, x.shape[-1]).to(torch.float16)
-        v = llm_int8_linear(x2, self.q, self.s_w, self.threshold).to(torch.float16)
-        return v.to(x.dtype).reshape(*x.shape[:-1], self.out_features)
-
-
-def act_int8_twin(llama_model, threshold=6.0):
-    """A copy of an HF `LlamaForCausalLM` whose seven linears per layer evaluate the law of activations="int8" (`llm_int8_linear` on
-    `quantize_rows_int8` of the fp16 weight, fp16 of the result): the oracle of the mode, in the role `int8_state_dict` and
-    `expand_kv_state_dict` have.  Everything else (embed_tokens, lm_head, the norms, attention, every rounding of the model's dtype) is
-    the copy's own, so an fp32 copy is the reference point and an fp16 copy is HF's fp16 evaluation of the same law.  The state dict
-    is that of `llama_model`.  Works on CPU and GPU."""
-    import copy
-    twin = copy.deepcopy(llama_model)
-    for layer in twin.model.layers:
-        for name in LAYER_LINEARS:
-            parent_name, attr = name.split(".")
-            parent = getattr(layer, parent_name)
-            lin = getattr(parent, attr)
-            if lin.bias is not None:
-                raise ValueError(f"act_int8_twin: {name} carries a bias (bias-free linears required)")
-            setattr(parent, attr, _ActInt8Linear(lin.weight, threshold))
-    return twin.eval()
-
-
-GQA_RATIOS = (1, 2, 4, 8)                                              # heads / kv_heads the grouped kernels are instantiated for
-
-
-def expand_kv_state_dict(llama_model):
-    """The state dict of the multi-head twin of a grouped-query `llama_model`: every `k_proj` / `v_proj` weight [kv_heads * d, hidden]
-    becomes [heads * d, hidden] with each head's block of d rows repeated G = heads / kv_heads times in `repeat_interleave` order
-    (twin head h = K/V head h // G, which is HF's `repeat_kv`); everything else as it is.  Loadable into an HF model of the same
-    config with `num_key_value_heads = num_attention_heads`, which then computes what the grouped model computes: the oracle of
-    grouped_kv=True, in the role `int8_state_dict` has for weights="int8".  Plain torch; works on CPU tensors."""
-    cfg = llama_model.config
-    heads = int(cfg.num_attention_heads)
-    kv = int(getattr(cfg, "num_key_value_heads", None) or heads)
-    if kv < 1 or heads % kv:
-        raise ValueError(f"expand_kv_state_dict: num_key_value_heads {kv} does not divide num_attention_heads {heads}")
-    G = heads // kv
-    out = {}
-    for name, w in llama_model.state_dict().items():
-        if name.endswith("self_attn.k_proj.weight") or name.endswith("self_attn.v_proj.weight"):
-            d = w.shape[0] // kv
-            out[name] = w.detach().view(kv, d, w.shape[1]).repeat_interleave(G, dim=0).reshape(heads * d, w.shape[1]).clone()
-        else:
-            out[name] = w.detach().clone()
-    return out
-
-
-class _LinearRoute:
-    """Routes the bias-free fp16 `nn.Linear` layers of a frozen decoder through libcgpt's MFMA GEMM (`cgpt_linear_f16`, the kernel
-    of the ViT's qkv / proj / MLP) for calls with at least `min_rows` rows, i.e. the PREFILL of a Monte-Carlo batch (200 rows x 44
-    tokens = 8 800 rows); decode steps (one row per copy) stay with the vendor library.  One patch per module; the patch is inert
-    outside `enabled()`, and the switch is a context variable (per thread / per task), so another thread or another classifier that
-    calls the same shared decoder meanwhile is not routed.  Eligibility (fp16, contiguous, on the device, no bias, K in 64s, N in 256s)
-    is re-checked at every call: after a `.to()`, a dtype change or a weight swap (a LoRA merge) the original forward runs."""
-    import contextvars as _cv
-    _active = _cv.ContextVar("cgpt_linear_route", default=False)
-
-    @staticmethod
-    def _eligible(m):
-        w = m.weight
-        return (m.bias is None and w.dtype == torch.float16 and w.is_cuda and w.is_contiguous()
-                and w.shape == (m.out_features, m.in_features) and m.in_features % 64 == 0 and m.out_features % 256 == 0)
-
-    @classmethod
-    def install(cls, model, min_rows=1024):
-        import ctypes as C
-        from . import _lib
-        L = _lib.lib()
-        n = 0
-        for m in model.modules():
-            if not isinstance(m, torch.nn.Linear):
-                continue
-            if getattr(m, "_cgpt_routed", False):                       # patched by an earlier classifier on the same module
-                n += 1
-                continue
-            if not cls._eligible(m):                                    # W must be readable for whole 256-row tiles, K in 64s
-                continue
-            orig = m.forward
-
-            def fwd(x, m=m, orig=orig):
-                rows = x.numel() // x.shape[-1] if x.shape[-1] else 0
-                if (not cls._active.get() or rows < min_rows or x.dtype != torch.float16 or not x.is_cuda
-                        or x.device != m.weight.device or not cls._eligible(m)):
-                    return orig(x)
-                K, N = m.in_features, m.out_features
-                a = x.reshape(rows, K)
-                if rows % 256 or not a.is_contiguous():                 # the kernel reads whole 256-row tiles: pad rows exist but are
-                    pad = x.new_empty(((rows + 255) // 256 * 256, K))   # never stored from (their garbage stays in their own outputs)
-                    pad[:rows].copy_(a)
-                    a = pad
-                out = x.new_empty((rows, N))
-                st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-                _lib.check(L.cgpt_linear_f16(C.c_void_p(a.data_ptr()), K, C.c_void_p(m.weight.data_ptr()), K, None,
-                                             C.c_void_p(out.data_ptr()), N, None, N, rows, N, K, 0, st))
-                return out.view(*x.shape[:-1], N)
-            m.forward = fwd
-            m._cgpt_routed = True
-            n += 1
-        return n
-
-    @classmethod
-    def enabled(cls):
-        import contextlib
-
-        @contextlib.contextmanager
-        def ctx():
-            token = cls._active.set(True)
-            try:
-                yield
-            finally:
-                cls._active.reset(token)
-        return ctx()
-
-
-def hip_decode_unsupported(llama_model, max_batch=None, grouped_kv=False, activations="fp16"):
-    """Every property of `llama_model` (and of the classifier batch) that keeps it off the native token step (`decode="hip"`,
-    csrc/llm.hip), as a list of sentences; empty = supported.  The step kernels are written for HF `LlamaForCausalLM` in fp16 on
-    a HIP device: bias-free linears, RMSNorm, `rotate_half` rotary with the default (unscaled) rope_theta law, as many K/V heads
-    as query heads, head size 128, SwiGLU, no sliding window -- Vicuna-7B / 13B.  ALL failing properties are collected, so one
-    message names them all.
-    grouped_kv=True (the engine's grouped-query mode): fewer K/V heads than query heads are accepted when they
-    divide them and heads / kv_heads is 1, 2, 4 or 8 -- Llama-3-8B (32 / 8), Llama-2-70B's shape (64 / 8).
-    activations="int8" (DESIGN.md 4.4.7): hidden_size and intermediate_size must be multiples of 128, because one K-tile of the int8
-    kernel is 128 bytes -- 7B, 13B, Llama-3-8B and 70B all are."""
-    cfg = getattr(llama_model, "config", None)
-    bad = []
-    if type(llama_model).__name__ != "LlamaForCausalLM" or cfg is None:
-        return [f"architecture: {type(llama_model).__name__} (HF LlamaForCausalLM required)"]
-    prm = next(llama_model.parameters())
-    if not (prm.is_cuda and getattr(torch.version, "hip", None)):
-        bad.append(f"device: {prm.device} (a HIP device is required)")
-    dtypes = sorted({str(q.dtype) for q in llama_model.parameters()})
-    if dtypes != ["torch.float16"]:
-        bad.append(f"dtype: {', '.join(dtypes)} (torch.float16 required)")
-    heads, hidden = int(cfg.num_attention_heads), int(cfg.hidden_size)
-    head_dim = int(getattr(cfg, "head_dim", None) or hidden // heads)
-    if head_dim != 128 or hidden != heads * 128:
-        bad.append(f"head size: head_dim {head_dim} with hidden_size {hidden} / {heads} heads (head_dim 128 and hidden = heads x 128 required)")
-    kv = int(getattr(cfg, "num_key_value_heads", None) or heads)
-    if grouped_kv:
-        if kv < 1 or heads % kv or heads // kv not in GQA_RATIOS:
-            bad.append(f"K/V heads: num_key_value_heads {kv} with num_attention_heads {heads} (grouped_kv takes a count that divides "
-                       f"the query heads with a ratio in {list(GQA_RATIOS)})")
-    elif kv != heads:
-        bad.append(f"K/V heads: num_key_value_heads {kv} != num_attention_heads {heads} (grouped-query attention is not supported)")
-    with_bias = [n for n, m in llama_model.named_modules() if isinstance(m, torch.nn.Linear) and m.bias is not None]
-    if getattr(cfg, "attention_bias", False) or getattr(cfg, "mlp_bias", False) or with_bias:
-        bad.append(f"biases: {len(with_bias)} linear layers carry a bias (bias-free linears required)")
-    rope = getattr(cfg, "rope_parameters", None) or getattr(cfg, "rope_scaling", None) or {}
-    rope_type = rope.get("rope_type", rope.get("type", "default")) if isinstance(rope, dict) else str(rope)
-    if rope_type != "default":
-        bad.append(f"rotary law: rope type {rope_type!r} (only the default, unscaled rope_theta law is supported)")
-    if getattr(cfg, "sliding_window", None):
-        bad.append(f"sliding window: {cfg.sliding_window} (full attention required)")
-    if getattr(cfg, "hidden_act", "silu") != "silu":
-        bad.append(f"activation: {cfg.hidden_act} (SwiGLU with silu required)")
-    for name, val in (("hidden_size", hidden), ("intermediate_size", int(cfg.intermediate_size)), ("vocab_size", int(cfg.vocab_size))):
-        if val % 64:
-            bad.append(f"shape: {name} {val} is not a multiple of 64")
-    if activations == "int8":
-        for name, val in (("hidden_size", hidden), ("intermediate_size", int(cfg.intermediate_size))):
-            if val % 128:
-                bad.append(f'shape: {name} {val} is not a multiple of 128 (activations="int8": one K-tile of the int8 kernel is 128 bytes)')
-    if max_batch is not None and int(max_batch) > 256:
-        bad.append(f"batch: max_batch {int(max_batch)} > 256 rows (one GEMM row tile)")
-    eos = getattr(getattr(llama_model, "generation_config", None), "eos_token_id", None)      # as greedy_tokens resolves it
-    eos = getattr(cfg, "eos_token_id", None) if eos is None else eos
-    if isinstance(eos, (list, tuple)) and len(eos) > 8:
-        bad.append(f"EOS ids: {len(eos)} end-of-sequence ids (the token select takes at most 8)")
-    return bad
-
-
-def _rope_theta(cfg):
-    rope = getattr(cfg, "rope_parameters", None) or getattr(cfg, "rope_scaling", None) or {}
-    theta = rope.get("rope_theta") if isinstance(rope, dict) else None
-    return float(theta or getattr(cfg, "rope_theta", None) or 10000.0)
-
-
-class _HipDecoder:
-    """The native token step of a frozen LlamaForCausalLM (`cgpt_llm_*`, include/cgpt.h): validates the model, creates the handle
-    and hands it the module's own fp16 parameters ONCE (the library keeps fused copies: 2 bytes per parameter more HBM, 13.5 GB at
-    7B; a later change of the module's weights is not seen; with weights="int8" the seven linears of every layer are held as row-wise
-    absmax int8 instead, quantised on the device at load, 7.2 GB at 7B -- see `quantize_rows_int8`).  `greedy` enqueues the whole loop after the prefill on the current
-    stream -- no host sync, capturable -- on the K/V buffers the prefill filled, in place."""
-    MAX_LEN = 4096                                                     # positions the rotary table covers (prompt + new tokens)
-
-    def __init__(self, llama_model, max_batch, weights="fp16", early_stop=False, grouped_kv=False, activations="fp16", int8_threshold=6.0,
-                 outlier_cap=64):
-        import ctypes as C
-        from . import _lib
-        if weights not in _lib.LLM_WEIGHT_FORMATS:
-            raise ValueError(f'weights={weights!r}: expected "fp16" or "int8"')
-        if activations not in _lib.LLM_ACT_FORMATS:
-            raise ValueError(f'activations={activations!r}: expected "fp16" or "int8"')
-        if activations == "int8" and weights != "int8":
-            raise ValueError('activations="int8" needs weights="int8": int8 activations multiply int8 weights')
-        if activations == "int8" and not 1 <= int(outlier_cap) <= 1024:
-            raise ValueError(f"outlier_cap={outlier_cap!r}: expected 1..1024")
-        self.weights = weights
-        self.activations, self.int8_threshold, self.outlier_cap = activations, float(int8_threshold), int(outlier_cap)
-        self._act_stats = None
-        self.early_stop = bool(early_stop)
-        self._greedy_ran = False                                       # live_steps has nothing to report before the first `greedy`
-        self.stop_sequences = ()                                       # none is the handle's state at create
-        self.grouped_kv = bool(grouped_kv)
-        bad = hip_decode_unsupported(llama_model, max_batch, grouped_kv=self.grouped_kv, activations=activations)
-        if bad:
-            raise ValueError('decode="hip" does not support this decoder -- ' + "; ".join(bad))
-        self._C, self._lib_mod, self.L = C, _lib, _lib.lib()
-        cfg = llama_model.config
-        self.device = next(llama_model.parameters()).device
-        self.layers, self.heads, self.vocab = int(cfg.num_hidden_layers), int(cfg.num_attention_heads), int(cfg.vocab_size)
-        # K/V heads of the caches every entry works on: the model's own count under grouped_kv, the query heads otherwise
-        self.kv_heads = int(getattr(cfg, "num_key_value_heads", None) or self.heads) if self.grouped_kv else self.heads
-        self.max_batch = int(max_batch)
-        # fp16 handles pass the config up to max_len, which every build of the library accepts (an A/B against an older build loads it
-        # through CGPT_LIB_PATH); weight_format travels only when it says something
-        # and so does grouped_kv: the extended struct (cgpt_llm_config_gqa) is sent only when the flag is set
-        # and so does the activation format (cgpt_llm_config_act)
-        size = (C.sizeof(_lib.LlmConfigAct) if activations != "fp16" else C.sizeof(_lib.LlmConfigGqa) if self.grouped_kv else
-                C.sizeof(_lib.LlmConfig) if weights != "fp16" else _lib.LLM_CONFIG_SIZE_F16)
-        c = _lib.LlmConfig(struct_size=size, weight_format=_lib.LLM_WEIGHT_FORMATS[weights], device=self.device.index or 0, hidden=int(cfg.hidden_size),
-                           layers=self.layers, heads=self.heads, kv_heads=self.kv_heads, head_dim=128, mlp=int(cfg.intermediate_size),
-                           vocab=self.vocab, rms_eps=float(cfg.rms_norm_eps), rope_theta=_rope_theta(cfg),
-                           max_batch=self.max_batch, max_len=self.MAX_LEN)
-        self.handle = C.c_void_p()
-        ext = _lib.LlmConfigGqa(base=c, grouped_kv=int(self.grouped_kv), reserved=0)     # create reads past `base` only when the size says so
-        act = _lib.LlmConfigAct(gqa=ext, act_format=_lib.LLM_ACT_FORMATS[activations], act_threshold=self.int8_threshold,
-                                outlier_cap=self.outlier_cap, reserved2=0)
-        _lib.check(self.L.cgpt_llm_create(C.byref(act.gqa.base), C.byref(self.handle)))
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        wanted = ["model.embed_tokens.weight", "model.norm.weight", "lm_head.weight"]
-        for i in range(self.layers):
-            wanted += [f"model.layers.{i}.self_attn.{n}_proj.weight" for n in "qkvo"]
-            wanted += [f"model.layers.{i}.mlp.{n}_proj.weight" for n in ("gate", "up", "down")]
-            wanted += [f"model.layers.{i}.{n}_layernorm.weight" for n in ("input", "post_attention")]
-        sd = llama_model.state_dict()
-        for name in wanted:
-            w = sd[name].detach()
-            assert w.dtype == torch.float16 and w.device == self.device, name
-            w = w.contiguous()
-            _lib.check(self.L.cgpt_llm_load_weight_f16(self.handle, name.encode(), C.c_void_p(w.data_ptr()), w.numel(), st))
-        torch.cuda.current_stream(self.device).synchronize()           # contiguous() temporaries may go once the copies have run
-        if self.early_stop:                                            # off is the handle's state at create: nothing is called for it
-            _lib.check(self.L.cgpt_llm_set_early_stop(self.handle, 1))
-
-    @property
-    def weight_bytes(self):
-        """Bytes the handle holds for weight matrices, row scales and the dequantisation scratch (cgpt_llm_weight_bytes: the
-        library's own accounting).  None on a build of the library that predates the entry (CGPT_LIB_PATH A/B runs)."""
-        C = self._C
-        if not hasattr(self.L, "cgpt_llm_weight_bytes"):
-            return None
-        n = C.c_int64()
-        self._lib_mod.check(self.L.cgpt_llm_weight_bytes(self.handle, C.byref(n)))
-        return int(n.value)
-
-    def act_stats(self):
-        """{rows, outliers, max_outliers_per_row, overflow_rows} of the native calls since the last read (cgpt_llm_act_stats: one
-        device sync; the counters are reset).  When nothing ran since, the last non-empty reading is returned again.  RuntimeError when
-        a row had more outliers than `outlier_cap`: its result is not the law's."""
-        C = self._C
-        if self.activations != "int8":
-            raise RuntimeError('act_stats: the engine was built with activations="fp16"')
-        v = (C.c_int64 * 4)()
-        self._lib_mod.check(self.L.cgpt_llm_act_stats(self.handle, v))
-        if v[0] > 0 or self._act_stats is None:
-            self._act_stats = {"rows": int(v[0]), "outliers": int(v[1]), "max_outliers_per_row": int(v[2]), "overflow_rows": int(v[3])}
-        if self._act_stats["overflow_rows"] > 0:
-            stats, self._act_stats = self._act_stats, None
-            raise RuntimeError(f'activations="int8": {stats["overflow_rows"]} of {stats["rows"]} activation rows had more than '
-                               f'outlier_cap={self.outlier_cap} outliers (the largest row: {stats["max_outliers_per_row"]}); their '
-                               "results are not the law's -- raise outlier_cap (up to 1024) or int8_threshold")
-        return dict(self._act_stats)
-
-    def close(self):
-        if getattr(self, "handle", None) is not None and self.handle.value:
-            self.L.cgpt_llm_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _cache_tables(self, k_bufs, v_bufs, B, need_len):
-        """Host tables of the per-layer K / V device pointers, after checking every buffer is what the kernels index:
-        [B, heads, len_stride, 128] fp16 ([B, kv_heads, len_stride, 128] under grouped_kv), contiguous, on the handle's device, long
-        enough for the last appended row."""
-        C = self._C
-        assert len(k_bufs) == len(v_bufs) == self.layers, "one K and one V buffer per layer"
-        stride = int(k_bufs[0].shape[2])
-        assert need_len <= stride and need_len <= self.MAX_LEN, (need_len, stride, self.MAX_LEN)
-        for t in list(k_bufs) + list(v_bufs):
-            assert (t.dtype == torch.float16 and t.device == self.device and t.is_contiguous()
-                    and tuple(t.shape) == (B, self.kv_heads, stride, 128)), (tuple(t.shape), t.dtype, t.device)
-        kp = (C.c_void_p * self.layers)(*[t.data_ptr() for t in k_bufs])
-        vp = (C.c_void_p * self.layers)(*[t.data_ptr() for t in v_bufs])
-        return kp, vp, stride
-
-    def _starts_ptr(self, starts, B):
-        """`starts` [B] int32 on the handle's device (pad positions per row of a left-padded batch; the kernels read it when they run,
-        so a captured call sees its contents at every replay) -> the pointer the _ragged entries take."""
-        assert (starts.dtype == torch.int32 and starts.device == self.device and starts.is_contiguous()
-                and tuple(starts.shape) == (B,)), (tuple(starts.shape), starts.dtype, starts.device)
-        return self._C.c_void_p(starts.data_ptr())
-
-    def step(self, tokens, pos, k_bufs, v_bufs, starts=None):
-        """One teacher-forced step: tokens [B] int64 at position `pos` -> logits [B, vocab] fp32; K / V row `pos` appended in place.
-        starts (or None: the plain entry): left-padded rows, `pos` is the position in the padded buffer."""
-        C = self._C
-        B = int(tokens.shape[0])
-        assert tokens.dtype == torch.int64 and tokens.device == self.device and tokens.is_contiguous() and 1 <= B <= self.max_batch
-        kp, vp, stride = self._cache_tables(k_bufs, v_bufs, B, int(pos) + 1)
-        logits = torch.empty((B, self.vocab), dtype=torch.float32, device=self.device)
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        if starts is None:
-            self._lib_mod.check(self.L.cgpt_llm_step(self.handle, C.c_void_p(tokens.data_ptr()), B, int(pos), kp, vp, stride,
-                                                     C.c_void_p(logits.data_ptr()), st))
-        else:
-            self._lib_mod.check(self.L.cgpt_llm_step_ragged(self.handle, C.c_void_p(tokens.data_ptr()), B, int(pos),
-                                                            self._starts_ptr(starts, B), kp, vp, stride, C.c_void_p(logits.data_ptr()), st))
-        return logits
-
-    def prefill(self, embs, k_bufs, v_bufs, starts=None):
-        """The native prefill: embs [B, L, hidden] fp16 -> last-position logits [B, vocab] fp32; rows 0 .. L-1 of every layer's K / V
-        buffer filled in place.  The workspace is reserved here, for `max_batch` rows of this prompt length, so that batches of any
-        size share one reservation (outside any capture: a captured call must come after an eager one of the same prompt length,
-        which `_generate_graph`'s warm-up run is).  A longer prompt later grows it; the library keeps the replaced buffers until the
-        handle goes, so graphs captured before keep replaying on valid memory.
-        starts (or None: the plain entry): row b is left-padded by starts[b] positions; cache rows starts[b] .. L-1 are filled."""
-        C = self._C
-        B, L, hidden = embs.shape
-        assert (embs.dtype == torch.float16 and embs.device == self.device and embs.is_contiguous() and hidden == self.heads * 128
-                and 1 <= B <= self.max_batch and L >= 1)
-        kp, vp, stride = self._cache_tables(k_bufs, v_bufs, B, L)
-        if not torch.cuda.is_current_stream_capturing():
-            self._lib_mod.check(self.L.cgpt_llm_prefill_reserve(self.handle, self.max_batch, L))
-        logits = torch.empty((B, self.vocab), dtype=torch.float32, device=self.device)
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        if starts is None:
-            self._lib_mod.check(self.L.cgpt_llm_prefill(self.handle, C.c_void_p(embs.data_ptr()), B, int(L), kp, vp, stride,
-                                                        C.c_void_p(logits.data_ptr()), st))
-        else:
-            self._lib_mod.check(self.L.cgpt_llm_prefill_ragged(self.handle, C.c_void_p(embs.data_ptr()), B, int(L),
-                                                               self._starts_ptr(starts, B), kp, vp, stride,
-                                                               C.c_void_p(logits.data_ptr()), st))
-        return logits
-
-    def greedy(self, first_logits, prompt_len, num_new, min_new, eos_ids, pad_id, k_bufs, v_bufs, return_logits=False, starts=None):
-        """The loop of `greedy_tokens` after the prefill: tokens [B, num_new] int64 (and the logits each arg-max saw).
-        starts (or None: the plain entry): the prefill's left padding; `prompt_len` is then the padded length."""
-        C = self._C
-        B, V = first_logits.shape
-        assert (first_logits.dtype == torch.float32 and first_logits.device == self.device and first_logits.is_contiguous()
-                and V == self.vocab and 1 <= B <= self.max_batch and num_new >= 1 and len(eos_ids) <= 8)
-        kp, vp, stride = self._cache_tables(k_bufs, v_bufs, B, prompt_len + num_new - 1)
-        tokens = torch.empty((B, num_new), dtype=torch.int64, device=self.device)
-        steps = torch.empty((B, num_new, V), dtype=torch.float32, device=self.device) if return_logits else None
-        eos = (C.c_int64 * max(1, len(eos_ids)))(*[int(e) for e in eos_ids])
-        self._greedy_ran = True
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        tail = (int(num_new), int(min_new), eos, len(eos_ids), int(pad_id), kp, vp, stride, C.c_void_p(tokens.data_ptr()),
-                C.c_void_p(steps.data_ptr()) if return_logits else None, st)
-        if starts is None:
-            self._lib_mod.check(self.L.cgpt_llm_greedy(self.handle, C.c_void_p(first_logits.data_ptr()), B, int(prompt_len), *tail))
-        else:
-            self._lib_mod.check(self.L.cgpt_llm_greedy_ragged(self.handle, C.c_void_p(first_logits.data_ptr()), B, int(prompt_len),
-                                                              self._starts_ptr(starts, B), *tail))
-        return (tokens, steps) if return_logits else tokens
-
-    def sample(self, first_logits, prompt_len, num_new, min_new, eos_ids, pad_id, k_bufs, v_bufs, settings, draw_ids, seed,
-               return_logits=False, starts=None):
-        """`greedy` with the sampling law in the place of the arg-max (cgpt_llm_sample / cgpt_llm_sample_ragged; `sample_token_law`).
-        settings = (do_sample, temperature, top_k, top_p, repetition_penalty); draw_ids [B] int64 and seed [1] int64 (the 64 bits of
-        the seed) live on the device and are read when the kernels run, so a captured call draws whatever they hold at each replay."""
-        C = self._C
-        B, V = first_logits.shape
-        assert (first_logits.dtype == torch.float32 and first_logits.device == self.device and first_logits.is_contiguous()
-                and V == self.vocab and 1 <= B <= self.max_batch and num_new >= 1 and len(eos_ids) <= 8)
-        assert (draw_ids.dtype == torch.int64 and draw_ids.device == self.device and draw_ids.is_contiguous()
-                and tuple(draw_ids.shape) == (B,)), (tuple(draw_ids.shape), draw_ids.dtype, draw_ids.device)
-        assert seed.dtype == torch.int64 and seed.device == self.device and seed.numel() == 1, (seed.dtype, seed.device)
-        params = self._lib_mod.sample_params(*check_sample_settings(settings))
-        kp, vp, stride = self._cache_tables(k_bufs, v_bufs, B, prompt_len + num_new - 1)
-        tokens = torch.empty((B, num_new), dtype=torch.int64, device=self.device)
-        steps = torch.empty((B, num_new, V), dtype=torch.float32, device=self.device) if return_logits else None
-        eos = (C.c_int64 * max(1, len(eos_ids)))(*[int(e) for e in eos_ids])
-        self._greedy_ran = True
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        tail = (int(num_new), int(min_new), eos, len(eos_ids), int(pad_id), kp, vp, stride, C.c_void_p(tokens.data_ptr()),
-                C.c_void_p(steps.data_ptr()) if return_logits else None, params, C.c_void_p(draw_ids.data_ptr()),
-                C.c_void_p(seed.data_ptr()), st)
-        if starts is None:
-            self._lib_mod.check(self.L.cgpt_llm_sample(self.handle, C.c_void_p(first_logits.data_ptr()), B, int(prompt_len), *tail))
-        else:
-            self._lib_mod.check(self.L.cgpt_llm_sample_ragged(self.handle, C.c_void_p(first_logits.data_ptr()), B, int(prompt_len),
-                                                              self._starts_ptr(starts, B), *tail))
-        return (tokens, steps) if return_logits else tokens
-
-    def set_early_stop(self, on):
-        """cgpt_llm_set_early_stop: read by the next `greedy` when it enqueues; a captured call keeps what it was captured under."""
-        self._lib_mod.check(self.L.cgpt_llm_set_early_stop(self.handle, int(bool(on))))
-        self.early_stop = bool(on)
-
-    def set_stop_sequences(self, seqs):
-        """cgpt_llm_set_stop_sequences: token-id sequences (`check_stop_words_ids`; () or None clears them) at which a row of the next
-        `greedy` finishes besides its EOS ids; read when it enqueues, a captured call keeps what it was captured under."""
-        C = self._C
-        seqs = check_stop_words_ids(seqs)
-        flat = [t for s in seqs for t in s]
-        ids = (C.c_int64 * max(1, len(flat)))(*flat)
-        lens = (C.c_int32 * max(1, len(seqs)))(*[len(s) for s in seqs])
-        self._lib_mod.check(self.L.cgpt_llm_set_stop_sequences(self.handle, ids, lens, len(seqs)))
-        self.stop_sequences = seqs
-
-    def live_steps(self):
-        """cgpt_llm_live_steps after the last `greedy` (or the last replay of a graph that captured it): the token steps that ran.
-        Synchronises the CURRENT stream -- the one the call was enqueued or the graph replayed on; RuntimeError when no greedy has
-        been enqueued."""
-        C = self._C
-        if not self._greedy_ran:
-            raise RuntimeError("live_steps: no native greedy decode has run on this engine yet")
-        n = C.c_int32(-1)
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._lib_mod.check(self.L.cgpt_llm_live_steps(self.handle, C.byref(n), st))
-        return int(n.value)
-
-    MAX_CANDS, MAX_TAIL = 64, 64                                       # SCORE_MAX_CANDS, SCORE_MAX_TAIL (csrc/llm.h)
-
-    def score(self, first_logits, prompt_len, cand_tokens, cand_lens, label_smoothing, k_bufs, v_bufs, starts=None, row_lens=None):
-        """Every candidate on the prompt cache a prefill left (cgpt_llm_score): first_logits [B, vocab] fp32 = that prefill's result,
-        cand_tokens [C, Tmax] int64 on the device, cand_lens = the C token counts (host) -> [B, C] fp32, the SUM over each
-        candidate's tokens of the label-smoothed cross-entropy.  Reads cache rows 0 .. prompt_len-1 and writes none.  The workspace is
-        reserved here (outside any capture), for `max_batch` rows of this call's tail rows.
-        starts and row_lens (both, or both None: the plain entry) -- per-row prompts and candidates (cgpt_llm_score_ragged): starts
-        [B] int32 = the ragged prefill's left padding, `prompt_len` the padded length; cand_tokens [B, C, Tmax], row_lens [B, C] int32 on
-        the device = each row's real length of each candidate, cand_lens = the longest length of each candidate over the rows
-        (`pack_row_candidates`).  Reads cache rows starts[b] .. prompt_len-1 only; sums each row's own tokens."""
-        C = self._C
-        B, V = first_logits.shape
-        assert (starts is None) == (row_lens is None), "starts and row_lens travel together"
-        n, tmax = cand_tokens.shape[-2:]
-        lens = [int(t) for t in cand_lens]
-        assert (first_logits.dtype == torch.float32 and first_logits.device == self.device and first_logits.is_contiguous()
-                and V == self.vocab and 1 <= B <= self.max_batch)
-        assert (cand_tokens.dtype == torch.int64 and cand_tokens.device == self.device and cand_tokens.is_contiguous()
-                and len(lens) == n and tuple(cand_tokens.shape) == ((n, tmax) if starts is None else (B, n, tmax)))
-        if row_lens is not None:
-            assert (row_lens.dtype == torch.int32 and row_lens.device == self.device and row_lens.is_contiguous()
-                    and tuple(row_lens.shape) == (B, n)), (tuple(row_lens.shape), row_lens.dtype, row_lens.device)
-        kp, vp, stride = self._cache_tables(k_bufs, v_bufs, B, int(prompt_len))
-        if not torch.cuda.is_current_stream_capturing():
-            self._lib_mod.check(self.L.cgpt_llm_score_reserve(self.handle, self.max_batch, max(1, sum(t - 1 for t in lens))))
-        out = torch.empty((B, n), dtype=torch.float32, device=self.device)
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        tail = ((C.c_int32 * n)(*lens), n, int(tmax), float(label_smoothing), kp, vp, stride, C.c_void_p(out.data_ptr()), st)
-        if starts is None:
-            self._lib_mod.check(self.L.cgpt_llm_score(self.handle, C.c_void_p(first_logits.data_ptr()), B, int(prompt_len),
-                                                      C.c_void_p(cand_tokens.data_ptr()), *tail))
-        else:
-            self._lib_mod.check(self.L.cgpt_llm_score_ragged(self.handle, C.c_void_p(first_logits.data_ptr()), B, int(prompt_len),
-                                                             self._starts_ptr(starts, B), C.c_void_p(cand_tokens.data_ptr()),
-                                                             C.c_void_p(row_lens.data_ptr()), *tail))
-        return out
 
 
 class MiniGPT4Classifier:
@@ -1157,11 +330,11 @@ class MiniGPT4Classifier:
         if sample == "hip":
             self._sample_settings()                         # a ValueError for a setting the sampler refuses comes now
         # the keyword reaches the engine only when it is set (as `law` reaches an encoder)
-        gqa = {"grouped_kv": True} if grouped_kv else {}
+        engine_kw = {"grouped_kv": True} if grouped_kv else {}
         self.activations, self.int8_threshold, self.outlier_cap = activations, float(int8_threshold), int(outlier_cap)
         if activations == "int8":
-            gqa.update(activations="int8", int8_threshold=self.int8_threshold, outlier_cap=self.outlier_cap)
-        self._hip = _HipDecoder(llama_model, self.max_batch, weights=weights, early_stop=early_stop, **gqa) if decode == "hip" else None
+            engine_kw.update(activations="int8", int8_threshold=self.int8_threshold, outlier_cap=self.outlier_cap)
+        self._hip = _HipDecoder(llama_model, self.max_batch, weights=weights, early_stop=early_stop, **engine_kw) if decode == "hip" else None
         if self._hip is not None and stops:                 # none is the handle's state at create: nothing is called for it
             self._hip.set_stop_sequences(stops)
         self.routed_linears = (_LinearRoute.install(llama_model)
@@ -1386,6 +559,25 @@ class MiniGPT4Classifier:
                                                            list(stop_sequences_criteria(self.stop_words_ids)))
         return kw
 
+    def _eos_and_pad_ids(self):
+        """(eos ids, pad id) as `generate` resolves them: the checkpoint's generation_config, else its config; without a pad id the
+        first EOS id, else 0."""
+        llm = self.llama_model
+        gen = getattr(llm, "generation_config", None)
+        eos = getattr(gen, "eos_token_id", None)
+        eos = getattr(llm.config, "eos_token_id", None) if eos is None else eos
+        eos_ids = list(eos) if isinstance(eos, (list, tuple)) else ([eos] if eos is not None else [])
+        pad = getattr(gen, "pad_token_id", None)
+        pad = getattr(llm.config, "pad_token_id", None) if pad is None else pad
+        pad = (eos_ids[0] if eos_ids else 0) if pad is None else pad
+        return eos_ids, pad
+
+    def _kv_buffers(self, embs, B, length):
+        """One K and one V buffer per layer for the native engine, [B, kv_heads, length, 128] each, allocated by `embs.new_empty`:
+        inside a capture they belong to the graph's pool."""
+        shape = (B, self._hip.kv_heads, length, 128)
+        return ([embs.new_empty(shape) for _ in range(self._hip.layers)], [embs.new_empty(shape) for _ in range(self._hip.layers)])
+
     def greedy_tokens(self, embs, return_logits=False, starts=None):
         """What `generate(inputs_embeds=embs, attention_mask=ones, max_new_tokens=n, do_sample=False, min_length=1, ...)` returns for
         prompts without padding, as a straight loop of the model's own forward calls: [B, n] token ids, pad_token_id after a row's
@@ -1419,20 +611,12 @@ class MiniGPT4Classifier:
                 return self.keys, self.values
 
         llm = self.llama_model
-        gen = getattr(llm, "generation_config", None)
-        eos = getattr(gen, "eos_token_id", None)
-        eos = getattr(llm.config, "eos_token_id", None) if eos is None else eos
-        eos_ids = list(eos) if isinstance(eos, (list, tuple)) else ([eos] if eos is not None else [])
-        pad = getattr(gen, "pad_token_id", None)
-        pad = getattr(llm.config, "pad_token_id", None) if pad is None else pad
-        pad = (eos_ids[0] if eos_ids else 0) if pad is None else pad
+        eos_ids, pad = self._eos_and_pad_ids()
         B, L, _ = embs.shape
         assert starts is None or self.prefill == "hip", 'left-padded rows need prefill="hip"'
         if self.prefill == "hip":                                      # the whole decode in this library: no HF forward, no DynamicCache
             assert B <= self.max_batch, f"{B} rows > max_batch {self.max_batch} (the native decoder's workspace)"
-            shape = (B, self._hip.kv_heads, L + self.max_new_tokens, 128)    # what PreallocLayer allocates on the other path
-            k_bufs = [embs.new_empty(shape) for _ in range(self._hip.layers)]
-            v_bufs = [embs.new_empty(shape) for _ in range(self._hip.layers)]
+            k_bufs, v_bufs = self._kv_buffers(embs, B, L + self.max_new_tokens)      # what PreallocLayer allocates on the other path
             logits = self._hip.prefill(embs.contiguous(), k_bufs, v_bufs, starts=starts)
             self.decode_stats["hip_prefills"] += 1
             self.decode_stats["hip_steps"] += self.max_new_tokens - 1
@@ -1668,9 +852,7 @@ class MiniGPT4Classifier:
         table = torch.zeros((len(toks), Tmax), dtype=torch.long)
         for c, t in enumerate(toks):
             table[c, :lens[c]] = t
-        shape = (B, hip.kv_heads, L, 128)                              # the prompt's rows only: scoring appends nothing
-        k_bufs = [embs.new_empty(shape) for _ in range(hip.layers)]
-        v_bufs = [embs.new_empty(shape) for _ in range(hip.layers)]
+        k_bufs, v_bufs = self._kv_buffers(embs, B, L)                   # the prompt's rows only: scoring appends nothing
         first = hip.prefill(embs, k_bufs, v_bufs)
         sums = hip.score(first, L, table.to(embs.device), lens, self.label_smoothing, k_bufs, v_bufs)
         self.decode_stats["hip_prefills"] += 1
@@ -1707,9 +889,7 @@ class MiniGPT4Classifier:
             inv = inv.to(embs.device)
             embs, starts = embs[inv].contiguous(), starts[inv].contiguous()
         L = int(embs.shape[1])
-        shape = (B, hip.kv_heads, L, 128)
-        k_bufs = [embs.new_empty(shape) for _ in range(hip.layers)]
-        v_bufs = [embs.new_empty(shape) for _ in range(hip.layers)]
+        k_bufs, v_bufs = self._kv_buffers(embs, B, L)
         first = hip.prefill(embs, k_bufs, v_bufs, starts=starts)
         sums = hip.score(first, L, table.to(embs.device), T, self.label_smoothing, k_bufs, v_bufs, starts=starts,
                          row_lens=row_lens.to(embs.device))

@@ -1,6 +1,6 @@
 """activations="int8": the LLM.int8() forward on the native LLaMA engine (cgpt_llm_config_act.act_format = 1).
 
-The law is `llm_int8_linear` (minigpt4.py): row-wise int8 activations with a per-row outlier split, int32 accumulation, fp32 scales.
+The law is `llm_int8_linear` (llm_laws.py): row-wise int8 activations with a per-row outlier split, int32 accumulation, fp32 scales.
 Integer accumulation is exact, so everything here except the accuracy test is `torch.equal`:
   1. the operand map of the int8 MFMA on exact integer data;
   2. the raw entry cgpt_llm_linear_i8 against the law, bit for bit, over row counts on both sides of a row tile, one and several K
@@ -22,14 +22,14 @@ import certifiedgpt_amd as cg
 from certifiedgpt_amd import _lib
 from certifiedgpt_amd.agents.label_adapter import AnswerLabelMap
 from certifiedgpt_amd.minigpt4 import (MiniGPT4Classifier, WordHashTokenizer, _HipDecoder, act_int8_twin, expand_kv_state_dict,
-                                       greedy_decode_parity, left_pad_embeds, llm_int8_linear, prepare_texts, quantize_rows_int8)
+                                       greedy_decode_parity, left_pad_embeds, llm_int8_linear, quantize_rows_int8)
 from oracle import model_oracle as mo
 from gpu_util import DEV, make_classifier
+import llm_util as lu
+from llm_util import PAD, EOS, PROMPT
 
 pytestmark = pytest.mark.gpu
 
-PAD, BOS, EOS = 0, 1, 2
-PROMPT = prepare_texts(["<Img><ImageHere></Img> [vqa] what is shown in the picture"])[0]
 SENT = 0x5A
 SHAPES = [(64, 128), (192, 256), (64, 1024), (128, 2048)]              # (N, K): 1, 1, 2 and 4 K slices at M <= 256
 EPI_F16, EPI_RESID, EPI_SWIGLU = 0, 1, 2
@@ -206,30 +206,6 @@ def test_bad_sizes_are_refused():
 
 
 # ------------------------------------------------------------------------------------------ 3. engine identities
-def _decoder(hidden, heads, mlp, vocab, layers=2, kv_heads=None, plant=True):
-    """A frozen random-init fp16 LlamaForCausalLM on the device.  plant: one input_layernorm and one post_attention_layernorm channel
-    of every layer x 50, so that every row the q/k/v and gate/up linears read has outliers."""
-    from transformers import LlamaConfig, LlamaForCausalLM
-    lcfg = LlamaConfig(vocab_size=vocab, hidden_size=hidden, intermediate_size=mlp, num_hidden_layers=layers, num_attention_heads=heads,
-                       num_key_value_heads=kv_heads or heads, max_position_embeddings=2048, pad_token_id=PAD, bos_token_id=BOS,
-                       eos_token_id=EOS)
-    torch.manual_seed(0)
-    prev = torch.get_default_dtype()
-    torch.set_default_dtype(torch.float16)
-    try:
-        with torch.device(DEV):
-            llm = LlamaForCausalLM(lcfg).eval()
-    finally:
-        torch.set_default_dtype(prev)
-    for prm in llm.parameters():
-        prm.requires_grad = False
-    if plant:
-        for layer in llm.model.layers:
-            layer.input_layernorm.weight[11] *= 50.0
-            layer.post_attention_layernorm.weight[301] *= 50.0
-    return llm
-
-
 def _act(llm, rows=200, **kw):
     """outlier_cap 1024, the largest: a planted norm channel x 50 reaches the SwiGLU output through gate AND up, so a row whose planted
     activation is large has hundreds of down_proj inputs past the threshold (230 of 1408 were seen) -- far more than the default 64."""
@@ -240,26 +216,15 @@ def _act(llm, rows=200, **kw):
 @pytest.fixture(scope="module")
 def small():
     """hidden 512 = 4 heads x 128, MLP 1408 = 11 x 128, vocabulary 320, 2 layers, planted norm channels."""
-    llm = _decoder(512, 4, 1408, 320)
+    llm = lu.llama_decoder(512, 4, 1408, 320, plant=True)
     dec = _act(llm)
     yield llm, dec
     dec.close()
 
 
-def _buffers(dec, B, length):
-    shape = (B, dec.kv_heads, length, 128)
-    return ([torch.full(shape, 77.0, dtype=torch.float16, device=DEV) for _ in range(dec.layers)],
-            [torch.full(shape, -55.0, dtype=torch.float16, device=DEV) for _ in range(dec.layers)])
-
-
-def _embeds(llm, B, L, seed):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    return llm.get_input_embeddings()(torch.randint(3, llm.config.vocab_size, (B, L), generator=g).to(DEV)).contiguous()
-
-
 def _run(dec, embs, n_new, starts=None):
     B, L = embs.shape[:2]
-    kb, vb = _buffers(dec, B, L + n_new + 1)
+    kb, vb = lu.sentinel_cache(dec.layers, dec.kv_heads, B, L + n_new + 1)
     first = dec.prefill(embs, kb, vb, starts=starts)
     tokens, steps = dec.greedy(first, L, n_new, 1, [EOS], PAD, kb, vb, return_logits=True, starts=starts)
     torch.cuda.synchronize()
@@ -278,7 +243,7 @@ def _same(a, b, where, caches=True):
 def test_200_rows_equal_128_plus_72_and_outliers_exist(small):
     llm, dec = small
     dec.act_stats()
-    embs = _embeds(llm, 200, 12, seed=3)
+    embs = lu.embeds(llm, 200, 12, seed=3)
     whole = _run(dec, embs, 4)
     st = dec.act_stats()
     assert st["outliers"] > 0 and st["overflow_rows"] == 0 and st["max_outliers_per_row"] <= CAP
@@ -293,7 +258,7 @@ def test_an_overflowing_row_raises_and_names_the_cap(small):
     llm, _ = small
     dec = _act(llm, rows=37, outlier_cap=1)
     try:
-        out = _run(dec, _embeds(llm, 37, 12, seed=3), 2)
+        out = _run(dec, lu.embeds(llm, 37, 12, seed=3), 2)
         assert bool(torch.isfinite(out[0]).all())                      # finite and memory-safe, though not the law's
         with pytest.raises(RuntimeError) as e:
             dec.act_stats()
@@ -306,7 +271,7 @@ def test_a_left_padded_row_equals_the_row_alone(small):
     llm, dec = small
     g = torch.Generator(device="cpu").manual_seed(48)
     lens = torch.randint(1, 25, (20,), generator=g).tolist()
-    embs, _, starts = left_pad_embeds([_embeds(llm, 1, n, seed=100 + i) for i, n in enumerate(lens)])
+    embs, _, starts = left_pad_embeds([lu.embeds(llm, 1, n, seed=100 + i) for i, n in enumerate(lens)])
     embs, starts = embs.contiguous(), starts.to(DEV)
     padded = _run(dec, embs, 4, starts)
     for i in (0, 7):
@@ -318,10 +283,10 @@ def test_a_left_padded_row_equals_the_row_alone(small):
 def test_one_graph_replayed_twice_gives_the_eager_bits(small):
     llm, dec = small
     L, n_new = 12, 4
-    embs = _embeds(llm, 200, L, seed=5)
+    embs = lu.embeds(llm, 200, L, seed=5)
     dec.act_stats()
     eager = _run(dec, embs, n_new)
-    kb, vb = _buffers(dec, 200, L + n_new + 1)
+    kb, vb = lu.sentinel_cache(dec.layers, dec.kv_heads, 200, L + n_new + 1)
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
@@ -338,7 +303,7 @@ def test_one_graph_replayed_twice_gives_the_eager_bits(small):
 
 def test_early_stop_gives_the_same_tokens(small):
     llm, dec = small
-    embs = _embeds(llm, 37, 12, seed=6)
+    embs = lu.embeds(llm, 37, 12, seed=6)
     off = _run(dec, embs, 6)
     dec.set_early_stop(True)
     try:
@@ -350,12 +315,12 @@ def test_early_stop_gives_the_same_tokens(small):
 
 def test_a_grouped_kv_handle_equals_the_plain_handle_on_the_expanded_twin():
     """Unlike the fp16 engine (cgpt.h: the narrower fused projection runs another K split), the two are bit-equal here: integer sums."""
-    llm = _decoder(512, 4, 1408, 320, kv_heads=2)
-    twin = _decoder(512, 4, 1408, 320, plant=False)
+    llm = lu.llama_decoder(512, 4, 1408, 320, kv_heads=2, plant=True)
+    twin = lu.llama_decoder(512, 4, 1408, 320, plant=False)
     twin.load_state_dict(expand_kv_state_dict(llm), strict=True)
     a, b = _act(llm, grouped_kv=True), _act(twin)
     try:
-        embs = _embeds(llm, 37, 12, seed=8)
+        embs = lu.embeds(llm, 37, 12, seed=8)
         ra, rb = _run(a, embs, 4), _run(b, embs, 4)
         _same(ra, rb, "grouped against expanded", caches=False)
         assert a.act_stats()["outliers"] > 0
@@ -367,8 +332,8 @@ def test_a_grouped_kv_handle_equals_the_plain_handle_on_the_expanded_twin():
 def test_a_candidate_scored_alone_equals_the_candidate_among_others(small):
     llm, dec = small
     B, L = 37, 12
-    embs = _embeds(llm, B, L, seed=9)
-    kb, vb = _buffers(dec, B, L)
+    embs = lu.embeds(llm, B, L, seed=9)
+    kb, vb = lu.sentinel_cache(dec.layers, dec.kv_heads, B, L)
     first = dec.prefill(embs, kb, vb)
     table = torch.tensor([[5, 9, 17, 40], [6, 8, 0, 0], [7, 30, 31, 0]], dtype=torch.int64, device=DEV)
     among = dec.score(first, L, table, [4, 2, 3], 0.1, kb, vb)
@@ -379,10 +344,10 @@ def test_a_candidate_scored_alone_equals_the_candidate_among_others(small):
 
 
 def test_threshold_6_equals_threshold_0_where_nothing_reaches_6():
-    llm = _decoder(512, 4, 1408, 320, plant=False)
+    llm = lu.llama_decoder(512, 4, 1408, 320, plant=False)
     a, b = _act(llm), _act(llm, int8_threshold=0.0)
     try:
-        embs = _embeds(llm, 37, 12, seed=10)
+        embs = lu.embeds(llm, 37, 12, seed=10)
         _same(_run(a, embs, 4), _run(b, embs, 4), "threshold 6 against 0")
         assert a.act_stats()["outliers"] == 0 and b.act_stats()["outliers"] == 0
     finally:
@@ -409,20 +374,6 @@ def test_a_linear_is_the_same_through_the_prefill_and_the_step_launch(small, whi
 
 
 # ------------------------------------------------------------------------------------------ 5. accuracy against the twin
-def _model_prefill(model, embs):
-    from transformers import DynamicCache
-    cache = DynamicCache(config=model.config)
-    pos = torch.arange(embs.shape[1], device=embs.device).unsqueeze(0)
-    with torch.no_grad():
-        out = model(inputs_embeds=embs, position_ids=pos, past_key_values=cache, use_cache=True, logits_to_keep=1)
-    return out.logits[:, -1].float(), [l.keys for l in cache.layers], [l.values for l in cache.layers]
-
-
-def _err(a, ref):
-    d = (a.float() - ref.float()).abs()
-    return float(d.max()), float(d.pow(2).mean().sqrt())
-
-
 @pytest.fixture(scope="module")
 def twins(small):
     llm, _ = small
@@ -437,16 +388,16 @@ def test_error_against_the_fp32_twin_is_within_the_projects_margin(small, twins,
     llm, dec = small
     twin16, twin32 = twins
     L = 12
-    embs = _embeds(llm, B, L, seed=B)
-    kb, vb = _buffers(dec, B, L)
+    embs = lu.embeds(llm, B, L, seed=B)
+    kb, vb = lu.sentinel_cache(dec.layers, dec.kv_heads, B, L)
     lib = dec.prefill(embs, kb, vb)
     torch.cuda.synchronize()
-    hf, hk, hv = _model_prefill(twin16, embs)
-    ref, rk, rv = _model_prefill(twin32, embs.float())
-    figures = {"logits": _err(lib, ref) + _err(hf, ref)}
+    hf, hk, hv = lu.model_prefill(twin16, embs)
+    ref, rk, rv = lu.model_prefill(twin32, embs.float())
+    figures = {"logits": lu.err(lib, ref) + lu.err(hf, ref)}
     for l in range(len(hk)):
-        figures[f"k{l}"] = _err(kb[l], rk[l]) + _err(hk[l], rk[l])
-        figures[f"v{l}"] = _err(vb[l], rv[l]) + _err(hv[l], rv[l])
+        figures[f"k{l}"] = lu.err(kb[l], rk[l]) + lu.err(hk[l], rk[l])
+        figures[f"v{l}"] = lu.err(vb[l], rv[l]) + lu.err(hv[l], rv[l])
     print(f"[act int8 accuracy, {B} rows x {L}] (max e_lib / max e_hf, rms e_lib / rms e_hf): "
           + ", ".join(f"{k} ({x[0] / x[2]:.3f}, {x[1] / x[3]:.3f}) [e_lib {x[0]:.4g} {x[1]:.4g}, e_hf {x[2]:.4g} {x[3]:.4g}]"
                       for k, x in figures.items()), flush=True)
@@ -458,13 +409,13 @@ def test_greedy_decode_keeps_the_twins_decisive_rows(small, twins):
     llm, dec = small
     twin16, _ = twins
     B, L, n = 200, 12, 20
-    embs = _embeds(llm, B, L, seed=21)
+    embs = lu.embeds(llm, B, L, seed=21)
     with torch.no_grad():
         out = twin16.generate(inputs_embeds=embs, attention_mask=torch.ones(embs.shape[:2], dtype=torch.int, device=DEV), max_new_tokens=n,
                               output_scores=True, return_dict_in_generate=True, do_sample=False, num_beams=1, min_new_tokens=1)
     hf_tokens, hf_scores = out.sequences, torch.stack(out.scores, dim=1).float()
     first, tokens, _, _, _ = _run(dec, embs, n)
-    hf_first, _, _ = _model_prefill(twin16, embs)
+    hf_first, _, _ = lu.model_prefill(twin16, embs)
     eps = 2.0 * float((first - hf_first).abs().max())
     v = greedy_decode_parity(hf_tokens, hf_scores, tokens, eps)
     print(f"[act int8 greedy parity] eps {eps:.4g}: {v['identical']}/{B} rows identical to the twin's generate, "
@@ -473,12 +424,8 @@ def test_greedy_decode_keeps_the_twins_decisive_rows(small, twins):
 
 
 # ------------------------------------------------------------------------------------------ 6. the classifier at Vicuna width
-def _up256(n):
-    return (n + 255) // 256 * 256
-
-
 def test_classifier_at_vicuna_width():
-    llm = _decoder(4096, 32, 11008, 32000, plant=False)
+    llm = lu.llama_decoder(4096, 32, 11008, 32000, plant=False)
     cfg = mo.Config(mode=mo.MODE_ENCODE_IMG, num_classes=10)
     enc = make_classifier(cfg, max_batch=100)
     try:
@@ -502,7 +449,7 @@ def test_classifier_at_vicuna_width():
             assert st["max_outliers_per_row"] <= clf.outlier_cap and st["outliers"] >= st["max_outliers_per_row"]
             H, F, V = 4096, 11008, 32000
             mats = [(3 * H, H), (H, H), (2 * F, H), (H, F)]
-            want = 2 * sum(_up256(a) * b + _up256(a) * 2 for a, b in mats) + 2 * V * H * 2      # no fp16 scratch
+            want = 2 * sum(lu.up256(a) * b + lu.up256(a) * 2 for a, b in mats) + 2 * V * H * 2      # no fp16 scratch
             assert s["weight_bytes"] == want, (s["weight_bytes"], want)
             del clf
             vocab = sorted(set(answers), key=lambda a: (-answers.count(a), a))[:3]

@@ -5,7 +5,6 @@ own token and HF's own cache; with e_hf = |HF fp16 - fp32| and e_lib = |library 
 passes when max e_lib <= 1.5 max e_hf and rms e_lib <= 1.5 rms e_hf: the reference engine's own rounding error is the bound, and
 1.5 is room for two independent rounding noises whose maxima over B x V values differ by chance.  Trajectories are judged by the
 project's rule (`greedy_decode_parity`): a row may leave HF's trajectory only where HF's own top-2 margin is within the logit noise."""
-import copy
 import dataclasses
 
 import numpy as np
@@ -17,160 +16,19 @@ from certifiedgpt_amd.agents import registry, setup_agent
 from certifiedgpt_amd.agents import minigpt4_certify_agent  # noqa: F401
 from certifiedgpt_amd.agents.label_adapter import AnswerLabelMap
 from certifiedgpt_amd.minigpt4 import (MiniGPT4Classifier, WordHashTokenizer, _HipDecoder, fp16_ulp, greedy_decode_parity,
-                                       hip_decode_unsupported, prepare_texts)
+                                       hip_decode_unsupported)
 from oracle import model_oracle as mo, smooth_oracle as so
 from gpu_util import DEV, make_classifier
+import llm_util as lu
+from llm_util import PAD, EOS, PROMPT
 
 pytestmark = pytest.mark.gpu
-
-PAD, BOS, EOS = 0, 1, 2
-PROMPT = prepare_texts(["<Img><ImageHere></Img> [vqa] what is shown in the picture"])[0]
-
-
-def _decoder(hidden, heads, mlp, vocab, layers=2):
-    """A frozen random-init fp16 LlamaForCausalLM on the device (no checkpoint is in the container; nothing is downloaded)."""
-    from transformers import LlamaConfig, LlamaForCausalLM
-    lcfg = LlamaConfig(vocab_size=vocab, hidden_size=hidden, intermediate_size=mlp, num_hidden_layers=layers, num_attention_heads=heads,
-                       num_key_value_heads=heads, max_position_embeddings=2048, pad_token_id=PAD, bos_token_id=BOS, eos_token_id=EOS)
-    torch.manual_seed(0)
-    prev = torch.get_default_dtype()
-    torch.set_default_dtype(torch.float16)
-    try:
-        with torch.device(DEV):
-            llm = LlamaForCausalLM(lcfg).eval()
-    finally:
-        torch.set_default_dtype(prev)
-    for prm in llm.parameters():
-        prm.requires_grad = False
-    return llm
-
-
-def _small_decoder():
-    """Small enough that every weight and logit can be compared: hidden 512 = 4 heads x 128, MLP 1408, vocabulary 320, 2 layers."""
-    return _decoder(512, 4, 1408, 320)
-
-
-def _vicuna_width_decoder():
-    """Vicuna-7B's widths (hidden 4096, 32 heads, MLP 11008, vocabulary 32000) with 2 random-init layers."""
-    return _decoder(4096, 32, 11008, 32000)
-
-
-def _cache_from(cfg, keys, values, dtype):
-    from transformers import DynamicCache
-    c = DynamicCache(config=cfg)
-    for l, (k, v) in enumerate(zip(keys, values)):
-        c.update(k.to(dtype).clone(), v.to(dtype).clone(), l)
-    return c
-
-
-def _prefill(llm, embs, extra):
-    """HF prefill of embs [B, L, hidden] -> (last-position logits fp32, per-layer K / V buffers [B, heads, L + extra, 128] whose first
-    L rows are HF's cache and whose other rows hold a sentinel)."""
-    from transformers import DynamicCache
-    B, L, _ = embs.shape
-    cache = DynamicCache(config=llm.config)
-    with torch.no_grad():
-        out = llm(inputs_embeds=embs, position_ids=torch.arange(L, device=DEV)[None], past_key_values=cache, use_cache=True,
-                  logits_to_keep=1)
-    kb, vb = [], []
-    for layer in cache.layers:
-        k = torch.full((B, layer.keys.shape[1], L + extra, 128), 77.0, dtype=torch.float16, device=DEV)
-        v = torch.full_like(k, -55.0)
-        k[:, :, :L] = layer.keys
-        v[:, :, :L] = layer.values
-        kb.append(k)
-        vb.append(v)
-    return out.logits[:, -1].float(), kb, vb, cache
-
-
-def _teacher_forced(llm, dec, B, L=12, steps=6, seed=3):
-    """The accuracy criterion of the module docstring; returns the per-step figures."""
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    ids = torch.randint(3, llm.config.vocab_size, (B, L), generator=g).to(DEV)
-    embs = llm.get_input_embeddings()(ids)
-    llm32 = copy.deepcopy(llm).float()
-    logits, kb, vb, cache = _prefill(llm, embs, steps)
-    tok = logits.argmax(-1)
-    rows = []
-    for s in range(steps):
-        pos = L + s
-        keys = [l.keys.clone() for l in cache.layers]
-        vals = [l.values.clone() for l in cache.layers]
-        for l in range(len(kb)):                                       # HF's own cache, every step
-            kb[l][:, :, :pos] = keys[l]
-            vb[l][:, :, :pos] = vals[l]
-        before = [t.clone() for t in kb + vb]
-        lib = dec.step(tok, pos, kb, vb)
-        pid = torch.full((1, 1), pos, device=DEV, dtype=torch.long)
-        with torch.no_grad():
-            hf = llm(input_ids=tok[:, None], position_ids=pid, past_key_values=cache, use_cache=True).logits[:, -1].float()
-            c32 = _cache_from(llm.config, keys, vals, torch.float32)
-            ref = llm32(input_ids=tok[:, None], position_ids=pid, past_key_values=c32, use_cache=True).logits[:, -1].float()
-        fin = torch.isfinite(ref) & torch.isfinite(hf) & torch.isfinite(lib)
-        assert bool(fin.all())
-        e_hf, e_lib = (hf - ref).abs(), (lib - ref).abs()
-        # the appended rows.  "Within 1 fp16 ulp of HF's row" needs a magnitude to measure the ulp at.  Measured at each element's own
-        # magnitude it is not a property any engine with its own GEMM can have: an element of a key or value row is a dot product (and a
-        # rotated key a sum of two rounded products) that may cancel to far below its terms, while one fp16 rounding tipped upstream by
-        # another summation order moves it by an ulp of the TERMS (measured: up to 44 own-magnitude ulp in a layer-0 value element, 1536
-        # in a rotated key element near zero).  What is asserted instead, for layer 0, whose input teacher forcing makes identical in
-        # both engines:
-        #   (a) the value row within 1 ulp, the key row within 2 ulp, the ulp taken at the largest element of the head's 128-vector
-        #       in HF's row.  2 for keys: a rotation can shrink a pair's larger element by up to sqrt(2), i.e. one binade, so one ulp
-        #       of the un-rotated terms reads up to 2 there;
-        #   (b) at least 98 % of the row's elements bit-equal to HF's.  An element can differ only where another summation order tips
-        #       an fp16 rounding: fp32 accumulation noise of ~sqrt(K) 2^-24 relative against an fp16 spacing of 2^-11..2^-10 is a share
-        #       of 0.1 - 0.8 % at K = 512..4096 for the projection, about as much again from the RMSNorm in front of it, and a rotated
-        #       key takes two inputs: 1 - 2 % at the very most.  Rounding anywhere ELSE than HF does (a product of the rotary kept
-        #       unrounded inside a fused multiply-add, another cos / sin) moves an order of magnitude more: this is the assertion
-        #       that guards the rotary rounding contract.
-        # Every row of every layer is also held to the yardstick of the logits (from layer 1 on the input carries layer 0's rounding
-        # noise, so HF's row is no closer to the fp32 model's than ours): distance to the fp32 row against HF's own.  Every other
-        # cache row: bit-unchanged.
-        kv = {}
-        for l in range(len(kb)):
-            for name, mine, theirs, exact, was in (("k", kb[l], cache.layers[l].keys, c32.layers[l].keys, before[l]),
-                                                   ("v", vb[l], cache.layers[l].values, c32.layers[l].values, before[len(kb) + l])):
-                new, want, ref32 = mine[:, :, pos].float(), theirs[:, :, pos].float(), exact[:, :, pos].float()
-                assert bool(torch.isfinite(new).all())
-                d_hf, d_lib = (want - ref32).abs(), (new - ref32).abs()
-                kv[f"{name}{l}"] = (float(d_lib.max()), float(d_hf.max()), float(d_lib.pow(2).mean().sqrt()), float(d_hf.pow(2).mean().sqrt()),
-                                    float((new == want).float().mean()))
-                if l == 0:
-                    ulp = want.abs().amax(dim=-1, keepdim=True).clamp_min(2.0 ** -14).log2().floor().sub(10).exp2()
-                    kv[f"{name}{l}"] += (float(((new - want).abs() / ulp).max()),)
-                keep = torch.ones(mine.shape[2], dtype=torch.bool, device=DEV)
-                keep[pos] = False
-                assert torch.equal(mine[:, :, keep], was[:, :, keep])
-        rows.append({"step": s, "max_hf": float(e_hf.max()), "max_lib": float(e_lib.max()),
-                     "rms_hf": float(e_hf.pow(2).mean().sqrt()), "rms_lib": float(e_lib.pow(2).mean().sqrt()),
-                     "max_lib_vs_hf": float((lib - hf).abs().max()), "max_logit": float(hf.abs().max()), "kv": kv})
-        tok = hf.argmax(-1)                                            # HF's own token
-    del llm32
-    return rows
-
-
-def _check_ratios(name, rows):
-    for r in rows:
-        print(f"[teacher-forced {name}] step {r['step']}: max e_lib / max e_hf = {r['max_lib'] / r['max_hf']:.3f} "
-              f"({r['max_lib']:.4g} / {r['max_hf']:.4g}), rms ratio {r['rms_lib'] / r['rms_hf']:.3f} "
-              f"({r['rms_lib']:.4g} / {r['rms_hf']:.4g}), max |lib - hf| {r['max_lib_vs_hf']:.4g}, max |logit| {r['max_logit']:.4g}", flush=True)
-        print("    appended rows, (max, rms) error ratio library / HF against the fp32 model, share of elements equal to HF's: "
-              + ", ".join(f"{k} ({v[0] / v[1]:.2f}, {v[2] / v[3]:.2f}, {v[4]:.4f})" for k, v in r["kv"].items())
-              + f"; layer 0 largest difference in head-max ulp: k {r['kv']['k0'][5]:.2f}, v {r['kv']['v0'][5]:.2f}", flush=True)
-    for r in rows:
-        assert r["max_lib"] <= 1.5 * r["max_hf"], r
-        assert r["rms_lib"] <= 1.5 * r["rms_hf"], r
-        for k, v in r["kv"].items():
-            assert v[0] <= 1.5 * v[1] and v[2] <= 1.5 * v[3], (r["step"], k, v)
-        assert r["kv"]["v0"][5] <= 1.0 and r["kv"]["k0"][5] <= 2.0, (r["step"], r["kv"]["v0"], r["kv"]["k0"])     # head-max ulp
-        assert r["kv"]["v0"][4] >= 0.98 and r["kv"]["k0"][4] >= 0.98, (r["step"], r["kv"]["v0"], r["kv"]["k0"])   # bit-equal share
 
 
 # ------------------------------------------------------------------------------------------ fixtures
 @pytest.fixture(scope="module")
 def small():
-    llm = _small_decoder()
+    llm = lu.small_decoder()
     assert hip_decode_unsupported(llm, 200) == []
     dec = _HipDecoder(llm, 200)
     yield llm, dec
@@ -179,7 +37,7 @@ def small():
 
 @pytest.fixture(scope="module")
 def vicuna():
-    llm = _vicuna_width_decoder()
+    llm = lu.vicuna_width_decoder()
     dec = _HipDecoder(llm, 200)
     yield llm, dec
     dec.close()
@@ -190,19 +48,19 @@ def vicuna():
 @pytest.fixture(scope="module")
 def vicuna_teacher_forced(vicuna):
     llm, dec = vicuna
-    return {B: _teacher_forced(llm, dec, B, L=44, steps=4) for B in (200, 37)}
+    return {B: lu.teacher_forced(llm, dec, B, L=44, steps=4) for B in (200, 37)}
 
 
 # ------------------------------------------------------------------------------------------ 4. teacher-forced step parity
 @pytest.mark.parametrize("B", [200, 37])
 def test_teacher_forced_step_error_is_within_hfs_own_fp16_error_small_decoder(small, B):
     llm, dec = small
-    _check_ratios(f"small decoder, {B} rows", _teacher_forced(llm, dec, B))
+    lu.check_ratios(f"small decoder, {B} rows", lu.teacher_forced(llm, dec, B))
 
 
 @pytest.mark.parametrize("B", [200, 37])
 def test_teacher_forced_step_error_is_within_hfs_own_fp16_error_vicuna_width(vicuna_teacher_forced, B):
-    _check_ratios(f"Vicuna width, {B} rows", vicuna_teacher_forced[B])
+    lu.check_ratios(f"Vicuna width, {B} rows", vicuna_teacher_forced[B])
 
 
 def test_step_entries_refuse_a_half_loaded_handle_and_a_position_outside_the_cache(small):
@@ -257,7 +115,7 @@ def test_replays_are_bit_identical_and_rows_do_not_depend_on_the_batch(which, re
     B, L, n = 200, 16, 6
     g = torch.Generator(device="cpu").manual_seed(5)
     embs = llm.get_input_embeddings()(torch.randint(3, llm.config.vocab_size, (B, L), generator=g).to(DEV))
-    first, kb, vb, _ = _prefill(llm, embs, n)
+    first, kb, vb, _ = lu.prefill(llm, embs, n)
     runs = []
     for _ in range(2):
         k2, v2 = [t.clone() for t in kb], [t.clone() for t in vb]
@@ -298,7 +156,7 @@ def test_min_new_tokens_and_pad_after_eos_follow_greedy_tokens_rule(small, min_n
     B, L, n = 37, 10, 6
     g = torch.Generator(device="cpu").manual_seed(9)
     embs = llm.get_input_embeddings()(torch.randint(3, 320, (B, L), generator=g).to(DEV))
-    first, kb, vb, _ = _prefill(llm, embs, n)
+    first, kb, vb, _ = lu.prefill(llm, embs, n)
     forced = torch.arange(B, device=DEV) % 3 == 0
     first = first.clone()
     first[forced, EOS] = 1.0e4                                         # EOS wins the first arg-max in these rows unless suppressed

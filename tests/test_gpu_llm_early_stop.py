@@ -13,33 +13,14 @@ import pytest
 import torch
 
 from certifiedgpt_amd.agents.label_adapter import AnswerLabelMap
-from certifiedgpt_amd.minigpt4 import MiniGPT4Classifier, WordHashTokenizer, _HipDecoder, prepare_texts
+from certifiedgpt_amd.minigpt4 import MiniGPT4Classifier, WordHashTokenizer, _HipDecoder
 from oracle import model_oracle as mo
 from gpu_util import DEV, make_classifier
-from test_gpu_llm_decode import _prefill, _small_decoder, _vicuna_width_decoder
+import llm_util as lu
+from llm_util import LOGIT_SENTINEL, PROMPT
 from test_llm_early_stop_cpu import expected_live_steps, finishing_select
 
 pytestmark = pytest.mark.gpu
-
-K_SENT, V_SENT, LOGIT_SENT = 77.0, -55.0, 123.0                     # _prefill's cache sentinels; ours for the step logits
-PROMPT = prepare_texts(["<Img><ImageHere></Img> [vqa] what is shown in the picture"])[0]
-
-
-def _zero_head(llm):
-    with torch.no_grad():
-        llm.lm_head.weight.zero_()
-    return llm
-
-
-def _ids(llm, B, L, seed):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    return torch.randint(3, llm.config.vocab_size, (B, L), generator=g).to(DEV)
-
-
-def _sentinel_cache(dec, B, length):
-    shape = (B, dec.heads, length, 128)
-    return ([torch.full(shape, K_SENT, dtype=torch.float16, device=DEV) for _ in range(dec.layers)],
-            [torch.full(shape, V_SENT, dtype=torch.float16, device=DEV) for _ in range(dec.layers)])
 
 
 def _greedy(dec, on, first, L, n, min_new, eos, pad, kb, vb, logits=False, starts=None):
@@ -51,7 +32,7 @@ def _greedy(dec, on, first, L, n, min_new, eos, pad, kb, vb, logits=False, start
     try:
         if logits:                                                     # dec.greedy allocates its own buffer: go through the C entry
             tokens = torch.full((B, n), -7, dtype=torch.int64, device=DEV)
-            buf = torch.full((B, n, V), LOGIT_SENT, dtype=torch.float32, device=DEV)
+            buf = torch.full((B, n, V), LOGIT_SENTINEL, dtype=torch.float32, device=DEV)
             kp, vp, stride = dec._cache_tables(kb, vb, B, L + n - 1)
             ids = (C.c_int64 * max(1, len(eos)))(*eos)
             st = torch.cuda.current_stream()
@@ -69,27 +50,9 @@ def _greedy(dec, on, first, L, n, min_new, eos, pad, kb, vb, logits=False, start
     return tokens, steps, kb, vb, buf
 
 
-def _check_dead_part(L, live, on, off, layers=None):
-    """The contract of include/cgpt.h: cache rows L + live .. keep their sentinel on the `on` run, rows L .. L + live - 1 are the off
-    run's bit for bit (as are the prompt rows, which no step writes); step logits rows 0 .. live are the off run's, later rows keep
-    their sentinel."""
-    _, _, k_on, v_on, lg_on = on
-    _, _, k_off, v_off, lg_off = off
-    for l in (range(len(k_on)) if layers is None else layers):
-        assert bool((k_on[l][:, :, L + live:] == K_SENT).all()) and bool((v_on[l][:, :, L + live:] == V_SENT).all()), (l, live)
-        assert torch.equal(k_on[l][:, :, :L + live], k_off[l][:, :, :L + live]), (l, live)
-        assert torch.equal(v_on[l][:, :, :L + live], v_off[l][:, :, :L + live]), (l, live)
-        n_off = k_off[l].shape[2] - 1                                  # the off run appended every row but the last (n - 1 steps)
-        assert not bool((k_off[l][:, :, L:n_off] == K_SENT).all(dim=-1).any())      # so the sentinel check above says something
-    if lg_on is not None:
-        assert torch.equal(lg_on[:, :live + 1], lg_off[:, :live + 1])
-        assert bool((lg_on[:, live + 1:] == LOGIT_SENT).all())
-        assert not bool((lg_off == LOGIT_SENT).all(dim=-1).any())
-
-
 @pytest.fixture(scope="module")
 def zero_small():
-    llm = _zero_head(_small_decoder())
+    llm = lu.zero_head(lu.small_decoder())
     dec = _HipDecoder(llm, 64)
     yield llm, dec
     dec.close()
@@ -97,7 +60,7 @@ def zero_small():
 
 @pytest.fixture(scope="module")
 def small():
-    llm = _small_decoder()
+    llm = lu.small_decoder()
     dec = _HipDecoder(llm, 64)
     yield llm, dec
     dec.close()
@@ -108,7 +71,7 @@ def small():
 def test_exact_finishing_step_small_decoder(zero_small, min_new, want):
     llm, dec = zero_small
     B, L, n = 37, 12, 8
-    first, kb, vb, _ = _prefill(llm, llm.get_input_embeddings()(_ids(llm, B, L, 3)), n)      # the model's own prefill
+    first, kb, vb, _ = lu.prefill(llm, llm.get_input_embeddings()(lu.ids(llm, B, L, 3)), n)      # the model's own prefill
     assert bool((first == 0).all())
     off = _greedy(dec, False, first, L, n, min_new, [0], 0, kb, vb, logits=True)
     on = _greedy(dec, True, first, L, n, min_new, [0], 0, kb, vb, logits=True)
@@ -117,11 +80,11 @@ def test_exact_finishing_step_small_decoder(zero_small, min_new, want):
     assert torch.equal(off[0], want_tokens)                            # the law of the module docstring
     assert torch.equal(on[0], off[0])
     assert off[1] == n - 1 and on[1] == want == expected_live_steps(off[0], [0])
-    _check_dead_part(L, want, on, off)
+    lu.check_dead_part(L, want, on, off)
     # the same without step logits (the engine's own logits buffer)
     on2 = _greedy(dec, True, first, L, n, min_new, [0], 0, kb, vb)
     assert torch.equal(on2[0], off[0]) and on2[1] == want
-    _check_dead_part(L, want, on2, off[:4] + (None,))
+    lu.check_dead_part(L, want, on2, off[:4] + (None,))
 
 
 # ------------------------------------------------------------------------------------------ 2. + 3. staggered finish on natural rows
@@ -137,15 +100,15 @@ def _staggered(dec, first, L, n, kb, vb, starts=None):
     on = _greedy(dec, True, first, L, n, 0, eos, 0, kb, vb, starts=starts)
     assert torch.equal(on[0], off[0])
     assert off[1] == n - 1 and on[1] == expected_live_steps(off[0], eos) == F
-    _check_dead_part(L, F, on, off)
+    lu.check_dead_part(L, F, on, off)
     return F
 
 
 def test_staggered_finish_on_natural_rows(small):
     llm, dec = small
     B, L, n = 5, 12, 8
-    kb, vb = _sentinel_cache(dec, B, L + n)
-    first = dec.prefill(llm.get_input_embeddings()(_ids(llm, B, L, 4)).contiguous(), kb, vb)
+    kb, vb = lu.sentinel_cache(dec.layers, dec.heads, B, L + n)
+    first = dec.prefill(llm.get_input_embeddings()(lu.ids(llm, B, L, 4)).contiguous(), kb, vb)
     _staggered(dec, first, L, n, kb, vb)
 
 
@@ -153,10 +116,10 @@ def test_staggered_finish_on_left_padded_rows(small):
     llm, dec = small
     B, L, n = 5, 12, 8
     starts = torch.tensor([0, 1, 5, 11, 3], dtype=torch.int32, device=DEV)
-    embs = llm.get_input_embeddings()(_ids(llm, B, L, 4)).clone()
+    embs = llm.get_input_embeddings()(lu.ids(llm, B, L, 4)).clone()
     for b, s in enumerate(starts.tolist()):
         embs[b, :s] = 0
-    kb, vb = _sentinel_cache(dec, B, L + n)
+    kb, vb = lu.sentinel_cache(dec.layers, dec.heads, B, L + n)
     first = dec.prefill(embs.contiguous(), kb, vb, starts=starts)
     _staggered(dec, first, L, n, kb, vb, starts=starts)
 
@@ -167,12 +130,12 @@ def test_int8_handle(zero_small):
     dec = _HipDecoder(llm, 64, weights="int8")
     try:
         B, L, n = 37, 12, 8
-        kb, vb = _sentinel_cache(dec, B, L + n)
-        first = dec.prefill(llm.get_input_embeddings()(_ids(llm, B, L, 3)).contiguous(), kb, vb)
+        kb, vb = lu.sentinel_cache(dec.layers, dec.heads, B, L + n)
+        first = dec.prefill(llm.get_input_embeddings()(lu.ids(llm, B, L, 3)).contiguous(), kb, vb)
         off = _greedy(dec, False, first, L, n, 3, [0], 0, kb, vb)
         on = _greedy(dec, True, first, L, n, 3, [0], 0, kb, vb)
         assert torch.equal(on[0], off[0]) and on[1] == 3 == expected_live_steps(off[0], [0]) and off[1] == n - 1
-        _check_dead_part(L, 3, on, off)
+        lu.check_dead_part(L, 3, on, off)
     finally:
         dec.close()
 
@@ -181,7 +144,7 @@ def test_int8_handle(zero_small):
 def test_one_capture_serves_every_finishing_step(zero_small):
     llm, dec = zero_small
     B, L, n = 37, 12, 8
-    first0, kb, vb, _ = _prefill(llm, llm.get_input_embeddings()(_ids(llm, B, L, 3)), n)
+    first0, kb, vb, _ = lu.prefill(llm, llm.get_input_embeddings()(lu.ids(llm, B, L, 3)), n)
     late = first0.clone()
     late[:, 5] = 1.0                                                   # select 0 picks token 5, the zero logits of step 1 give EOS: F = 1
     at_once = first0.clone()
@@ -213,22 +176,22 @@ def test_one_capture_serves_every_finishing_step(zero_small):
         off, on = eager[name]
         got = replay(late if name == "late" else at_once)
         assert torch.equal(got[0], off[0]) and got[1] == on[1] == expected_live_steps(off[0], [0]), name
-        _check_dead_part(L, on[1], got, off)
+        lu.check_dead_part(L, on[1], got, off)
     del graph
 
 
 # ------------------------------------------------------------------------------------------ 6. Vicuna width
 def test_vicuna_width():
-    llm = _zero_head(_vicuna_width_decoder())
+    llm = lu.zero_head(lu.vicuna_width_decoder())
     dec = _HipDecoder(llm, 200)
     try:
         B, L, n = 200, 44, 6
-        kb, vb = _sentinel_cache(dec, B, L + n)
-        first = dec.prefill(llm.get_input_embeddings()(_ids(llm, B, L, 3)).contiguous(), kb, vb)
+        kb, vb = lu.sentinel_cache(dec.layers, dec.heads, B, L + n)
+        first = dec.prefill(llm.get_input_embeddings()(lu.ids(llm, B, L, 3)).contiguous(), kb, vb)
         off = _greedy(dec, False, first, L, n, 2, [0], 0, kb, vb)
         on = _greedy(dec, True, first, L, n, 2, [0], 0, kb, vb)
         assert torch.equal(on[0], off[0]) and on[1] == 2 == expected_live_steps(off[0], [0]) and off[1] == n - 1
-        _check_dead_part(L, 2, on, off, layers=(0, 1))
+        lu.check_dead_part(L, 2, on, off, layers=(0, 1))
     finally:
         dec.close()
         del llm

@@ -18,40 +18,15 @@ import torch
 import certifiedgpt_amd as cg
 from certifiedgpt_amd.agents.label_adapter import AnswerLabelMap
 from certifiedgpt_amd.minigpt4 import (MiniGPT4Classifier, WordHashTokenizer, _HipDecoder, expand_kv_state_dict, hip_decode_unsupported,
-                                       int8_state_dict, left_pad_embeds, prepare_texts)
+                                       int8_state_dict, left_pad_embeds)
 from oracle import model_oracle as mo
 from gpu_util import DEV, make_classifier
-from test_gpu_llm_decode import _check_ratios, _teacher_forced
-from test_llm_early_stop_cpu import expected_live_steps
+import llm_util as lu
+from llm_util import PAD, EOS, K_SENTINEL, V_SENTINEL, PROMPT
 
 pytestmark = pytest.mark.gpu
 
-PAD, BOS, EOS = 0, 1, 2
-K_SENTINEL, V_SENTINEL = 77.0, -55.0
-PROMPT = prepare_texts(["<Img><ImageHere></Img> [vqa] what is shown in the picture"])[0]
 GUARD = 5                                                              # sentinel positions behind every cache
-
-
-def _decoder(hidden, heads, kv_heads, mlp, vocab, layers=2, theta=10000.0, sd=None):
-    """A frozen random-init fp16 LlamaForCausalLM on the device (no checkpoint is in the container; nothing is downloaded)."""
-    from transformers import LlamaConfig, LlamaForCausalLM
-    lcfg = LlamaConfig(vocab_size=vocab, hidden_size=hidden, intermediate_size=mlp, num_hidden_layers=layers, num_attention_heads=heads,
-                       num_key_value_heads=kv_heads, max_position_embeddings=2048, pad_token_id=PAD, bos_token_id=BOS, eos_token_id=EOS,
-                       rope_theta=theta)
-    torch.manual_seed(0)
-    prev = torch.get_default_dtype()
-    torch.set_default_dtype(torch.float16)
-    try:
-        with torch.device(DEV):
-            llm = LlamaForCausalLM(lcfg).eval()
-    finally:
-        torch.set_default_dtype(prev)
-    if sd is not None:
-        missing, unexpected = llm.load_state_dict(sd, strict=True)
-        assert not missing and not unexpected
-    for prm in llm.parameters():
-        prm.requires_grad = False
-    return llm
 
 
 class _Pair:
@@ -59,8 +34,8 @@ class _Pair:
 
     def __init__(self, hidden, heads, kv_heads, mlp=1408, vocab=320):
         self.G = heads // kv_heads
-        self.llm = _decoder(hidden, heads, kv_heads, mlp, vocab)
-        self.twin = _decoder(hidden, heads, heads, mlp, vocab, sd=expand_kv_state_dict(self.llm))
+        self.llm = lu.llama_decoder(hidden, heads, mlp, vocab, kv_heads=kv_heads)
+        self.twin = lu.llama_decoder(hidden, heads, mlp, vocab, kv_heads=heads, sd=expand_kv_state_dict(self.llm))
         assert hip_decode_unsupported(self.llm, 64, grouped_kv=True) == []
         self.gqa = _HipDecoder(self.llm, 64, grouped_kv=True)
         self.mha = _HipDecoder(self.twin, 64)
@@ -87,19 +62,6 @@ def pairs():
         p.close()
 
 
-def _buffers(dec, B, length):
-    """Caches [B, kv_heads, length + GUARD, 128] of the engine `dec`, sentinel-filled: positions length .. are the guard region."""
-    shape = (B, dec.kv_heads, length + GUARD, 128)
-    kb = [torch.full(shape, K_SENTINEL, dtype=torch.float16, device=DEV) for _ in range(dec.layers)]
-    vb = [torch.full(shape, V_SENTINEL, dtype=torch.float16, device=DEV) for _ in range(dec.layers)]
-    return kb, vb
-
-
-def _embeds(llm, B, L, seed):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    return llm.get_input_embeddings()(torch.randint(3, llm.config.vocab_size, (B, L), generator=g).to(DEV)).contiguous()
-
-
 def _same_caches(grouped, twin, G, where):
     """Grouped cache head g == twin heads g G .. g G + G - 1, every layer and position (sentinels included: nothing else written)."""
     for l, (x, y) in enumerate(zip(grouped, twin)):
@@ -108,7 +70,7 @@ def _same_caches(grouped, twin, G, where):
 
 def _run(dec, embs, n_new, starts=None, min_new=1, eos=(EOS,)):
     B, L = embs.shape[:2]
-    kb, vb = _buffers(dec, B, L + n_new - 1)
+    kb, vb = lu.sentinel_cache(dec.layers, dec.kv_heads, B, L + n_new - 1 + GUARD)
     first = dec.prefill(embs, kb, vb, starts=starts)
     tokens, steps = dec.greedy(first, L, n_new, min_new, list(eos), PAD, kb, vb, return_logits=True, starts=starts)
     torch.cuda.synchronize()
@@ -121,9 +83,9 @@ def _run(dec, embs, n_new, starts=None, min_new=1, eos=(EOS,)):
 def test_prefill_equals_the_plain_engine_on_the_expanded_twin(pairs, which, L):
     p = pairs(which)
     for B in (5, 37):
-        embs = _embeds(p.llm, B, L, seed=B + L)
-        ka, va = _buffers(p.gqa, B, L)
-        kb, vb = _buffers(p.mha, B, L)
+        embs = lu.embeds(p.llm, B, L, seed=B + L)
+        ka, va = lu.sentinel_cache(p.gqa.layers, p.gqa.kv_heads, B, L + GUARD)
+        kb, vb = lu.sentinel_cache(p.mha.layers, p.mha.kv_heads, B, L + GUARD)
         a = p.gqa.prefill(embs, ka, va)
         b = p.mha.prefill(embs, kb, vb)
         torch.cuda.synchronize()
@@ -155,12 +117,12 @@ def test_steps_and_greedy_equal_the_plain_engine_on_the_expanded_twin(pairs, whi
         (f"the decode GEMM's K split differs between the grouped q/k/v width {n_grouped} and the twin's {n_twin} at hidden {hidden}: the "
          "steps below are then two valid summation orders, not bit-equal -- choose shapes with equal slice counts")
     B, L, steps = 37, 12, 4
-    embs = _embeds(p.llm, B, L, seed=3)
+    embs = lu.embeds(p.llm, B, L, seed=3)
     g = torch.Generator(device="cpu").manual_seed(11)
     forced = torch.randint(3, 320, (steps, B), generator=g).to(DEV)
     got = {}
     for name, dec in (("gqa", p.gqa), ("mha", p.mha)):
-        kb, vb = _buffers(dec, B, L + steps)
+        kb, vb = lu.sentinel_cache(dec.layers, dec.kv_heads, B, L + steps + GUARD)
         logits = [dec.prefill(embs, kb, vb)]
         for i in range(steps):
             logits.append(dec.step(forced[i].contiguous(), L + i, kb, vb))
@@ -180,7 +142,7 @@ def test_steps_and_greedy_equal_the_plain_engine_on_the_expanded_twin(pairs, whi
 def test_a_long_row_crosses_the_step_kernels_staging_chunks(pairs):
     """Prompt 130: the step attention walks three 64-key chunks, the last one partial and holding the new key."""
     p = pairs("g4")
-    embs = _embeds(p.llm, 5, 130, seed=9)
+    embs = lu.embeds(p.llm, 5, 130, seed=9)
     a, b = _run(p.gqa, embs, 4), _run(p.mha, embs, 4)
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[2], b[2])
     _same_caches(a[3], b[3], p.G, "long row K")
@@ -193,7 +155,7 @@ def test_a_padded_row_equals_the_row_alone_on_the_same_grouped_handle(pairs, whi
     p = pairs(which)
     L, n_new = 80, 5
     lens = [1, 15, 16, 17, 63, 64, 65, 80]
-    embs, _, starts = left_pad_embeds([_embeds(p.llm, 1, n, seed=100 + n) for n in lens])
+    embs, _, starts = left_pad_embeds([lu.embeds(p.llm, 1, n, seed=100 + n) for n in lens])
     assert embs.shape[1] == L
     embs, starts = embs.contiguous(), starts.to(DEV)
     a = _run(p.gqa, embs, n_new, starts)
@@ -207,8 +169,8 @@ def test_a_padded_row_equals_the_row_alone_on_the_same_grouped_handle(pairs, whi
                 assert torch.equal(padded[b, :, s:L + n_new - 1], alone[0, :, :n + n_new - 1]), where
                 assert bool((padded[b, :, :s] == sentinel).all()), where + ": rows below start[b] were touched"
     # the step entry itself, teacher-forced, against the twin through the same ragged entries
-    ka, va = _buffers(p.gqa, len(lens), L + 1)
-    kb, vb = _buffers(p.mha, len(lens), L + 1)
+    ka, va = lu.sentinel_cache(p.gqa.layers, p.gqa.kv_heads, len(lens), L + 1 + GUARD)
+    kb, vb = lu.sentinel_cache(p.mha.layers, p.mha.kv_heads, len(lens), L + 1 + GUARD)
     p.gqa.prefill(embs, ka, va, starts=starts)
     p.mha.prefill(embs, kb, vb, starts=starts)
     tok = torch.randint(3, 320, (len(lens),), generator=torch.Generator().manual_seed(1)).to(DEV)
@@ -224,7 +186,7 @@ def test_a_padded_row_equals_the_row_alone_on_the_same_grouped_handle(pairs, whi
 def test_only_the_prompt_and_the_appended_rows_are_written(pairs, which):
     p = pairs(which)
     L, n_new = 21, 6
-    _, _, _, kb, vb = _run(p.gqa, _embeds(p.llm, 7, L, seed=2), n_new)
+    _, _, _, kb, vb = _run(p.gqa, lu.embeds(p.llm, 7, L, seed=2), n_new)
     used = L + n_new - 1                                               # positions 0 .. prompt + steps - 1
     for l in range(len(kb)):
         assert tuple(kb[l].shape) == (7, p.gqa.kv_heads, used + GUARD, 128)
@@ -236,10 +198,10 @@ def test_only_the_prompt_and_the_appended_rows_are_written(pairs, which):
 def test_graph_replays_and_row_splits_are_bit_identical(pairs):
     p = pairs("g4")
     L, n_new = 12, 4
-    embs = _embeds(p.llm, 37, L, seed=3)
+    embs = lu.embeds(p.llm, 37, L, seed=3)
     eager = _run(p.gqa, embs, n_new)
     static = embs.clone()
-    kb, vb = _buffers(p.gqa, 37, L + n_new - 1)
+    kb, vb = lu.sentinel_cache(p.gqa.layers, p.gqa.kv_heads, 37, L + n_new - 1 + GUARD)
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
@@ -268,7 +230,7 @@ def test_graph_replays_and_row_splits_are_bit_identical(pairs):
 def test_scores_equal_the_twins_and_leave_the_cache_alone(pairs, which):
     p = pairs(which)
     B, L, n_new = 5, 13, 4
-    embs = _embeds(p.llm, B, L, seed=4)
+    embs = lu.embeds(p.llm, B, L, seed=4)
     g = torch.Generator(device="cpu").manual_seed(5)
     cands = [torch.randint(3, 320, (n,), generator=g) for n in (1, 2, 5)]
     table = torch.zeros((3, 5), dtype=torch.long)
@@ -277,7 +239,7 @@ def test_scores_equal_the_twins_and_leave_the_cache_alone(pairs, which):
     table, lens = table.to(DEV), [len(c) for c in cands]
     out = {}
     for name, dec in (("gqa", p.gqa), ("mha", p.mha)):
-        kb, vb = _buffers(dec, B, L + n_new - 1)
+        kb, vb = lu.sentinel_cache(dec.layers, dec.kv_heads, B, L + n_new - 1 + GUARD)
         first = dec.prefill(embs, kb, vb)
         before = [t.clone() for t in kb + vb]
         sums = dec.score(first, L, table, lens, 0.1, kb, vb)
@@ -294,13 +256,13 @@ def test_scores_equal_the_twins_and_leave_the_cache_alone(pairs, which):
 # ------------------------------------------------------------------------------------------ 7. int8
 def test_a_grouped_int8_handle_equals_a_grouped_fp16_handle_on_the_dequantised_weights(pairs):
     p = pairs("g4")
-    twin8 = _decoder(512, 4, 1, 1408, 320, sd=int8_state_dict(p.llm, device="cpu"))
+    twin8 = lu.llama_decoder(512, 4, 1408, 320, kv_heads=1, sd=int8_state_dict(p.llm, device="cpu"))
     q8 = _HipDecoder(p.llm, 64, weights="int8", grouped_kv=True)
     f16 = _HipDecoder(twin8, 64, grouped_kv=True)
     try:
         assert q8.weight_bytes < f16.weight_bytes < p.mha.weight_bytes
         for L in (12, 70):
-            embs = _embeds(p.llm, 37, L, seed=L)
+            embs = lu.embeds(p.llm, 37, L, seed=L)
             a, b = _run(q8, embs, 5), _run(f16, embs, 5)
             assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[2], b[2]), L
             for x, y in zip(a[3] + a[4], b[3] + b[4]):
@@ -316,16 +278,16 @@ def test_early_stop_tokens_and_live_steps(pairs, F):
     """The synthetic finishing law of test_gpu_llm_early_stop.py: with lm_head = 0 every logit is 0 and the first-max arg-max is
     token 0, which is the EOS and pad id here; it is suppressed on the first F tokens (then token 1 wins), so every row finishes at
     select F."""
-    llm = _decoder(512, 4, 2, 1408, 320)
+    llm = lu.llama_decoder(512, 4, 1408, 320, kv_heads=2)
     with torch.no_grad():
         llm.lm_head.weight.zero_()
     dec = _HipDecoder(llm, 64, grouped_kv=True)
     try:
         B, L, n = 9, 12, 8
-        embs = _embeds(llm, B, L, seed=3)
+        embs = lu.embeds(llm, B, L, seed=3)
         res = {}
         for on in (False, True):
-            kb, vb = _buffers(dec, B, L + n - 1)
+            kb, vb = lu.sentinel_cache(dec.layers, dec.kv_heads, B, L + n - 1 + GUARD)
             first = dec.prefill(embs, kb, vb)
             dec.set_early_stop(on)
             try:
@@ -336,7 +298,7 @@ def test_early_stop_tokens_and_live_steps(pairs, F):
         want = torch.zeros(B, n, dtype=torch.int64, device=DEV)
         want[:, :F] = 1
         assert torch.equal(res[False][0], want) and torch.equal(res[True][0], res[False][0])
-        assert res[False][1] == n - 1 and res[True][1] == F == expected_live_steps(res[False][0], [0])
+        assert res[False][1] == n - 1 and res[True][1] == F == lu.expected_live_steps(res[False][0], [0])
         for l in range(dec.layers):                                    # the dead steps appended nothing; the live ones what the off run did
             assert bool((res[True][2][l][:, :, L + F:] == K_SENTINEL).all()) and bool((res[True][3][l][:, :, L + F:] == V_SENTINEL).all())
             assert torch.equal(res[True][2][l][:, :, :L + F], res[False][2][l][:, :, :L + F])
@@ -349,7 +311,7 @@ def test_early_stop_tokens_and_live_steps(pairs, F):
 def llama3():
     """Llama-3-8B's widths (hidden 4096, 32 / 8 heads, MLP 14336, rope_theta 500000) with 2 random-init layers and a 32000-token
     vocabulary (the real 128256 adds seconds, not coverage)."""
-    llm = _decoder(4096, 32, 8, 14336, 32000, theta=500000.0)
+    llm = lu.llama_decoder(4096, 32, 14336, 32000, kv_heads=8, theta=500000.0)
     dec = _HipDecoder(llm, 200, grouped_kv=True)
     llm32 = copy.deepcopy(llm).float()
     yield llm, dec, llm32
@@ -361,21 +323,7 @@ def llama3():
 @pytest.mark.parametrize("B", [200, 37])
 def test_teacher_forced_step_error_is_within_hfs_own_fp16_error_llama3_width(llama3, B):
     llm, dec, _ = llama3
-    _check_ratios(f"Llama-3 width, grouped_kv, {B} rows", _teacher_forced(llm, dec, B, L=44, steps=4))
-
-
-def _model_prefill(model, embs):
-    from transformers import DynamicCache
-    cache = DynamicCache(config=model.config)
-    with torch.no_grad():
-        out = model(inputs_embeds=embs, position_ids=torch.arange(embs.shape[1], device=DEV)[None], past_key_values=cache, use_cache=True,
-                    logits_to_keep=1)
-    return out.logits[:, -1].float(), [l.keys for l in cache.layers], [l.values for l in cache.layers]
-
-
-def _err(a, ref):
-    d = (a.float() - ref.float()).abs()
-    return float(d.max()), float(d.pow(2).mean().sqrt())
+    lu.check_ratios(f"Llama-3 width, grouped_kv, {B} rows", lu.teacher_forced(llm, dec, B, L=44, steps=4))
 
 
 @pytest.mark.parametrize("L", [12, 44])
@@ -383,18 +331,18 @@ def test_prefill_error_is_within_hfs_own_fp16_error_llama3_width(llama3, L):
     """The criterion of test_gpu_llm_prefill.py (`_check_against_hf`) on caches of kv_heads heads."""
     llm, dec, llm32 = llama3
     B = 37
-    embs = _embeds(llm, B, L, seed=3)
-    kb, vb = _buffers(dec, B, L)
+    embs = lu.embeds(llm, B, L, seed=3)
+    kb, vb = lu.sentinel_cache(dec.layers, dec.kv_heads, B, L + GUARD)
     lib = dec.prefill(embs, kb, vb)
     torch.cuda.synchronize()
-    hf, hk, hv = _model_prefill(llm, embs)
-    ref, rk, rv = _model_prefill(llm32, embs.float())
+    hf, hk, hv = lu.model_prefill(llm, embs)
+    ref, rk, rv = lu.model_prefill(llm32, embs.float())
     assert hk[0].shape[1] == 8 and bool(torch.isfinite(lib).all())
-    figures = {"logits": _err(lib, ref) + _err(hf, ref)}
+    figures = {"logits": lu.err(lib, ref) + lu.err(hf, ref)}
     share = {}
     for l in range(len(kb)):
         for nm, mine, theirs, exact in (("k", kb[l], hk[l], rk[l]), ("v", vb[l], hv[l], rv[l])):
-            figures[f"{nm}{l}"] = _err(mine[:, :, :L], exact) + _err(theirs, exact)
+            figures[f"{nm}{l}"] = lu.err(mine[:, :, :L], exact) + lu.err(theirs, exact)
             if l == 0:
                 share[nm] = float((mine[:, :, :L] == theirs).float().mean())
     print(f"[prefill Llama-3 width, grouped_kv, {B} rows x {L} positions] (max, rms) error ratio library / HF against the fp32 model: "
@@ -436,7 +384,8 @@ def test_classifier_answers_and_certificate_equal_the_twin_classifiers(pairs):
             for extra in (dict(prefill="hip", ragged="hip", prompt_bucket=16, weights="int8"), dict(prefill="model")):
                 model, twin = p.llm, p.twin
                 if extra.get("weights") == "int8":                     # the twin of an int8 engine: dequantised, then expanded
-                    twin = _decoder(512, 4, 4, 1408, 320, sd=expand_kv_state_dict(_decoder(512, 4, 2, 1408, 320, sd=int8_state_dict(p.llm, device="cpu"))))
+                    twin = lu.llama_decoder(512, 4, 1408, 320, kv_heads=4, sd=expand_kv_state_dict(
+                        lu.llama_decoder(512, 4, 1408, 320, kv_heads=2, sd=int8_state_dict(p.llm, device="cpu"))))
                     extra_ref = dict(prefill="hip", ragged="hip", prompt_bucket=16)
                 else:
                     extra_ref = extra

@@ -18,33 +18,13 @@ import torch
 import certifiedgpt_amd as cg
 from certifiedgpt_amd.agents.label_adapter import AnswerLabelMap
 from certifiedgpt_amd.minigpt4 import (MiniGPT4Classifier, WordHashTokenizer, _HipDecoder, greedy_decode_parity, int8_state_dict,
-                                       left_pad_embeds, prepare_texts)
+                                       left_pad_embeds)
 from oracle import model_oracle as mo
 from gpu_util import DEV, make_classifier
+import llm_util as lu
+from llm_util import PAD, EOS, K_SENTINEL, PROMPT
 
 pytestmark = pytest.mark.gpu
-
-PAD, BOS, EOS = 0, 1, 2
-K_SENTINEL, V_SENTINEL = 77.0, -55.0
-PROMPT = prepare_texts(["<Img><ImageHere></Img> [vqa] what is shown in the picture"])[0]
-
-
-def _decoder(hidden, heads, mlp, vocab, layers=2):
-    """A frozen random-init fp16 LlamaForCausalLM on the device (no checkpoint is in the container; nothing is downloaded)."""
-    from transformers import LlamaConfig, LlamaForCausalLM
-    lcfg = LlamaConfig(vocab_size=vocab, hidden_size=hidden, intermediate_size=mlp, num_hidden_layers=layers, num_attention_heads=heads,
-                       num_key_value_heads=heads, max_position_embeddings=2048, pad_token_id=PAD, bos_token_id=BOS, eos_token_id=EOS)
-    torch.manual_seed(0)
-    prev = torch.get_default_dtype()
-    torch.set_default_dtype(torch.float16)
-    try:
-        with torch.device(DEV):
-            llm = LlamaForCausalLM(lcfg).eval()
-    finally:
-        torch.set_default_dtype(prev)
-    for prm in llm.parameters():
-        prm.requires_grad = False
-    return llm
 
 
 def _twin(llm):
@@ -57,7 +37,7 @@ def _twin(llm):
 
 class _Pair:
     def __init__(self, hidden, heads, mlp, vocab):
-        self.llm = _decoder(hidden, heads, mlp, vocab)
+        self.llm = lu.llama_decoder(hidden, heads, mlp, vocab)
         self.twin = _twin(self.llm)
         self.int8 = _HipDecoder(self.llm, 200, weights="int8")         # quantised by the library from W
         self.fp16 = _HipDecoder(self.twin, 200)                        # the existing fp16 engine on W'
@@ -85,19 +65,6 @@ def vicuna():
     torch.cuda.empty_cache()
 
 
-def _buffers(llm, B, length):
-    cfg = llm.config
-    shape = (B, cfg.num_attention_heads, length, 128)
-    kb = [torch.full(shape, K_SENTINEL, dtype=torch.float16, device=DEV) for _ in range(cfg.num_hidden_layers)]
-    vb = [torch.full(shape, V_SENTINEL, dtype=torch.float16, device=DEV) for _ in range(cfg.num_hidden_layers)]
-    return kb, vb
-
-
-def _embeds(llm, B, L, seed):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    return llm.get_input_embeddings()(torch.randint(3, llm.config.vocab_size, (B, L), generator=g).to(DEV)).contiguous()
-
-
 def _same_caches(a, b, where):
     for l, (x, y) in enumerate(zip(a, b)):
         assert torch.equal(x, y), f"{where}: cache of layer {l} differs"
@@ -117,12 +84,12 @@ def test_the_quantised_model_differs_from_the_model(small):
 def test_teacher_forced_steps_equal_the_fp16_engine_on_the_dequantised_weights(which, B, request):
     p = request.getfixturevalue(which)
     L, steps = 44, 4
-    embs = _embeds(p.llm, B, L, seed=B)
+    embs = lu.embeds(p.llm, B, L, seed=B)
     g = torch.Generator(device="cpu").manual_seed(7 + B)
     forced = torch.randint(3, p.llm.config.vocab_size, (steps, B), generator=g).to(DEV)
     got = {}
     for name, dec in (("int8", p.int8), ("fp16", p.fp16)):
-        kb, vb = _buffers(p.llm, B, L + steps + 2)
+        kb, vb = lu.sentinel_cache(p.llm.config.num_hidden_layers, p.llm.config.num_attention_heads, B, L + steps + 2)
         logits = [dec.prefill(embs, kb, vb)]
         for i in range(steps):
             logits.append(dec.step(forced[i].contiguous(), L + i, kb, vb))
@@ -141,7 +108,7 @@ def test_teacher_forced_steps_equal_the_fp16_engine_on_the_dequantised_weights(w
 # ------------------------------------------------------------------------------------------ 2. prefill and greedy
 def _run(dec, llm, embs, n_new, starts=None):
     B, L = embs.shape[:2]
-    kb, vb = _buffers(llm, B, L + n_new + 1)
+    kb, vb = lu.sentinel_cache(llm.config.num_hidden_layers, llm.config.num_attention_heads, B, L + n_new + 1)
     first = dec.prefill(embs, kb, vb, starts=starts)
     tokens, steps = dec.greedy(first, L, n_new, 1, [EOS], PAD, kb, vb, return_logits=True, starts=starts)
     torch.cuda.synchronize()
@@ -159,13 +126,13 @@ def _assert_same_run(a, b, where):
 
 @pytest.mark.parametrize("L", [1, 12, 44, 70, 300])
 def test_prefill_and_greedy_equal_the_fp16_engine_small_decoder(small, L):
-    embs = _embeds(small.llm, 37, L, seed=L)
+    embs = lu.embeds(small.llm, 37, L, seed=L)
     _assert_same_run(_run(small.int8, small.llm, embs, 5), _run(small.fp16, small.twin, embs, 5), f"small decoder, 37 rows, L {L}")
 
 
 @pytest.mark.parametrize("B, L", [(200, 12), (200, 44), (37, 12), (37, 44)])
 def test_prefill_and_greedy_equal_the_fp16_engine_vicuna_width(vicuna, B, L):
-    embs = _embeds(vicuna.llm, B, L, seed=B + L)
+    embs = lu.embeds(vicuna.llm, B, L, seed=B + L)
     _assert_same_run(_run(vicuna.int8, vicuna.llm, embs, 5), _run(vicuna.fp16, vicuna.twin, embs, 5), f"Vicuna width, {B} rows, L {L}")
 
 
@@ -173,14 +140,15 @@ def test_left_padded_rows_through_the_ragged_entries(small):
     L, n_new = 48, 5
     g = torch.Generator(device="cpu").manual_seed(48)
     lens = torch.randint(1, L + 1, (60,), generator=g).tolist()
-    embs, _, starts = left_pad_embeds([_embeds(small.llm, 1, n, seed=100 + i) for i, n in enumerate(lens)])
+    embs, _, starts = left_pad_embeds([lu.embeds(small.llm, 1, n, seed=100 + i) for i, n in enumerate(lens)])
     assert embs.shape[1] == max(lens) and len(set(lens)) > 10
     embs, starts = embs.contiguous(), starts.to(DEV)
     a = _run(small.int8, small.llm, embs, n_new, starts)               # cgpt_llm_prefill_ragged, _greedy_ragged (-> _step_ragged's kernels)
     b = _run(small.fp16, small.twin, embs, n_new, starts)
     _assert_same_run(a, b, "ragged, small decoder")
-    kb, vb = _buffers(small.llm, 60, embs.shape[1] + 2)                # and the step entry itself, teacher-forced
-    kb2, vb2 = _buffers(small.llm, 60, embs.shape[1] + 2)
+    cfg = small.llm.config                                             # and the step entry itself, teacher-forced
+    kb, vb = lu.sentinel_cache(cfg.num_hidden_layers, cfg.num_attention_heads, 60, embs.shape[1] + 2)
+    kb2, vb2 = lu.sentinel_cache(cfg.num_hidden_layers, cfg.num_attention_heads, 60, embs.shape[1] + 2)
     small.int8.prefill(embs, kb, vb, starts=starts)
     small.fp16.prefill(embs, kb2, vb2, starts=starts)
     tok = torch.randint(3, 320, (60,), generator=g).to(DEV)
@@ -201,10 +169,10 @@ def test_graph_replays_and_row_splits_are_bit_identical(vicuna):
     the graph must hold), and 200 rows equal the same rows run as 128 + 72: 2400 / 1536 token rows take the large-shape kernel,
     864 take the 128 x 128 kernel, all of them reading the scratch."""
     L, n_new = 12, 4
-    embs = _embeds(vicuna.llm, 200, L, seed=3)
+    embs = lu.embeds(vicuna.llm, 200, L, seed=3)
     eager = _run(vicuna.int8, vicuna.llm, embs, n_new)
     static = embs.clone()
-    kb, vb = _buffers(vicuna.llm, 200, L + n_new + 1)
+    kb, vb = lu.sentinel_cache(vicuna.llm.config.num_hidden_layers, vicuna.llm.config.num_attention_heads, 200, L + n_new + 1)
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
@@ -231,10 +199,6 @@ def test_graph_replays_and_row_splits_are_bit_identical(vicuna):
 
 
 # ------------------------------------------------------------------------------------------ 4. the bytes
-def _up256(n):
-    return (n + 255) // 256 * 256
-
-
 @pytest.mark.parametrize("which", ["small", "vicuna"])
 def test_weight_bytes_is_the_formula(which, request):
     p = request.getfixturevalue(which)
@@ -242,17 +206,17 @@ def test_weight_bytes_is_the_formula(which, request):
     H, F, V, layers = c.hidden_size, c.intermediate_size, c.vocab_size, c.num_hidden_layers
     mats = [(3 * H, H), (H, H), (2 * F, H), (H, F)]                    # fused q/k/v, o, fused gate/up, down: [N, K]
     table = 2 * V * H * 2                                              # embed_tokens and lm_head, fp16
-    scratch = max(_up256(n) * k for n, k in mats) * 2                  # one fp16 matrix, the largest: up256(2 mlp) x hidden
-    assert scratch == _up256(2 * F) * H * 2
-    int8 = layers * sum(_up256(n) * k + _up256(n) * 2 for n, k in mats) + table + scratch     # int8 rows + fp16 scales, padded alike
-    fp16 = layers * sum(_up256(n) * k * 2 for n, k in mats) + table
+    scratch = max(lu.up256(n) * k for n, k in mats) * 2                  # one fp16 matrix, the largest: up256(2 mlp) x hidden
+    assert scratch == lu.up256(2 * F) * H * 2
+    int8 = layers * sum(lu.up256(n) * k + lu.up256(n) * 2 for n, k in mats) + table + scratch     # int8 rows + fp16 scales, padded alike
+    fp16 = layers * sum(lu.up256(n) * k * 2 for n, k in mats) + table
     assert p.int8.weight_bytes == int8, (p.int8.weight_bytes, int8)
     assert p.fp16.weight_bytes == fp16, (p.fp16.weight_bytes, fp16)
     assert p.int8.weight_bytes < p.fp16.weight_bytes
     if which == "vicuna":                                              # the 7B figure of DESIGN.md 4.4.3, from the same formula
         full = lambda per_layer, extra: 32 * per_layer + table + extra  # noqa: E731
-        i32 = full(sum(_up256(n) * k + _up256(n) * 2 for n, k in mats), scratch)
-        f32 = full(sum(_up256(n) * k * 2 for n, k in mats), 0)
+        i32 = full(sum(lu.up256(n) * k + lu.up256(n) * 2 for n, k in mats), scratch)
+        f32 = full(sum(lu.up256(n) * k * 2 for n, k in mats), 0)
         print(f"[weight_bytes, 7B widths x 32 layers, derived] int8 {i32 / 1e9:.3f} GB, fp16 {f32 / 1e9:.3f} GB, ratio {i32 / f32:.3f}", flush=True)
 
 
@@ -308,36 +272,22 @@ def test_classifier_answers_and_certificate_equal_the_fp16_engine_on_the_dequant
 
 
 # ------------------------------------------------------------------------------------------ 6. what the quantisation costs (measured)
-def _model_prefill(model, embs):
-    from transformers import DynamicCache
-    cache = DynamicCache(config=model.config)
-    pos = torch.arange(embs.shape[1], device=embs.device).unsqueeze(0)
-    with torch.no_grad():
-        out = model(inputs_embeds=embs, position_ids=pos, past_key_values=cache, use_cache=True, logits_to_keep=1)
-    return out.logits[:, -1].float(), [l.keys for l in cache.layers], [l.values for l in cache.layers]
-
-
-def _err(a, ref):
-    d = (a.float() - ref.float()).abs()
-    return float(d.max()), float(d.pow(2).mean().sqrt())
-
-
 def _cost(name, llm, B, L, n_new):
     """Figures of one model: error ratios int8 engine / HF fp16 against the fp32 model, and the trajectories against the fp16 ENGINE
     on the same (unquantised) weights."""
     d8, d16 = _HipDecoder(llm, B, weights="int8"), _HipDecoder(llm, B)
     try:
-        embs = _embeds(llm, B, L, seed=5)
+        embs = lu.embeds(llm, B, L, seed=5)
         q = _run(d8, llm, embs, n_new)
         f = _run(d16, llm, embs, n_new)
-        hf, hk, hv = _model_prefill(llm, embs)
+        hf, hk, hv = lu.model_prefill(llm, embs)
         llm32 = copy.deepcopy(llm).float()
-        ref, rk, rv = _model_prefill(llm32, embs.float())
+        ref, rk, rv = lu.model_prefill(llm32, embs.float())
         del llm32
-        figures = {"logits": _err(q[0], ref) + _err(hf, ref)}
+        figures = {"logits": lu.err(q[0], ref) + lu.err(hf, ref)}
         for l in range(len(hk)):
-            figures[f"k{l}"] = _err(q[3][l][:, :, :L], rk[l]) + _err(hk[l], rk[l])
-            figures[f"v{l}"] = _err(q[4][l][:, :, :L], rv[l]) + _err(hv[l], rv[l])
+            figures[f"k{l}"] = lu.err(q[3][l][:, :, :L], rk[l]) + lu.err(hk[l], rk[l])
+            figures[f"v{l}"] = lu.err(q[4][l][:, :, :L], rv[l]) + lu.err(hv[l], rv[l])
         # step 0 of the greedy loop reads -inf in the EOS column (min_new = 1): every later step's logits must be finite
         finite = all(bool(torch.isfinite(t).all()) for t in (q[0], q[2][:, 1:], f[0], hf, ref, q[3][0][:, :, :L], q[4][0][:, :, :L]))
         d_first = float((q[0] - f[0]).abs().max())

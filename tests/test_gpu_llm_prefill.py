@@ -24,36 +24,16 @@ from certifiedgpt_amd.minigpt4 import (MiniGPT4Classifier, WordHashTokenizer, _H
                                        hip_decode_unsupported, prepare_texts)
 from oracle import model_oracle as mo, smooth_oracle as so
 from gpu_util import DEV, make_classifier
+import llm_util as lu
+from llm_util import K_SENTINEL, V_SENTINEL, PROMPT
 
 pytestmark = pytest.mark.gpu
-
-PAD, BOS, EOS = 0, 1, 2
-PROMPT = prepare_texts(["<Img><ImageHere></Img> [vqa] what is shown in the picture"])[0]
-K_SENTINEL, V_SENTINEL = 77.0, -55.0
-
-
-def _decoder(hidden, heads, mlp, vocab, layers=2):
-    """A frozen random-init fp16 LlamaForCausalLM on the device (no checkpoint is in the container; nothing is downloaded)."""
-    from transformers import LlamaConfig, LlamaForCausalLM
-    lcfg = LlamaConfig(vocab_size=vocab, hidden_size=hidden, intermediate_size=mlp, num_hidden_layers=layers, num_attention_heads=heads,
-                       num_key_value_heads=heads, max_position_embeddings=2048, pad_token_id=PAD, bos_token_id=BOS, eos_token_id=EOS)
-    torch.manual_seed(0)
-    prev = torch.get_default_dtype()
-    torch.set_default_dtype(torch.float16)
-    try:
-        with torch.device(DEV):
-            llm = LlamaForCausalLM(lcfg).eval()
-    finally:
-        torch.set_default_dtype(prev)
-    for prm in llm.parameters():
-        prm.requires_grad = False
-    return llm
 
 
 @pytest.fixture(scope="module")
 def small():
     """hidden 512 = 4 heads x 128, MLP 1408, vocabulary 320, 2 layers."""
-    llm = _decoder(512, 4, 1408, 320)
+    llm = lu.llama_decoder(512, 4, 1408, 320)
     assert hip_decode_unsupported(llm, 200) == []
     dec = _HipDecoder(llm, 200)
     llm32 = copy.deepcopy(llm).float()
@@ -64,7 +44,7 @@ def small():
 @pytest.fixture(scope="module")
 def vicuna():
     """Vicuna-7B's widths (hidden 4096, 32 heads, MLP 11008, vocabulary 32000) with 2 random-init layers."""
-    llm = _decoder(4096, 32, 11008, 32000)
+    llm = lu.llama_decoder(4096, 32, 11008, 32000)
     dec = _HipDecoder(llm, 200)
     llm32 = copy.deepcopy(llm).float()
     yield llm, dec, llm32
@@ -73,57 +53,28 @@ def vicuna():
     torch.cuda.empty_cache()
 
 
-def _embeds(llm, B, L, seed):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    return llm.get_input_embeddings()(torch.randint(3, llm.config.vocab_size, (B, L), generator=g).to(DEV)).contiguous()
-
-
-def _model_prefill(model, embs):
-    """(last-position logits fp32, per-layer keys, per-layer values) of the model's own forward."""
-    from transformers import DynamicCache
-    L = embs.shape[1]
-    cache = DynamicCache(config=model.config)
-    with torch.no_grad():
-        out = model(inputs_embeds=embs, position_ids=torch.arange(L, device=DEV)[None], past_key_values=cache, use_cache=True,
-                    logits_to_keep=1)
-    return out.logits[:, -1].float(), [l.keys for l in cache.layers], [l.values for l in cache.layers]
-
-
-def _sentinel_buffers(llm, B, length):
-    cfg = llm.config
-    shape = (B, cfg.num_attention_heads, length, 128)
-    kb = [torch.full(shape, K_SENTINEL, dtype=torch.float16, device=DEV) for _ in range(cfg.num_hidden_layers)]
-    vb = [torch.full(shape, V_SENTINEL, dtype=torch.float16, device=DEV) for _ in range(cfg.num_hidden_layers)]
-    return kb, vb
-
-
 def _lib_prefill(llm, dec, embs, extra=3):
     B, L, _ = embs.shape
-    kb, vb = _sentinel_buffers(llm, B, L + extra)
+    kb, vb = lu.sentinel_cache(llm.config.num_hidden_layers, llm.config.num_attention_heads, B, L + extra)
     logits = dec.prefill(embs, kb, vb)
     torch.cuda.synchronize()
     return logits, kb, vb
 
 
-def _err(a, ref):
-    d = (a.float() - ref.float()).abs()
-    return float(d.max()), float(d.pow(2).mean().sqrt())
-
-
 def _check_against_hf(name, llm, dec, llm32, B, L, seed=3):
-    embs = _embeds(llm, B, L, seed)
+    embs = lu.embeds(llm, B, L, seed)
     lib, kb, vb = _lib_prefill(llm, dec, embs)
-    hf, hk, hv = _model_prefill(llm, embs)
-    ref, rk, rv = _model_prefill(llm32, embs.float())
+    hf, hk, hv = lu.model_prefill(llm, embs)
+    ref, rk, rv = lu.model_prefill(llm32, embs.float())
     assert bool(torch.isfinite(lib).all()) and bool(torch.isfinite(hf).all()) and bool(torch.isfinite(ref).all())
-    figures = {"logits": _err(lib, ref) + _err(hf, ref)}
+    figures = {"logits": lu.err(lib, ref) + lu.err(hf, ref)}
     layer0 = {}
     for l in range(len(kb)):
         for nm, mine, theirs, exact, sentinel in (("k", kb[l], hk[l], rk[l], K_SENTINEL), ("v", vb[l], hv[l], rv[l], V_SENTINEL)):
             new = mine[:, :, :L]
             assert bool(torch.isfinite(new).all())
             assert bool((mine[:, :, L:] == sentinel).all())            # no cache row outside 0 .. L-1 is written
-            figures[f"{nm}{l}"] = _err(new, exact) + _err(theirs, exact)
+            figures[f"{nm}{l}"] = lu.err(new, exact) + lu.err(theirs, exact)
             if l == 0:
                 want = theirs.float()
                 ulp = want.abs().amax(dim=-1, keepdim=True).clamp_min(2.0 ** -14).log2().floor().sub(10).exp2()
@@ -161,11 +112,11 @@ def test_prefill_error_is_within_hfs_own_fp16_error_vicuna_width(vicuna, B, L):
 def test_cache_rows_outside_the_prompt_are_bit_unchanged(small):
     llm, dec, _ = small
     B, L, extra = 37, 21, 20
-    kb, vb = _sentinel_buffers(llm, B, L + extra)
+    kb, vb = lu.sentinel_cache(llm.config.num_hidden_layers, llm.config.num_attention_heads, B, L + extra)
     for i, t in enumerate(kb + vb):                                    # a pattern of its own per buffer, not one constant
         t[:, :, L:] = torch.arange(extra * 128, device=DEV, dtype=torch.float16).view(extra, 128) * 0.25 + i
     before = [t.clone() for t in kb + vb]
-    dec.prefill(_embeds(llm, B, L, 4), kb, vb)
+    dec.prefill(lu.embeds(llm, B, L, 4), kb, vb)
     torch.cuda.synchronize()
     for t, was in zip(kb + vb, before):
         assert torch.equal(t[:, :, L:], was[:, :, L:])
@@ -177,9 +128,9 @@ def test_cache_rows_outside_the_prompt_are_bit_unchanged(small):
 def test_positions_at_or_after_p_do_not_reach_cache_rows_before_p(small, L, p):
     llm, dec, _ = small
     B = 9
-    embs = _embeds(llm, B, L, 6)
+    embs = lu.embeds(llm, B, L, 6)
     other = embs.clone()
-    other[:, p:] = _embeds(llm, B, L, 7)[:, p:]
+    other[:, p:] = lu.embeds(llm, B, L, 7)[:, p:]
     _, k1, v1 = _lib_prefill(llm, dec, embs)
     _, k2, v2 = _lib_prefill(llm, dec, other)
     for a, b in zip(k1 + v1, k2 + v2):
@@ -192,7 +143,7 @@ def test_positions_at_or_after_p_do_not_reach_cache_rows_before_p(small, L, p):
 def test_prefills_are_bit_identical_and_rows_do_not_depend_on_the_batch(which, request):
     llm, dec, _ = request.getfixturevalue(which)
     B, L = 200, 44
-    embs = _embeds(llm, B, L, 5)
+    embs = lu.embeds(llm, B, L, 5)
     first = _lib_prefill(llm, dec, embs)
     again = _lib_prefill(llm, dec, embs)
     assert torch.equal(first[0], again[0])
@@ -202,7 +153,7 @@ def test_prefills_are_bit_identical_and_rows_do_not_depend_on_the_batch(which, r
         assert torch.equal(lg, first[0][lo:hi])
         assert all(torch.equal(a, b[lo:hi]) for a, b in zip(kb + vb, first[1] + first[2]))
     # captured into a graph: two replays give the eager call's logits and cache, bit for bit
-    kb, vb = _sentinel_buffers(llm, B, L + 3)
+    kb, vb = lu.sentinel_cache(llm.config.num_hidden_layers, llm.config.num_attention_heads, B, L + 3)
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
@@ -306,7 +257,7 @@ def configs2(vicuna):
                            output_scores=True, return_dict_in_generate=True, **hf.hf_generate_kwargs())
     hf_tokens, hf_scores = out.sequences, torch.stack(out.scores, dim=1).float()
     lib_first, _, _ = _lib_prefill(llm, dec, embs)
-    hf_first, _, _ = _model_prefill(llm, embs)
+    hf_first, _, _ = lu.model_prefill(llm, embs)
     d_first = float((lib_first - hf_first).abs().max())
     eps = 2.0 * d_first
     yield {"enc": enc, "cfg": cfg, "tok": tok, "x": x, "emb": emb, "embs": embs, "hf_tokens": hf_tokens, "hf_scores": hf_scores,
@@ -406,9 +357,9 @@ def test_a_graph_captured_before_the_workspace_grew_replays_bit_for_bit(small):
     dec = _HipDecoder(llm, 200)                                        # a handle of its own: nothing is reserved yet
     try:
         def captured(B, L, seed):
-            embs = _embeds(llm, B, L, seed)
+            embs = lu.embeds(llm, B, L, seed)
             eager = _lib_prefill(llm, dec, embs)                       # reserves (and may grow) outside the capture
-            kb, vb = _sentinel_buffers(llm, B, L + 3)
+            kb, vb = lu.sentinel_cache(llm.config.num_hidden_layers, llm.config.num_attention_heads, B, L + 3)
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):

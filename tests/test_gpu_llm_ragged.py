@@ -22,38 +22,20 @@ from certifiedgpt_amd.minigpt4 import (MiniGPT4Classifier, WordHashTokenizer, _H
                                        left_pad_embeds, prepare_texts)
 from oracle import model_oracle as mo
 from gpu_util import DEV, make_classifier
+import llm_util as lu
+from llm_util import PAD, EOS, K_SENTINEL, V_SENTINEL
 
 pytestmark = pytest.mark.gpu
 
-PAD, BOS, EOS = 0, 1, 2
-K_SENTINEL, V_SENTINEL = 77.0, -55.0
 QUESTIONS = ["what is shown", "what is shown in the picture", "is there a dog or a cat in this picture",
              "how many people are there in the picture and what are they doing now"]
 PROMPTS = prepare_texts(["<Img><ImageHere></Img> [vqa] " + q for q in QUESTIONS])
 
 
-def _decoder(hidden, heads, mlp, vocab, layers=2):
-    """A frozen random-init fp16 LlamaForCausalLM on the device (no checkpoint is in the container; nothing is downloaded)."""
-    from transformers import LlamaConfig, LlamaForCausalLM
-    lcfg = LlamaConfig(vocab_size=vocab, hidden_size=hidden, intermediate_size=mlp, num_hidden_layers=layers, num_attention_heads=heads,
-                       num_key_value_heads=heads, max_position_embeddings=2048, pad_token_id=PAD, bos_token_id=BOS, eos_token_id=EOS)
-    torch.manual_seed(0)
-    prev = torch.get_default_dtype()
-    torch.set_default_dtype(torch.float16)
-    try:
-        with torch.device(DEV):
-            llm = LlamaForCausalLM(lcfg).eval()
-    finally:
-        torch.set_default_dtype(prev)
-    for prm in llm.parameters():
-        prm.requires_grad = False
-    return llm
-
-
 @pytest.fixture(scope="module")
 def small():
     """hidden 512 = 4 heads x 128, MLP 1408, vocabulary 320, 2 layers."""
-    llm = _decoder(512, 4, 1408, 320)
+    llm = lu.llama_decoder(512, 4, 1408, 320)
     assert hip_decode_unsupported(llm, 200) == []
     dec = _HipDecoder(llm, 200)
     llm32 = copy.deepcopy(llm).float()
@@ -64,21 +46,13 @@ def small():
 @pytest.fixture(scope="module")
 def vicuna():
     """Vicuna-7B's widths (hidden 4096, 32 heads, MLP 11008, vocabulary 32000) with 2 random-init layers."""
-    llm = _decoder(4096, 32, 11008, 32000)
+    llm = lu.llama_decoder(4096, 32, 11008, 32000)
     dec = _HipDecoder(llm, 200)
     llm32 = copy.deepcopy(llm).float()
     yield llm, dec, llm32
     dec.close()
     del llm, llm32
     torch.cuda.empty_cache()
-
-
-def _sentinel_buffers(llm, B, length):
-    cfg = llm.config
-    shape = (B, cfg.num_attention_heads, length, 128)
-    kb = [torch.full(shape, K_SENTINEL, dtype=torch.float16, device=DEV) for _ in range(cfg.num_hidden_layers)]
-    vb = [torch.full(shape, V_SENTINEL, dtype=torch.float16, device=DEV) for _ in range(cfg.num_hidden_layers)]
-    return kb, vb
 
 
 def _padded_batch(llm, L, lens, seed):
@@ -95,7 +69,7 @@ def _padded_batch(llm, L, lens, seed):
 def _run(llm, dec, embs, prompt_len, n_new, starts=None, extra=2):
     """prefill + greedy with the logits of every step; buffers hold `extra` rows past the last appended one."""
     B = embs.shape[0]
-    kb, vb = _sentinel_buffers(llm, B, prompt_len + n_new - 1 + extra)
+    kb, vb = lu.sentinel_cache(llm.config.num_hidden_layers, llm.config.num_attention_heads, B, prompt_len + n_new - 1 + extra)
     first = dec.prefill(embs, kb, vb, starts=starts)
     tokens, steps = dec.greedy(first, prompt_len, n_new, 1, [EOS], PAD, kb, vb, return_logits=True, starts=starts)
     torch.cuda.synchronize()
@@ -177,7 +151,7 @@ def test_starts_outside_the_prompt_are_clamped_and_replays_read_the_current_star
     assert all(torch.equal(a, b) for a, b in zip(got[3] + got[4], want[3] + want[4]))
     # one capture, two contents of the same starts tensor
     static = clamped.clone()
-    kb, vb = _sentinel_buffers(llm, B, L + n_new)
+    kb, vb = lu.sentinel_cache(llm.config.num_hidden_layers, llm.config.num_attention_heads, B, L + n_new)
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
@@ -205,21 +179,16 @@ def _model_prefill_padded(model, embs, mask):
     return out.logits[:, -1].float(), [l.keys for l in cache.layers], [l.values for l in cache.layers]
 
 
-def _err(a, ref):
-    d = (a.float() - ref.float()).abs()
-    return float(d.max()), float(d.pow(2).mean().sqrt())
-
-
 def _check_against_hf(name, llm, dec, llm32, L, lens, seed):
     embs, starts, mask = _padded_batch(llm, L, lens, seed)
     B = len(lens)
-    kb, vb = _sentinel_buffers(llm, B, L + 3)
+    kb, vb = lu.sentinel_cache(llm.config.num_hidden_layers, llm.config.num_attention_heads, B, L + 3)
     lib = dec.prefill(embs, kb, vb, starts=starts)
     torch.cuda.synchronize()
     hf, hk, hv = _model_prefill_padded(llm, embs, mask)
     ref, rk, rv = _model_prefill_padded(llm32, embs.float(), mask)
     assert bool(torch.isfinite(lib).all()) and bool(torch.isfinite(hf).all()) and bool(torch.isfinite(ref).all())
-    figures = {"logits": _err(lib, ref) + _err(hf, ref)}
+    figures = {"logits": lu.err(lib, ref) + lu.err(hf, ref)}
 
     def real(t):                                                       # [B, heads, L, 128] -> the real positions' rows
         return t[:, :, :L].permute(0, 2, 1, 3)[mask]
@@ -227,7 +196,7 @@ def _check_against_hf(name, llm, dec, llm32, L, lens, seed):
     for l in range(len(kb)):
         for nm, mine, theirs, exact in (("k", kb[l], hk[l], rk[l]), ("v", vb[l], hv[l], rv[l])):
             assert bool(torch.isfinite(real(mine)).all())
-            figures[f"{nm}{l}"] = _err(real(mine), real(exact)) + _err(real(theirs), real(exact))
+            figures[f"{nm}{l}"] = lu.err(real(mine), real(exact)) + lu.err(real(theirs), real(exact))
     print(f"[ragged prefill {name}, {B} rows padded to {L}, lengths {min(lens)} .. {max(lens)}] (max, rms) error ratio library / HF "
           "against the fp32 model on real positions: " + ", ".join(f"{k} ({v[0] / v[2]:.3f}, {v[1] / v[3]:.3f})" for k, v in figures.items())
           + f"; max |logit lib - hf| {float((lib - hf).abs().max()):.4g} at max |logit| {float(hf.abs().max()):.4g}", flush=True)
@@ -288,7 +257,7 @@ def test_classifier_decodes_distinct_texts_natively_and_follows_hf_generate(vicu
                                **hf.hf_generate_kwargs())
             hf_tokens, hf_scores = out.sequences, torch.stack(out.scores, dim=1).float()
             hf_first, _, _ = _model_prefill_padded(llm, embs, mask.bool())
-            kb, vb = _sentinel_buffers(llm, B, embs.shape[1] + 1)
+            kb, vb = lu.sentinel_cache(llm.config.num_hidden_layers, llm.config.num_attention_heads, B, embs.shape[1] + 1)
             lib_first = dec.prefill(embs.contiguous(), kb, vb, starts=starts)
             del kb, vb
             tokens = hip._generate_graph(embs, starts)

@@ -1,6 +1,6 @@
 """Sampled decoding on the native LLaMA engine (sample="hip"; cgpt_llm_sample*, csrc/llm_sample.hip).
 
-The oracle is `sample_token_law` / `sample_uniform` (certifiedgpt_amd/minigpt4.py, pinned to transformers' own processors and to
+The oracle is `sample_token_law` / `sample_uniform` (certifiedgpt_amd/llm_laws.py, pinned to transformers' own processors and to
 oracle.philox on the CPU by tests/test_llm_sample_cpu.py):
   * the uniforms are bit-equal to `sample_uniform` (24 bits, exact in fp32);
   * cases whose every decision has a margin >= 0.02 give the law's token exactly;
@@ -25,10 +25,11 @@ import torch
 from certifiedgpt_amd import _lib
 from certifiedgpt_amd.agents.label_adapter import AnswerLabelMap
 from certifiedgpt_amd.minigpt4 import (MiniGPT4Classifier, WordHashTokenizer, _HipDecoder, apply_stop_sequences, expand_kv_state_dict,
-                                       int8_state_dict, prepare_texts, sample_token_law, sample_uniform, stop_finish_columns)
+                                       int8_state_dict, sample_token_law, sample_uniform, stop_finish_columns)
 from gpu_util import DEV, make_classifier
+import llm_util as lu
+from llm_util import PROMPT
 from oracle import model_oracle as mo
-from test_gpu_llm_decode import _small_decoder
 
 pytestmark = pytest.mark.gpu
 
@@ -38,7 +39,6 @@ CHAT_KW = dict(do_sample=True, top_p=0.9, repetition_penalty=1.05, temperature=1
 MASS_ERR = 5e-8                              # measured on an MI355X over test 3's inputs: 4.9e-8, at V 32000 / sigma 2 / "chat"
 EPS = 4 * MASS_ERR
 SEED = 0x9E3779B97F4A7C15                    # a seed with both key words in use
-PROMPT = prepare_texts(["<Img><ImageHere></Img> [vqa] what is shown in the picture"])[0]
 
 
 def _i64(seed):
@@ -286,11 +286,6 @@ def test_entry_refuses_bad_settings_before_any_launch():
 EOS_ID, PAD_ID = 2, 0
 
 
-def _ids(llm, B, L, seed):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    return torch.randint(3, llm.config.vocab_size, (B, L), generator=g).to(DEV)
-
-
 def _buffers(dec, B, length):
     shape = (B, dec.kv_heads, length, 128)
     return ([torch.zeros(shape, dtype=torch.float16, device=DEV) for _ in range(dec.layers)],
@@ -308,7 +303,7 @@ def _sample(dec, embs, n, ids, seed, settings=CHAT, eos=(EOS_ID,), min_new=1, st
 
 @pytest.fixture(scope="module")
 def small():
-    llm = _small_decoder()
+    llm = lu.small_decoder()
     dec = _HipDecoder(llm, 200)
     yield llm, dec
     dec.close()
@@ -317,7 +312,7 @@ def small():
 def test_every_token_passes_the_margin_rule_and_replays_are_bit_identical(small):
     llm, dec = small
     B, L, n = 37, 12, 8
-    embs = llm.get_input_embeddings()(_ids(llm, B, L, 4)).contiguous()
+    embs = llm.get_input_embeddings()(lu.ids(llm, B, L, 4)).contiguous()
     ids = torch.arange(1000, 1000 + B, dtype=torch.int64)
     T, logits = _sample(dec, embs, n, ids, SEED, return_logits=True)
     T2 = _sample(dec, embs, n, ids, SEED)
@@ -365,7 +360,7 @@ def test_every_token_passes_the_margin_rule_and_replays_are_bit_identical(small)
 def test_partition_invariance(small):
     llm, dec = small
     B, L, n = 200, 12, 8
-    embs = llm.get_input_embeddings()(_ids(llm, B, L, 6)).contiguous()
+    embs = llm.get_input_embeddings()(lu.ids(llm, B, L, 6)).contiguous()
     ids = torch.arange(B, dtype=torch.int64)
     whole = _sample(dec, embs, n, ids, 42)
     parts = torch.cat([_sample(dec, embs[:128], n, ids[:128], 42), _sample(dec, embs[128:], n, ids[128:], 42)])
@@ -376,7 +371,7 @@ def test_partition_invariance(small):
 def test_early_stop_and_stop_sequences_compose(small):
     llm, dec = small
     B, L, n = 37, 12, 10
-    embs = llm.get_input_embeddings()(_ids(llm, B, L, 7)).contiguous()
+    embs = llm.get_input_embeddings()(lu.ids(llm, B, L, 7)).contiguous()
     ids = torch.arange(B, dtype=torch.int64)
     T = _sample(dec, embs, n, ids, 9, eos=())
     assert dec.live_steps() == n - 1
@@ -398,13 +393,13 @@ def test_early_stop_and_stop_sequences_compose(small):
 
 
 def test_live_steps_on_a_zeroed_lm_head():
-    llm = _small_decoder()
+    llm = lu.small_decoder()
     with torch.no_grad():
         llm.lm_head.weight.zero_()
     dec = _HipDecoder(llm, 8, early_stop=True)
     try:
         B, L, n, V = 4, 12, 10, 320
-        embs = llm.get_input_embeddings()(_ids(llm, B, L, 8)).contiguous()
+        embs = llm.get_input_embeddings()(lu.ids(llm, B, L, 8)).contiguous()
         ids = torch.arange(B, dtype=torch.int64)
         # every logit is 0: all 320 columns tie, both cuts keep the whole group, and the token is floor(320 u) up to the CDF's rounding
         T = _sample(dec, embs, n, ids, 5, eos=()).cpu()
@@ -425,7 +420,7 @@ def test_a_padded_row_equals_the_row_alone(small):
     llm, dec = small
     B, L, n = 5, 12, 8
     starts = torch.tensor([0, 11, 5, 1, 7], dtype=torch.int32)
-    embs = llm.get_input_embeddings()(_ids(llm, B, L, 10)).clone()
+    embs = llm.get_input_embeddings()(lu.ids(llm, B, L, 10)).clone()
     for b, s in enumerate(starts.tolist()):
         embs[b, :s] = 0
     ids = torch.tensor([3, 2 ** 32 + 1, 9, 0, 12345], dtype=torch.int64)
@@ -436,24 +431,23 @@ def test_a_padded_row_equals_the_row_alone(small):
 
 
 def test_int8_and_grouped_twins():
-    llm = _small_decoder()
+    llm = lu.small_decoder()
     B, L, n = 8, 12, 6
     ids = torch.arange(50, 50 + B, dtype=torch.int64)
     twin = copy.deepcopy(llm)
     twin.load_state_dict(int8_state_dict(llm, device="cpu"), strict=True)
     a, b = _HipDecoder(llm, 8, weights="int8"), _HipDecoder(twin, 8)
     try:
-        embs = llm.get_input_embeddings()(_ids(llm, B, L, 12)).contiguous()
+        embs = llm.get_input_embeddings()(lu.ids(llm, B, L, 12)).contiguous()
         assert torch.equal(_sample(a, embs, n, ids, 3), _sample(b, embs, n, ids, 3))
     finally:
         a.close()
         b.close()
-    from test_gpu_llm_gqa import _decoder as gqa_decoder
-    grouped = gqa_decoder(512, 4, 2, 1408, 320)
-    expanded = gqa_decoder(512, 4, 4, 1408, 320, sd=expand_kv_state_dict(grouped))
+    grouped = lu.llama_decoder(512, 4, 1408, 320, kv_heads=2)
+    expanded = lu.llama_decoder(512, 4, 1408, 320, kv_heads=4, sd=expand_kv_state_dict(grouped))
     a, b = _HipDecoder(grouped, 8, grouped_kv=True), _HipDecoder(expanded, 8)
     try:
-        embs = grouped.get_input_embeddings()(_ids(grouped, B, L, 13)).contiguous()
+        embs = grouped.get_input_embeddings()(lu.ids(grouped, B, L, 13)).contiguous()
         assert torch.equal(_sample(a, embs, n, ids, 3), _sample(b, embs, n, ids, 3))
     finally:
         a.close()

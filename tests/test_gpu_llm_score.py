@@ -14,40 +14,21 @@ import torch
 
 import certifiedgpt_amd as cg
 from certifiedgpt_amd.agents.label_adapter import AnswerLabelMap
-from certifiedgpt_amd.minigpt4 import MiniGPT4Classifier, WordHashTokenizer, _HipDecoder, hip_decode_unsupported, int8_state_dict, prepare_texts
+from certifiedgpt_amd.minigpt4 import MiniGPT4Classifier, WordHashTokenizer, _HipDecoder, hip_decode_unsupported, int8_state_dict
 from oracle import model_oracle as mo
 from gpu_util import DEV, make_classifier
+import llm_util as lu
+from llm_util import PAD, EOS, K_SENTINEL, V_SENTINEL, PROMPT
 
 pytestmark = pytest.mark.gpu
 
-PAD, BOS, EOS = 0, 1, 2
 EPS = 0.1
-PROMPT = prepare_texts(["<Img><ImageHere></Img> [vqa] what is shown in the picture"])[0]
-K_SENTINEL, V_SENTINEL = 77.0, -55.0
-
-
-def _decoder(hidden, heads, mlp, vocab, layers=2):
-    """A frozen random-init fp16 LlamaForCausalLM on the device (no checkpoint is in the container; nothing is downloaded)."""
-    from transformers import LlamaConfig, LlamaForCausalLM
-    lcfg = LlamaConfig(vocab_size=vocab, hidden_size=hidden, intermediate_size=mlp, num_hidden_layers=layers, num_attention_heads=heads,
-                       num_key_value_heads=heads, max_position_embeddings=2048, pad_token_id=PAD, bos_token_id=BOS, eos_token_id=EOS)
-    torch.manual_seed(0)
-    prev = torch.get_default_dtype()
-    torch.set_default_dtype(torch.float16)
-    try:
-        with torch.device(DEV):
-            llm = LlamaForCausalLM(lcfg).eval()
-    finally:
-        torch.set_default_dtype(prev)
-    for prm in llm.parameters():
-        prm.requires_grad = False
-    return llm
 
 
 @pytest.fixture(scope="module")
 def small():
     """hidden 512 = 4 heads x 128, MLP 1408, vocabulary 320, 2 layers."""
-    llm = _decoder(512, 4, 1408, 320)
+    llm = lu.llama_decoder(512, 4, 1408, 320)
     assert hip_decode_unsupported(llm, 200) == []
     dec = _HipDecoder(llm, 200)
     llm32 = copy.deepcopy(llm).float()
@@ -58,18 +39,13 @@ def small():
 @pytest.fixture(scope="module")
 def vicuna():
     """Vicuna-7B's widths (hidden 4096, 32 heads, MLP 11008, vocabulary 32000) with 2 random-init layers."""
-    llm = _decoder(4096, 32, 11008, 32000)
+    llm = lu.llama_decoder(4096, 32, 11008, 32000)
     dec = _HipDecoder(llm, 200)
     llm32 = copy.deepcopy(llm).float()
     yield llm, dec, llm32
     dec.close()
     del llm, llm32
     torch.cuda.empty_cache()
-
-
-def _embeds(llm, B, L, seed):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    return llm.get_input_embeddings()(torch.randint(3, llm.config.vocab_size, (B, L), generator=g).to(DEV)).contiguous()
 
 
 def _candidates(vocab, lengths, seed):
@@ -103,17 +79,9 @@ def _model_sums(model, embs, cands, chunk=50):
     return out
 
 
-def _buffers(llm, B, length):
-    cfg = llm.config
-    shape = (B, cfg.num_attention_heads, length, 128)
-    kb = [torch.full(shape, K_SENTINEL, dtype=torch.float16, device=DEV) for _ in range(cfg.num_hidden_layers)]
-    vb = [torch.full(shape, V_SENTINEL, dtype=torch.float16, device=DEV) for _ in range(cfg.num_hidden_layers)]
-    return kb, vb
-
-
 def _lib_sums(llm, dec, embs, cands, extra=3, keep=False):
     B, L, _ = embs.shape
-    kb, vb = _buffers(llm, B, L + extra)
+    kb, vb = lu.sentinel_cache(llm.config.num_hidden_layers, llm.config.num_attention_heads, B, L + extra)
     first = dec.prefill(embs, kb, vb)
     table, lens = _table(cands)
     sums = dec.score(first, L, table, lens, EPS, kb, vb)
@@ -121,20 +89,15 @@ def _lib_sums(llm, dec, embs, cands, extra=3, keep=False):
     return (sums, first, kb, vb) if keep else sums
 
 
-def _err(a, ref):
-    d = (a.float() - ref.float()).abs()
-    return float(d.max()), float(d.pow(2).mean().sqrt())
-
-
 def _check_accuracy(name, llm, dec, llm32, B, L, lengths):
-    embs = _embeds(llm, B, L, 3)
+    embs = lu.embeds(llm, B, L, 3)
     cands = _candidates(llm.config.vocab_size, lengths, 17)
     lib = _lib_sums(llm, dec, embs, cands)
     hf = _model_sums(llm, embs, cands)
     ref = _model_sums(llm32, embs.float(), cands)
     assert tuple(lib.shape) == (B, len(lengths))
     assert bool(torch.isfinite(lib).all()) and bool(torch.isfinite(hf).all()) and bool(torch.isfinite(ref).all())
-    (lmax, lrms), (hmax, hrms) = _err(lib, ref), _err(hf, ref)
+    (lmax, lrms), (hmax, hrms) = lu.err(lib, ref), lu.err(hf, ref)
     print(f"[score {name}, {B} rows x {L} positions, candidate lengths {lengths}] (max, rms) error ratio library / HF against the fp32 "
           f"model: ({lmax / hmax:.3f}, {lrms / hrms:.3f}); max e_lib {lmax:.4g}, max e_hf {hmax:.4g}, max |lib - hf| "
           f"{float((lib - hf).abs().max()):.4g} at sums around {float(ref.mean()):.4g}", flush=True)
@@ -162,7 +125,7 @@ def test_score_error_is_within_hfs_own_fp16_error_vicuna_width(vicuna):
 # ------------------------------------------------------------------------------------------ 2. exact properties
 def test_rows_candidates_and_their_order_do_not_change_a_single_bit(small):
     llm, dec, _ = small
-    embs = _embeds(llm, 5, 13, 4)
+    embs = lu.embeds(llm, 5, 13, 4)
     cands = _candidates(320, (3, 1, 5, 2), 18)
     full = _lib_sums(llm, dec, embs, cands)
     assert torch.equal(full, _lib_sums(llm, dec, embs, cands))         # scoring twice
@@ -179,7 +142,7 @@ def test_a_candidate_is_scored_through_its_own_earlier_tokens_only(small):
     """Causality inside a tail: changing token j changes the terms from j on (the sum), never what tokens before it see -- a
     candidate that is a prefix of another one scores the prefix's terms."""
     llm, dec, _ = small
-    embs = _embeds(llm, 5, 13, 5)
+    embs = lu.embeds(llm, 5, 13, 5)
     long_ = _candidates(320, (5,), 19)[0]
     other = long_.clone()
     other[3] = (other[3] + 7) % 317 + 3
@@ -191,7 +154,7 @@ def test_a_candidate_is_scored_through_its_own_earlier_tokens_only(small):
 def test_scoring_writes_no_cache_row_and_greedy_runs_on_afterwards(small):
     llm, dec, _ = small
     B, L, new = 9, 21, 5
-    embs = _embeds(llm, B, L, 6)
+    embs = lu.embeds(llm, B, L, 6)
     cands = _candidates(320, (2, 4, 1), 20)
     sums, first, kb, vb = _lib_sums(llm, dec, embs, cands, extra=new, keep=True)
     for t, sentinel in zip(kb + vb, [K_SENTINEL] * len(kb) + [V_SENTINEL] * len(vb)):
@@ -203,7 +166,7 @@ def test_scoring_writes_no_cache_row_and_greedy_runs_on_afterwards(small):
     assert torch.equal(again, sums)
     assert all(torch.equal(t, was) for t, was in zip(kb + vb, before))         # bitwise unchanged, prompt rows included
     scored = dec.greedy(first, L, new, 1, [EOS], PAD, kb, vb)
-    kb2, vb2 = _buffers(llm, B, L + new)
+    kb2, vb2 = lu.sentinel_cache(llm.config.num_hidden_layers, llm.config.num_attention_heads, B, L + new)
     plain = dec.greedy(dec.prefill(embs, kb2, vb2), L, new, 1, [EOS], PAD, kb2, vb2)
     torch.cuda.synchronize()
     assert torch.equal(scored, plain)
@@ -223,7 +186,7 @@ def test_the_top_candidate_is_the_fp32_models_on_decisive_rows(small):
     llm, dec, llm32 = small
     B, L = 40, 21
     g = torch.Generator(device="cpu").manual_seed(8)
-    base = _embeds(llm, 1, L, 7)
+    base = lu.embeds(llm, 1, L, 7)
     embs = (base.float() + 0.004 * torch.randn(B, L, 512, generator=g).to(DEV)).to(torch.float16).contiguous()
     with torch.no_grad():
         seq, own = base.float(), []
@@ -252,7 +215,7 @@ def test_int8_scoring_is_bit_for_bit_the_fp16_engine_on_the_dequantised_weights(
     twin.load_state_dict(int8_state_dict(llm))
     dec8, dec16 = _HipDecoder(llm, 200, weights="int8"), _HipDecoder(twin, 200)
     try:
-        embs = _embeds(llm, 37, 13, 9)
+        embs = lu.embeds(llm, 37, 13, 9)
         cands = _candidates(320, (1, 2, 5), 22)
         a, b = _lib_sums(llm, dec8, embs, cands), _lib_sums(twin, dec16, embs, cands)
         assert torch.equal(a, b) and bool(torch.isfinite(a).all())
@@ -268,8 +231,8 @@ def test_score_entries_refuse_before_any_launch(small):
     L = cg.lib()
     INVALID = 1
     B, Lp = 4, 8
-    embs = _embeds(llm, B, Lp, 10)
-    kb, vb = _buffers(llm, B, Lp)
+    embs = lu.embeds(llm, B, Lp, 10)
+    kb, vb = lu.sentinel_cache(llm.config.num_hidden_layers, llm.config.num_attention_heads, B, Lp)
     first = dec.prefill(embs, kb, vb)
     table, lens = _table(_candidates(320, (2, 3), 23))
     out = torch.full((B, 2), 3.0, device=DEV)

@@ -19,12 +19,12 @@ from certifiedgpt_amd.minigpt4 import (MiniGPT4Classifier, WordHashTokenizer, _H
                                        pack_row_candidates, prepare_texts)
 from oracle import model_oracle as mo
 from gpu_util import DEV, make_classifier
+import llm_util as lu
+from llm_util import K_SENTINEL, V_SENTINEL
 
 pytestmark = pytest.mark.gpu
 
-PAD, BOS, EOS = 0, 1, 2
 EPS = 0.1
-K_SENTINEL, V_SENTINEL = 77.0, -55.0
 L_PAD = 70
 STARTS = (0, 5, 6, 57, 69)
 # LENS[b][c]: row 0 at full length everywhere (every T_c is reached), row 1 with one token of the 5-token candidate and T_c - 1 = 2 of
@@ -34,28 +34,10 @@ GEOMETRY = (3, 1, 5, 2)
 INVALID, STATE = 1, 5
 
 
-def _decoder(hidden, heads, kv_heads, mlp, vocab, layers=2):
-    """A frozen random-init fp16 LlamaForCausalLM on the device (no checkpoint is in the container; nothing is downloaded)."""
-    from transformers import LlamaConfig, LlamaForCausalLM
-    lcfg = LlamaConfig(vocab_size=vocab, hidden_size=hidden, intermediate_size=mlp, num_hidden_layers=layers, num_attention_heads=heads,
-                       num_key_value_heads=kv_heads, max_position_embeddings=2048, pad_token_id=PAD, bos_token_id=BOS, eos_token_id=EOS)
-    torch.manual_seed(0)
-    prev = torch.get_default_dtype()
-    torch.set_default_dtype(torch.float16)
-    try:
-        with torch.device(DEV):
-            llm = LlamaForCausalLM(lcfg).eval()
-    finally:
-        torch.set_default_dtype(prev)
-    for prm in llm.parameters():
-        prm.requires_grad = False
-    return llm
-
-
 @pytest.fixture(scope="module")
 def small():
     """hidden 512 = 4 heads x 128, MLP 1408, vocabulary 320, 2 layers."""
-    llm = _decoder(512, 4, 4, 1408, 320)
+    llm = lu.llama_decoder(512, 4, 1408, 320, kv_heads=4)
     assert hip_decode_unsupported(llm, 200) == []
     dec = _HipDecoder(llm, 200)
     yield llm, dec
@@ -77,16 +59,9 @@ def _row_candidates(vocab, lens, seed):
     return [[torch.randint(3, vocab, (lens[b][c],), generator=g) for b in range(len(lens))] for c in range(len(lens[0]))]
 
 
-def _buffers(dec, B, length):
-    shape = (B, dec.kv_heads, length, 128)
-    kb = [torch.full(shape, K_SENTINEL, dtype=torch.float16, device=DEV) for _ in range(dec.layers)]
-    vb = [torch.full(shape, V_SENTINEL, dtype=torch.float16, device=DEV) for _ in range(dec.layers)]
-    return kb, vb
-
-
 def _ragged_sums(dec, embs, starts, cand, extra=3, keep=False, table=None):
     B, L, _ = embs.shape
-    kb, vb = _buffers(dec, B, L + extra)
+    kb, vb = lu.sentinel_cache(dec.layers, dec.kv_heads, B, L + extra)
     first = dec.prefill(embs, kb, vb, starts=starts)
     packed, lens, T, _ = pack_row_candidates(cand)
     table = (packed if table is None else table).to(DEV)
@@ -100,7 +75,7 @@ def _alone_sums(dec, embs, start, row_cands):
     """The existing plain path on ONE row, unpadded: cgpt_llm_prefill + cgpt_llm_score with the row's own tokens and lengths."""
     row = embs[:, start:].contiguous()
     L = row.shape[1]
-    kb, vb = _buffers(dec, 1, L + 3)
+    kb, vb = lu.sentinel_cache(dec.layers, dec.kv_heads, 1, L + 3)
     first = dec.prefill(row, kb, vb)
     lens = [len(t) for t in row_cands]
     table = torch.zeros((len(lens), max(lens)), dtype=torch.long)
@@ -138,7 +113,7 @@ def test_zero_padding_and_uniform_lengths_equal_the_plain_entry_on_the_batch(sma
     g = torch.Generator(device="cpu").manual_seed(18)
     shared = [torch.randint(3, 320, (n,), generator=g) for n in GEOMETRY]
     ragged = _ragged_sums(dec, embs, sdev, [[t] * B for t in shared])
-    kb, vb = _buffers(dec, B, L_PAD + 3)
+    kb, vb = lu.sentinel_cache(dec.layers, dec.kv_heads, B, L_PAD + 3)
     first = dec.prefill(embs, kb, vb)
     table = torch.zeros((4, max(GEOMETRY)), dtype=torch.long)
     for c, t in enumerate(shared):
@@ -150,7 +125,7 @@ def test_zero_padding_and_uniform_lengths_equal_the_plain_entry_on_the_batch(sma
 
 # ------------------------------------------------------------------------------------------ 3. grouped-query attention
 def test_a_padded_row_is_the_row_alone_on_a_grouped_kv_handle():
-    llm = _decoder(512, 4, 2, 1408, 320)
+    llm = lu.llama_decoder(512, 4, 1408, 320, kv_heads=2)
     assert hip_decode_unsupported(llm, 64, grouped_kv=True) == []
     dec = _HipDecoder(llm, 64, grouped_kv=True)
     try:
@@ -244,7 +219,7 @@ def test_the_ragged_entry_refuses_before_any_launch(small):
     L = cg.lib()
     B, Lp = 4, 8
     embs, sdev = _padded_embeds(llm, (0, 2, 5, 7), Lp, 10)
-    kb, vb = _buffers(dec, B, Lp)
+    kb, vb = lu.sentinel_cache(dec.layers, dec.kv_heads, B, Lp)
     first = dec.prefill(embs, kb, vb, starts=sdev)
     cand = _row_candidates(320, ((2, 3), (1, 3), (2, 1), (2, 2)), 110)
     table, lens, T, _ = pack_row_candidates(cand)

@@ -1,7 +1,7 @@
 """Per-row stop sequences on the native LLaMA engine (cgpt_llm_set_stop_sequences) and through the classifier.
 
 The oracle, everywhere and without any tolerance: greedy rows are independent, so a decode WITH stop sequences equals
-`apply_stop_sequences` (certifiedgpt_amd/minigpt4.py, pinned on the CPU by tests/test_llm_stop_cpu.py) applied to the SAME decode
+`apply_stop_sequences` (certifiedgpt_amd/llm_laws.py, pinned on the CPU by tests/test_llm_stop_cpu.py) applied to the SAME decode
 without them, bit for bit; the step logits of every select up to a row's finishing column are that decode's; and with early stop on,
 cgpt_llm_live_steps = min(F, n - 1) with F = the last row's finishing column, the dead part of the call leaving the cache and the
 step logits untouched (the sentinel pattern of tests/test_gpu_llm_early_stop.py).
@@ -14,32 +14,13 @@ import pytest
 import torch
 
 from certifiedgpt_amd.agents.label_adapter import AnswerLabelMap
-from certifiedgpt_amd.minigpt4 import (MiniGPT4Classifier, WordHashTokenizer, _HipDecoder, apply_stop_sequences, prepare_texts,
+from certifiedgpt_amd.minigpt4 import (MiniGPT4Classifier, WordHashTokenizer, _HipDecoder, apply_stop_sequences,
                                        stop_finish_columns)
 from gpu_util import DEV
-from test_gpu_llm_decode import _prefill, _small_decoder, _vicuna_width_decoder
+import llm_util as lu
+from llm_util import LOGIT_SENTINEL, PROMPT
 
 pytestmark = pytest.mark.gpu
-
-K_SENT, V_SENT, LOGIT_SENT = 77.0, -55.0, 123.0                     # _prefill's cache sentinels; ours for the step logits
-PROMPT = prepare_texts(["<Img><ImageHere></Img> [vqa] what is shown in the picture"])[0]
-
-
-def _zero_head(llm):
-    with torch.no_grad():
-        llm.lm_head.weight.zero_()
-    return llm
-
-
-def _ids(llm, B, L, seed):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    return torch.randint(3, llm.config.vocab_size, (B, L), generator=g).to(DEV)
-
-
-def _sentinel_cache(dec, B, length):
-    shape = (B, dec.heads, length, 128)
-    return ([torch.full(shape, K_SENT, dtype=torch.float16, device=DEV) for _ in range(dec.layers)],
-            [torch.full(shape, V_SENT, dtype=torch.float16, device=DEV) for _ in range(dec.layers)])
 
 
 def _greedy(dec, on, seqs, first, L, n, eos, pad, kb, vb, logits=False, starts=None, tokens_init=None):
@@ -53,7 +34,7 @@ def _greedy(dec, on, seqs, first, L, n, eos, pad, kb, vb, logits=False, starts=N
     try:
         if logits or tokens_init is not None:
             tokens = torch.full((B, n), -7, dtype=torch.int64, device=DEV) if tokens_init is None else tokens_init.clone()
-            buf = torch.full((B, n, V), LOGIT_SENT, dtype=torch.float32, device=DEV) if logits else None
+            buf = torch.full((B, n, V), LOGIT_SENTINEL, dtype=torch.float32, device=DEV) if logits else None
             kp, vp, stride = dec._cache_tables(kb, vb, B, L + n - 1)
             ids = (C.c_int64 * max(1, len(eos)))(*eos)
             st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -74,26 +55,9 @@ def _greedy(dec, on, seqs, first, L, n, eos, pad, kb, vb, logits=False, starts=N
     return tokens, steps, kb, vb, buf
 
 
-def _check_dead_part(L, live, on, off, layers=None):
-    """Cache rows L + live .. keep their sentinel on the `on` run, rows below are the off run's bit for bit (as are the prompt rows,
-    which no step writes); step logits rows 0 .. live are the off run's, later rows keep their sentinel."""
-    _, _, k_on, v_on, lg_on = on
-    _, _, k_off, v_off, lg_off = off
-    for l in (range(len(k_on)) if layers is None else layers):
-        assert bool((k_on[l][:, :, L + live:] == K_SENT).all()) and bool((v_on[l][:, :, L + live:] == V_SENT).all()), (l, live)
-        assert torch.equal(k_on[l][:, :, :L + live], k_off[l][:, :, :L + live]), (l, live)
-        assert torch.equal(v_on[l][:, :, :L + live], v_off[l][:, :, :L + live]), (l, live)
-        n_off = k_off[l].shape[2] - 1                                  # the off run appended every row but the last (n - 1 steps)
-        assert not bool((k_off[l][:, :, L:n_off] == K_SENT).all(dim=-1).any())      # so the sentinel check above says something
-    if lg_on is not None:
-        assert torch.equal(lg_on[:, :live + 1], lg_off[:, :live + 1])
-        assert bool((lg_on[:, live + 1:] == LOGIT_SENT).all())
-        assert not bool((lg_off == LOGIT_SENT).all(dim=-1).any())
-
-
 @pytest.fixture(scope="module")
 def zero_small():
-    llm = _zero_head(_small_decoder())
+    llm = lu.zero_head(lu.small_decoder())
     dec = _HipDecoder(llm, 64)
     yield llm, dec
     dec.close()
@@ -101,7 +65,7 @@ def zero_small():
 
 @pytest.fixture(scope="module")
 def small():
-    llm = _small_decoder()
+    llm = lu.small_decoder()
     dec = _HipDecoder(llm, 64)
     yield llm, dec
     dec.close()
@@ -113,8 +77,8 @@ def natural(small):
     and without EOS ids: computed once, shared, never changed."""
     llm, dec = small
     B, L, n = 37, 12, 12
-    kb, vb = _sentinel_cache(dec, B, L + n)
-    first = dec.prefill(llm.get_input_embeddings()(_ids(llm, B, L, 4)).contiguous(), kb, vb)
+    kb, vb = lu.sentinel_cache(dec.layers, dec.heads, B, L + n)
+    first = dec.prefill(llm.get_input_embeddings()(lu.ids(llm, B, L, 4)).contiguous(), kb, vb)
     plain = _greedy(dec, False, None, first, L, n, [], 5, kb, vb, logits=True)
     assert plain[1] == n - 1
     return dec, first, L, n, kb, vb, plain
@@ -130,7 +94,7 @@ def _natural_seqs(T):
 def test_exact_finishing_step_on_the_synthetic_law(zero_small, k):
     llm, dec = zero_small
     B, L, n, pad = 37, 12, 10, 5
-    first, kb, vb, _ = _prefill(llm, llm.get_input_embeddings()(_ids(llm, B, L, 3)), n)      # the model's own prefill
+    first, kb, vb, _ = lu.prefill(llm, llm.get_input_embeddings()(lu.ids(llm, B, L, 3)), n)      # the model's own prefill
     assert bool((first == 0).all())
     seqs = [[0] * k]
     off = _greedy(dec, False, seqs, first, L, n, [], pad, kb, vb, logits=True)
@@ -141,10 +105,10 @@ def test_exact_finishing_step_on_the_synthetic_law(zero_small, k):
     assert torch.equal(off[0], apply_stop_sequences(torch.zeros_like(want), [], seqs, pad))
     assert torch.equal(on[0], off[0])
     assert off[1] == n - 1 and on[1] == k - 1
-    _check_dead_part(L, k - 1, on, off)
+    lu.check_dead_part(L, k - 1, on, off)
     on2 = _greedy(dec, True, seqs, first, L, n, [], pad, kb, vb)        # the same without step logits (the engine's own buffer)
     assert torch.equal(on2[0], off[0]) and on2[1] == k - 1
-    _check_dead_part(L, k - 1, on2, off[:4] + (None,))
+    lu.check_dead_part(L, k - 1, on2, off[:4] + (None,))
     none = _greedy(dec, True, None, first, L, n, [], pad, kb, vb)       # cleared: nothing ever stops, as before the entry existed
     assert bool((none[0] == 0).all()) and none[1] == n - 1
 
@@ -197,10 +161,10 @@ def test_natural_rows_left_padded(small):
     starts = torch.randint(0, L, (B,), generator=g).to(torch.int32)
     starts[:4] = torch.tensor([0, 11, 5, 1], dtype=torch.int32)
     starts = starts.to(DEV)
-    embs = llm.get_input_embeddings()(_ids(llm, B, L, 4)).clone()
+    embs = llm.get_input_embeddings()(lu.ids(llm, B, L, 4)).clone()
     for b, s in enumerate(starts.tolist()):
         embs[b, :s] = 0
-    kb, vb = _sentinel_cache(dec, B, L + n)
+    kb, vb = lu.sentinel_cache(dec.layers, dec.heads, B, L + n)
     first = dec.prefill(embs.contiguous(), kb, vb, starts=starts)
     plain = _greedy(dec, False, None, first, L, n, [], 5, kb, vb, logits=True, starts=starts)
     _natural_rows(dec, first, L, n, kb, vb, plain, starts=starts)
@@ -239,7 +203,7 @@ def test_early_stop_on_natural_rows(natural):
     on = _greedy(dec, True, seqs, first4, L, n, [], pad, kb4, vb4, logits=True)
     assert torch.equal(off[0], apply_stop_sequences(T, [], seqs, pad)) and torch.equal(on[0], off[0])
     assert off[1] == n - 1 and on[1] == min(F, n - 1)
-    _check_dead_part(L, F, on, off)
+    lu.check_dead_part(L, F, on, off)
 
 
 # ------------------------------------------------------------------------------------------ 6. classifier
@@ -249,7 +213,7 @@ def test_classifier_graph_replays(small):
     saved = gen.eos_token_id
     try:
         # image embeds with the spread of the embedding table (the tiny encoder's rows all decode alike): rows that differ
-        embs = [llm.get_input_embeddings()(_ids(llm, 8, 6, seed)) for seed in (21, 22)]
+        embs = [llm.get_input_embeddings()(lu.ids(llm, 8, 6, seed)) for seed in (21, 22)]
         n, tok, pad = 8, WordHashTokenizer(320), 0
         gen.eos_token_id = []                                              # the natural rows
         kw = dict(max_new_tokens=n, max_batch=8, generate_kwargs=dict(min_length=0))
@@ -285,12 +249,12 @@ def test_classifier_graph_replays(small):
 
 # ------------------------------------------------------------------------------------------ 7. Vicuna width
 def test_vicuna_width():
-    llm = _vicuna_width_decoder()
+    llm = lu.vicuna_width_decoder()
     dec = _HipDecoder(llm, 8)
     try:
         B, L, n, pad = 8, 12, 6, 5
-        kb, vb = _sentinel_cache(dec, B, L + n)
-        first = dec.prefill(llm.get_input_embeddings()(_ids(llm, B, L, 3)).contiguous(), kb, vb)
+        kb, vb = lu.sentinel_cache(dec.layers, dec.heads, B, L + n)
+        first = dec.prefill(llm.get_input_embeddings()(lu.ids(llm, B, L, 3)).contiguous(), kb, vb)
         T = _greedy(dec, False, None, first, L, n, [], pad, kb, vb)[0]
         assert int(T.max()) >= 320                                         # the select at vocabulary 32 000: ids beyond the small one's
         seqs = [[int(T[0, 1])], T[1, 1:3].tolist(), T[2, 0:3].tolist()]
