@@ -128,6 +128,8 @@ SIGNATURES = {
     "cgpt_llm_prefill_reserve": (_I32, [_P, _I32, _I32]),
     "cgpt_llm_prefill": (_I32, [_P, _P, _I32, _I32, _P, _P, _I64, _P, _P]),
     "cgpt_llm_prefill_ragged": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _I64, _P, _P]),
+    "cgpt_llm_prefill_from": (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _P, _P]),
+    "cgpt_llm_kv_broadcast": (_I32, [_P, _P, _P, _I64, _I32, _I32, _P, _P, _P, _I64, _P]),
     "cgpt_llm_step_ragged": (_I32, [_P, _P, _I32, _I32, _P, _P, _P, _I64, _P, _P]),
     "cgpt_llm_greedy_ragged": (_I32, [_P, _P, _I32, _I32, _P, _I32, _I32, _P, _I32, _I64, _P, _P, _I64, _P, _P, _P]),
     "cgpt_llm_set_early_stop": (_I32, [_P, _I32]),

@@ -22,6 +22,8 @@ Config (a plain dict or any mapping; the reference's YAMLs define no smoothing k
             #          shrink by that ratio), activations: "fp16" | "int8" (with decode "hip", prefill "hip" and weights "int8": int8
             #          activations with a per-row outlier split, the LLM.int8() forward; int8_threshold: 6.0, outlier_cap: 64)
             #          -- see build_generating_classifier
+            #          also: shared_prefix: false | true (with decode and prefill "hip": the positions in front of the image tokens --
+            #          <s>, the template's opening, a system text -- are prefilled once per template, not once per noisy copy; same answers)
             #          also: classify: "generate" | "multi_select" (rank the answers by their teacher-forced loss instead of generating:
             #          every noisy copy votes for one of `answers`, never for "other"), score: "hf" | "hip" (who computes those losses;
             #          "hip" needs decode and prefill "hip"), end_sym: "\\n" (appended to every answer; the reference's VQA configs: "###")
@@ -215,6 +217,8 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
                   native prefill + the native scoring pass; needs decode and prefill "hip"), end_sym: "\\n" (appended to every answer);
                   stop_words_ids: None | [[ids], ...] (per-row stop sequences of the greedy decode, any decode), stop_text: None | str
                   (every decoded answer is cut at its first occurrence: "###" for checkpoints tuned with end_sym "###");
+                  shared_prefix: False | True (the prompt's first segment is prefilled once per template and copied into every row;
+                  same answers; needs decode and prefill "hip");
                   sample: "hf" | "hip" (who decodes a sampled call; "hip" needs decode "hip") and the generation fields do_sample,
                   temperature, top_k, top_p, repetition_penalty (handed to the classifier's generate_kwargs where present;
                   `Chat.answer`: do_sample True, top_p 0.9, repetition_penalty 1.05, temperature 1.0)"""
@@ -253,7 +257,8 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
                               end_sym=gen_cfg.get("end_sym", "\n"), activations=gen_cfg.get("activations", "fp16"),
                               int8_threshold=gen_cfg.get("int8_threshold", 6.0), outlier_cap=gen_cfg.get("outlier_cap", 64),
                               stop_words_ids=gen_cfg.get("stop_words_ids"), stop_text=gen_cfg.get("stop_text"),
-                              sample=gen_cfg.get("sample", "hf"), generate_kwargs=fields or None)
+                              sample=gen_cfg.get("sample", "hf"), shared_prefix=gen_cfg.get("shared_prefix", False),
+                              generate_kwargs=fields or None)
 
 
 def build_classifier(model_cfg, num_classes, max_batch, device_index, tokenizer=None, llama_model=None):

@@ -84,6 +84,18 @@ hipError_t launch_prefill_rope(half_t* qkv, int B, int L, int hidden, int heads,
 // starts as above: row b attends over cache rows start[b] .. p only, walked from start[b]; pad rows of `out` are written as zeros.
 hipError_t launch_prefill_attention(const half_t* qkv, int B, int L, int hidden, int heads, int kv_heads, const half_t* Kc, const half_t* Vc,
                                     int64_t len_stride, half_t* out, const int32_t* starts, hipStream_t stream);
+// The two launchers above for L positions that FOLLOW pos0 positions whose cache rows exist (cgpt_llm_prefill_from): qkv / out hold the
+// B L new rows; token row p is rotated at pos0 + p (starts: pos0 + p - start[b], start clamped into 0 .. L-1) and written to cache row
+// pos0 + p; its query attends over cache rows 0 .. pos0 + p (starts: start[b] ..).  The attention tiles the queries by absolute
+// position, so a row's output has the bits launch_prefill_attention gives it on the whole prompt of pos0 + L positions.
+hipError_t launch_prefill_rope_from(half_t* qkv, int B, int pos0, int L, int hidden, int heads, int kv_heads, half_t* Kc, half_t* Vc,
+                                    int64_t len_stride, const half_t* rope, const int32_t* starts, hipStream_t stream);
+hipError_t launch_prefill_attention_from(const half_t* qkv, int B, int pos0, int L, int hidden, int heads, int kv_heads, const half_t* Kc,
+                                         const half_t* Vc, int64_t len_stride, half_t* out, const int32_t* starts, hipStream_t stream);
+// Rows 0 .. P-1 of srcK / srcV [1, kv_heads, src_stride, 128] -> rows s_b .. s_b + P - 1 of every row b of dstK / dstV
+// [B, kv_heads, dst_stride, 128]; s_b = start[b] clamped into 0 .. dst_stride - P, 0 without starts.  16-byte copies, nothing else written.
+hipError_t launch_kv_broadcast(const half_t* srcK, const half_t* srcV, int64_t src_stride, int P, int B, int kv_heads, const int32_t* starts,
+                               half_t* dstK, half_t* dstV, int64_t dst_stride, hipStream_t stream);
 // act[rows, mlp] = fp16(fp16(silu(gate)) * up) from gu [rows, 2 mlp] with gate / up columns interleaved in blocks of 16.
 hipError_t launch_prefill_swiglu(const half_t* gu, int64_t rows, int mlp, half_t* act, hipStream_t stream);
 

@@ -698,8 +698,10 @@ cgpt_status big_gemm(cgpt_llm* m, const half_t* A, int K, const Mat& Wm, int N, 
 // The residual stream stays fp16 as in HF; a projection's output is added by the NEXT add + RMSNorm pass (`pending`).
 // starts (device, or null): row b is left-padded by start[b] positions.  Only the rotary and attention kernels look at it; pad
 // rows pass through the row-independent kernels and GEMMs like any other row (zero embeds stay zeros).
+// pos0 > 0 (cgpt_llm_prefill_from): the L positions follow pos0 positions whose cache rows exist; only the rotary and attention launches
+// differ (their _from twins).  pos0 = 0 launches what it always launched.
 cgpt_status run_prefill(cgpt_llm* m, const half_t* embeds, int B, int L, const int32_t* starts, void* const* kp, void* const* vp,
-                        int64_t len_stride, float* logits, hipStream_t st) {
+                        int64_t len_stride, float* logits, hipStream_t st, int pos0 = 0) {
     const cgpt_llm_config& c = m->cfg;
     const int H = c.hidden, F = c.mlp;
     const int64_t M = (int64_t)B * L;
@@ -710,9 +712,16 @@ cgpt_status run_prefill(cgpt_llm* m, const half_t* embeds, int B, int L, const i
         HIPCHK(launch_prefill_addnorm(x, pending, 1, 0, Lw.ln1, H, c.rms_eps, m->p_h, m->p_xn, M, st));
         x = m->p_h;
         CGCHK(big_gemm(m, m->p_xn, H, Lw.wqkv, qkv_width(c), m->p_qkv, M, st));
-        HIPCHK(launch_prefill_rope(m->p_qkv, B, L, H, c.heads, c.kv_heads, (half_t*)kp[l], (half_t*)vp[l], len_stride, m->rope, starts, st));
-        HIPCHK(launch_prefill_attention(m->p_qkv, B, L, H, c.heads, c.kv_heads, (const half_t*)kp[l], (const half_t*)vp[l], len_stride,
-                                          m->p_attn, starts, st));
+        if (pos0 > 0) {
+            HIPCHK(launch_prefill_rope_from(m->p_qkv, B, pos0, L, H, c.heads, c.kv_heads, (half_t*)kp[l], (half_t*)vp[l], len_stride, m->rope,
+                                            starts, st));
+            HIPCHK(launch_prefill_attention_from(m->p_qkv, B, pos0, L, H, c.heads, c.kv_heads, (const half_t*)kp[l], (const half_t*)vp[l],
+                                                 len_stride, m->p_attn, starts, st));
+        } else {
+            HIPCHK(launch_prefill_rope(m->p_qkv, B, L, H, c.heads, c.kv_heads, (half_t*)kp[l], (half_t*)vp[l], len_stride, m->rope, starts, st));
+            HIPCHK(launch_prefill_attention(m->p_qkv, B, L, H, c.heads, c.kv_heads, (const half_t*)kp[l], (const half_t*)vp[l], len_stride,
+                                              m->p_attn, starts, st));
+        }
         CGCHK(big_gemm(m, m->p_attn, H, Lw.wo, H, m->p_proj, M, st));
         HIPCHK(launch_prefill_addnorm(m->p_h, m->p_proj, 1, 0, Lw.ln2, H, c.rms_eps, m->p_h, m->p_xn, M, st));
         CGCHK(big_gemm(m, m->p_xn, H, Lw.wgu, 2 * F, m->p_gu, M, st));
@@ -1323,6 +1332,43 @@ cgpt_status cgpt_llm_prefill_ragged(cgpt_llm_handle h, const void* embeds_dev, i
     if (!starts_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_prefill_ragged: null starts_dev");
     return llm_prefill_entry("cgpt_llm_prefill_ragged", h, embeds_dev, B, L, starts_dev, k_ptrs_host, v_ptrs_host, kv_len_stride,
                              logits_dev, stream);
+}
+
+cgpt_status cgpt_llm_prefill_from(cgpt_llm_handle h, const void* embeds_dev, int32_t B, int32_t pos0, int32_t Ln, const int32_t* starts_dev,
+                                  void* const* k_ptrs_host, void* const* v_ptrs_host, int64_t kv_len_stride, float* logits_dev,
+                                  void* stream) {
+    const std::string who("cgpt_llm_prefill_from");
+    // what can be judged without the handle comes first, so that each refusal names its own argument
+    if (Ln < 1 || pos0 < 0) return cgpt_fail(CGPT_ERR_INVALID, who + ": Ln must be at least 1 and pos0 at least 0");
+    if ((int64_t)pos0 + Ln > kv_len_stride) return cgpt_fail(CGPT_ERR_INVALID, who + ": pos0 + Ln exceeds kv_len_stride");
+    if (!h || !embeds_dev || !logits_dev) return cgpt_fail(CGPT_ERR_INVALID, who + ": null argument");
+    if ((int64_t)pos0 + Ln > h->cfg.max_len) return cgpt_fail(CGPT_ERR_INVALID, who + ": pos0 + Ln exceeds max_len");
+    CGCHK(check_cache(h, who.c_str(), B, pos0 + Ln - 1, k_ptrs_host, v_ptrs_host, kv_len_stride));
+    CGCHK(ready(h, who.c_str()));
+    if ((int64_t)B * Ln > h->p_rows)
+        return cgpt_fail(CGPT_ERR_STATE, who + ": " + std::to_string((int64_t)B * Ln) + " token rows, the reserved workspace holds " +
+                                             std::to_string(h->p_rows) + " (call cgpt_llm_prefill_reserve outside any capture first)");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    return run_prefill(h, (const half_t*)embeds_dev, B, Ln, starts_dev, k_ptrs_host, v_ptrs_host, kv_len_stride, logits_dev,
+                       (hipStream_t)stream, pos0);
+}
+
+cgpt_status cgpt_llm_kv_broadcast(cgpt_llm_handle h, void* const* src_k_ptrs_host, void* const* src_v_ptrs_host, int64_t src_len_stride,
+                                  int32_t P, int32_t B, const int32_t* starts_dev, void* const* dst_k_ptrs_host,
+                                  void* const* dst_v_ptrs_host, int64_t dst_len_stride, void* stream) {
+    const std::string who("cgpt_llm_kv_broadcast");
+    if (P < 1) return cgpt_fail(CGPT_ERR_INVALID, who + ": P must be at least 1");
+    if (P > src_len_stride) return cgpt_fail(CGPT_ERR_INVALID, who + ": P exceeds src_len_stride");
+    if (P > dst_len_stride) return cgpt_fail(CGPT_ERR_INVALID, who + ": P exceeds dst_len_stride");
+    if (!h) return cgpt_fail(CGPT_ERR_INVALID, who + ": null handle");
+    if (P > h->cfg.max_len) return cgpt_fail(CGPT_ERR_INVALID, who + ": P exceeds max_len");
+    CGCHK(check_cache(h, who.c_str(), 1, P - 1, src_k_ptrs_host, src_v_ptrs_host, src_len_stride));
+    CGCHK(check_cache(h, who.c_str(), B, P - 1, dst_k_ptrs_host, dst_v_ptrs_host, dst_len_stride));
+    HIPCHK(hipSetDevice(h->cfg.device));
+    for (int l = 0; l < h->cfg.layers; ++l)
+        HIPCHK(launch_kv_broadcast((const half_t*)src_k_ptrs_host[l], (const half_t*)src_v_ptrs_host[l], src_len_stride, P, B, h->cfg.kv_heads,
+                                   starts_dev, (half_t*)dst_k_ptrs_host[l], (half_t*)dst_v_ptrs_host[l], dst_len_stride, (hipStream_t)stream));
+    return CGPT_OK;
 }
 
 cgpt_status cgpt_llm_score_reserve(cgpt_llm_handle h, int32_t max_rows, int32_t max_tail_rows) {

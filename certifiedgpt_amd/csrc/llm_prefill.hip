@@ -80,11 +80,14 @@ __global__ __launch_bounds__(256) void llm_prefill_addnorm_kernel(const half_t* 
 // GROUPED (grouped-query attention): the projection row is [hidden | kv_heads * 128 | kv_heads * 128] and the cache
 // [B, kv_heads, len_stride, 128]: q is rotated for all heads; k is rotated, and k / v written, by the threads of heads 0 .. kv_heads-1.
 // The plain instantiation never reads kv_heads.
-template <bool RAGGED, bool GROUPED>
+// CONT (cgpt_llm_prefill_from): the L positions of a row follow pos0 positions whose cache rows exist.  Token row p takes rotary row
+// pos0 + p (RAGGED: pos0 + p - start[b]) and cache row pos0 + p, which is the layout the whole prompt of pos0 + L positions has
+// under the same starts: [start[b] pad rows][pos0 earlier rows][the row's real new rows].  CONT = false never reads pos0.
+template <bool RAGGED, bool GROUPED, bool CONT = false>
 __global__ __launch_bounds__(256) void llm_prefill_rope_kernel(half_t* __restrict__ qkv, int64_t rows, int L, int hidden, int heads,
                                                                half_t* __restrict__ Kc, half_t* __restrict__ Vc, int64_t len_stride,
                                                                const half_t* __restrict__ rope, const int* __restrict__ starts,
-                                                               int kv_heads) {
+                                                               int kv_heads, int pos0) {
     const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (id >= rows * heads * 8) return;
     const int c8 = (int)(id & 7) * 8;
@@ -97,6 +100,7 @@ __global__ __launch_bounds__(256) void llm_prefill_rope_kernel(half_t* __restric
         if (p < s) return;
         rp = p - s;
     }
+    if constexpr (CONT) rp += pos0;
     const h16x8 cs = *reinterpret_cast<const h16x8*>(rope + (int64_t)rp * HD + c8);
     const h16x8 sn = *reinterpret_cast<const h16x8*>(rope + (int64_t)rp * HD + 64 + c8);
     if constexpr (GROUPED) {
@@ -118,7 +122,7 @@ __global__ __launch_bounds__(256) void llm_prefill_rope_kernel(half_t* __restric
     half_t* q = qkv + r * (GROUPED ? hidden + 2 * kv_heads * HD : 3 * hidden) + h * HD + c8;
     half_t* k = q + hidden;                                  // head h of the k block: h < kv_heads
     const half_t* v = k + (GROUPED ? kv_heads * HD : hidden);
-    const int64_t crow = ((int64_t)(b * (GROUPED ? kv_heads : heads) + h) * len_stride + p) * HD + c8;
+    const int64_t crow = ((int64_t)(b * (GROUPED ? kv_heads : heads) + h) * len_stride + (CONT ? pos0 + p : p)) * HD + c8;
     const h16x8 q0 = *reinterpret_cast<const h16x8*>(q), q1 = *reinterpret_cast<const h16x8*>(q + 64);
     const h16x8 k0 = *reinterpret_cast<const h16x8*>(k), k1 = *reinterpret_cast<const h16x8*>(k + 64);
     h16x8 qa, qb, ka, kb;
@@ -158,15 +162,23 @@ constexpr int AQ = 64, AKC = 64, AKP = HD + 8, AVP = AKC + 8;
 // GROUPED: query head h reads K/V head h / (heads / kv_heads) of a [B, kv_heads, len_stride, 128] cache, and a
 // projection row is hidden + 2 kv_heads 128 wide.  Each query head still stages its K/V head for itself (the G heads of a group do
 // not share a staged chunk here: this kernel is 3 % of a prefill).  The plain instantiation never reads kv_heads.
-template <bool RAGGED, bool GROUPED>
+//
+// CONT (cgpt_llm_prefill_from): the queries are positions pos0 .. pos0 + Lbuf - 1 (RAGGED: relative to s, pos0 .. pos0 + Lbuf - s - 1)
+// and qkv / out hold their Lbuf rows only: query q is row b Lbuf + (q - pos0) (RAGGED: + s); keys are cache rows 0 .. q as ever, the
+// earlier ones left by an earlier call.  The queries are tiled by their ABSOLUTE position -- grid index y stands for block
+// pos0 / 64 + y, queries 64 (pos0 / 64 + y) .., wave w for 16 w .. of them -- so a query meets the 64-key chunks, the 32-key blocks,
+// the wave-uniform break and the reduction order it meets in the plain kernel on the whole prompt: its output has the same bits.
+// Queries of the first block below pos0 are treated like queries past L: read from a clamped row, never stored; a wave that has
+// none at or above pos0 still stages and meets the barriers.  CONT = false never reads pos0.
+template <bool RAGGED, bool GROUPED, bool CONT = false>
 __global__ __launch_bounds__(256) void llm_prefill_attn_kernel(const half_t* __restrict__ qkv, int Lbuf, int hidden, int heads,
                                                                const half_t* __restrict__ Kc, const half_t* __restrict__ Vc,
                                                                int64_t len_stride, half_t* __restrict__ out,
-                                                               const int* __restrict__ starts, int kv_heads) {
+                                                               const int* __restrict__ starts, int kv_heads, int pos0) {
     __shared__ __attribute__((aligned(16))) half_t ks[AKC * AKP];
     __shared__ __attribute__((aligned(16))) half_t vt[HD * AVP];
     const int b = blockIdx.x / heads, h = blockIdx.x % heads;
-    const int qbase = blockIdx.y * AQ;
+    const int qbase = (CONT ? pos0 / AQ + (int)blockIdx.y : (int)blockIdx.y) * AQ;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r15 = lane & 15, g = lane >> 4;
     const int q0 = qbase + wave * 16;                       // wave-uniform
@@ -174,14 +186,14 @@ __global__ __launch_bounds__(256) void llm_prefill_attn_kernel(const half_t* __r
     if (RAGGED) {
         s = min(max(starts[b], 0), Lbuf - 1);
         for (int i = tid; i < AQ * 16; i += 256) {           // pad query rows among buffer positions qbase .. qbase + 63: zeros
-            const int row = qbase + (i >> 4);
-            if (row < s)
+            const int row = (CONT ? qbase - pos0 : qbase) + (i >> 4);
+            if (row < s && (!CONT || row >= 0))
                 *reinterpret_cast<h16x8*>(out + ((int64_t)b * Lbuf + row) * hidden + h * HD + (i & 15) * 8) = h16x8{0, 0, 0, 0, 0, 0, 0, 0};
         }
-        if (qbase >= Lbuf - s) return;
+        if (qbase >= (CONT ? pos0 + Lbuf - s : Lbuf - s)) return;
     }
-    const int L = Lbuf - s;                                  // real positions; everything below is relative to the first of them
-    const int64_t row0 = (int64_t)b * Lbuf + s;
+    const int L = CONT ? pos0 + Lbuf - s : Lbuf - s;         // real positions; everything below is relative to the first of them
+    const int64_t row0 = CONT ? (int64_t)b * Lbuf + s - pos0 : (int64_t)b * Lbuf + s;      // row0 + q: the row of (relative) query q
     const int64_t chead = GROUPED ? (int64_t)b * kv_heads + h / (heads / kv_heads) : (int64_t)(b * heads + h);
     const int64_t ldq = GROUPED ? hidden + 2 * kv_heads * HD : 3 * hidden;
     const half_t* Kh = Kc + (chead * len_stride + s) * HD;
@@ -190,7 +202,7 @@ __global__ __launch_bounds__(256) void llm_prefill_attn_kernel(const half_t* __r
     // B fragments of the wave's 16 queries: Q[q0 + r15][32 d + 8 g ..]
     h16x8 qf[4];
     {
-        const int qrow = min(q0 + r15, L - 1);
+        const int qrow = CONT ? max(min(q0 + r15, L - 1), pos0) : min(q0 + r15, L - 1);
         const half_t* qp = qkv + (row0 + qrow) * ldq + h * HD + 8 * g;
 #pragma unroll
         for (int d = 0; d < 4; ++d) qf[d] = *reinterpret_cast<const h16x8*>(qp + 32 * d);
@@ -218,7 +230,7 @@ __global__ __launch_bounds__(256) void llm_prefill_attn_kernel(const half_t* __r
             for (int e = 0; e < 8; ++e) vt[(d8 + e) * AVP + key] = vv[e];
         }
         __syncthreads();
-        if (q0 >= L) continue;                               // a wave with no query still stages and meets the barriers
+        if (q0 >= L || (CONT && q0 + 15 < pos0)) continue;   // a wave with no query still stages and meets the barriers
 #pragma unroll
         for (int kb = 0; kb < AKC; kb += 32) {
             const int kbase = k0 + kb;
@@ -273,18 +285,37 @@ __global__ __launch_bounds__(256) void llm_prefill_attn_kernel(const half_t* __r
             }
         }
     }
-    if (q0 >= L) return;
+    if (q0 >= L || (CONT && q0 + 15 < pos0)) return;
     float lr[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) lr[r] = __shfl(lrun, 4 * g + r);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int q = q0 + 4 * g + r;
-        if (q >= L) continue;
+        if (q >= L || (CONT && q < pos0)) continue;
         half_t* orow = out + (row0 + q) * hidden + h * HD + r15;
 #pragma unroll
         for (int t = 0; t < 8; ++t) orow[16 * t] = (half_t)(o[t][r] / lr[r]);
     }
+}
+
+// Prefix broadcast (cgpt_llm_kv_broadcast): rows 0 .. P-1 of every head of a one-row cache [1, kv_heads, src_stride, 128] go to rows
+// s_b .. s_b + P - 1 of every row b of a [B, kv_heads, dst_stride, 128] cache, s_b = start[b] clamped into 0 .. dst_stride - P (0
+// without starts).  One thread per 16 bytes; blockIdx.y = 0 copies K, 1 copies V.  Nothing else is written.
+__global__ __launch_bounds__(256) void llm_kv_broadcast_kernel(const half_t* __restrict__ srcK, const half_t* __restrict__ srcV,
+                                                               int64_t src_stride, int P, int B, int kv_heads,
+                                                               const int* __restrict__ starts, half_t* __restrict__ dstK,
+                                                               half_t* __restrict__ dstV, int64_t dst_stride) {
+    const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (id >= (int64_t)B * kv_heads * P * 16) return;
+    const int c8 = (int)(id & 15) * 8;
+    const int p = (int)((id >> 4) % P);
+    const int64_t bh = (id >> 4) / P;
+    const int b = (int)(bh / kv_heads), h = (int)(bh % kv_heads);
+    const int s = starts ? (int)min((int64_t)max(starts[b], 0), dst_stride - P) : 0;
+    const half_t* src = (blockIdx.y ? srcV : srcK) + ((int64_t)h * src_stride + p) * HD + c8;
+    half_t* dst = (blockIdx.y ? dstV : dstK) + (((int64_t)b * kv_heads + h) * dst_stride + s + p) * HD + c8;
+    *reinterpret_cast<h16x8*>(dst) = *reinterpret_cast<const h16x8*>(src);
 }
 
 __device__ __forceinline__ float silu_f16(float gate) { return rf16(gate / (1.0f + expf(-gate))); }
@@ -326,16 +357,16 @@ hipError_t launch_prefill_rope(half_t* qkv, int B, int L, int hidden, int heads,
     const bool grouped = kv_heads != heads;
     if (grouped && starts)
         hipLaunchKernelGGL((llm_prefill_rope_kernel<true, true>), grid, dim3(256), 0, stream, qkv, rows, L, hidden, heads, Kc, Vc, len_stride,
-                           rope, starts, kv_heads);
+                           rope, starts, kv_heads, 0);
     else if (grouped)
         hipLaunchKernelGGL((llm_prefill_rope_kernel<false, true>), grid, dim3(256), 0, stream, qkv, rows, L, hidden, heads, Kc, Vc, len_stride,
-                           rope, nullptr, kv_heads);
+                           rope, nullptr, kv_heads, 0);
     else if (starts)
         hipLaunchKernelGGL((llm_prefill_rope_kernel<true, false>), grid, dim3(256), 0, stream, qkv, rows, L, hidden, heads, Kc, Vc, len_stride,
-                           rope, starts, heads);
+                           rope, starts, heads, 0);
     else
         hipLaunchKernelGGL((llm_prefill_rope_kernel<false, false>), grid, dim3(256), 0, stream, qkv, rows, L, hidden, heads, Kc, Vc, len_stride,
-                           rope, nullptr, heads);
+                           rope, nullptr, heads, 0);
     return hipGetLastError();
 }
 
@@ -348,16 +379,70 @@ hipError_t launch_prefill_attention(const half_t* qkv, int B, int L, int hidden,
     const bool grouped = kv_heads != heads;
     if (grouped && starts)
         hipLaunchKernelGGL((llm_prefill_attn_kernel<true, true>), grid, dim3(256), 0, stream, qkv, L, hidden, heads, Kc, Vc, len_stride, out,
-                           starts, kv_heads);
+                           starts, kv_heads, 0);
     else if (grouped)
         hipLaunchKernelGGL((llm_prefill_attn_kernel<false, true>), grid, dim3(256), 0, stream, qkv, L, hidden, heads, Kc, Vc, len_stride, out,
-                           nullptr, kv_heads);
+                           nullptr, kv_heads, 0);
     else if (starts)
         hipLaunchKernelGGL((llm_prefill_attn_kernel<true, false>), grid, dim3(256), 0, stream, qkv, L, hidden, heads, Kc, Vc, len_stride, out,
-                           starts, heads);
+                           starts, heads, 0);
     else
         hipLaunchKernelGGL((llm_prefill_attn_kernel<false, false>), grid, dim3(256), 0, stream, qkv, L, hidden, heads, Kc, Vc, len_stride, out,
-                           nullptr, heads);
+                           nullptr, heads, 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_prefill_rope_from(half_t* qkv, int B, int pos0, int L, int hidden, int heads, int kv_heads, half_t* Kc, half_t* Vc,
+                                    int64_t len_stride, const half_t* rope, const int32_t* starts, hipStream_t stream) {
+    if (B < 1 || L < 1 || pos0 < 0 || (int64_t)pos0 + L > len_stride || hidden != heads * HD || kv_heads < 1 || kv_heads > heads ||
+        heads % kv_heads || !qkv || !Kc || !Vc || !rope)
+        return hipErrorInvalidValue;
+    const int64_t rows = (int64_t)B * L, threads = rows * heads * 8;
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    const bool grouped = kv_heads != heads;
+    if (grouped && starts)
+        hipLaunchKernelGGL((llm_prefill_rope_kernel<true, true, true>), grid, dim3(256), 0, stream, qkv, rows, L, hidden, heads, Kc, Vc,
+                           len_stride, rope, starts, kv_heads, pos0);
+    else if (grouped)
+        hipLaunchKernelGGL((llm_prefill_rope_kernel<false, true, true>), grid, dim3(256), 0, stream, qkv, rows, L, hidden, heads, Kc, Vc,
+                           len_stride, rope, nullptr, kv_heads, pos0);
+    else if (starts)
+        hipLaunchKernelGGL((llm_prefill_rope_kernel<true, false, true>), grid, dim3(256), 0, stream, qkv, rows, L, hidden, heads, Kc, Vc,
+                           len_stride, rope, starts, heads, pos0);
+    else
+        hipLaunchKernelGGL((llm_prefill_rope_kernel<false, false, true>), grid, dim3(256), 0, stream, qkv, rows, L, hidden, heads, Kc, Vc,
+                           len_stride, rope, nullptr, heads, pos0);
+    return hipGetLastError();
+}
+
+hipError_t launch_prefill_attention_from(const half_t* qkv, int B, int pos0, int L, int hidden, int heads, int kv_heads, const half_t* Kc,
+                                         const half_t* Vc, int64_t len_stride, half_t* out, const int32_t* starts, hipStream_t stream) {
+    if (B < 1 || L < 1 || pos0 < 0 || (int64_t)pos0 + L > len_stride || hidden != heads * HD || kv_heads < 1 || kv_heads > heads ||
+        heads % kv_heads || !qkv || !Kc || !Vc || !out)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(B * heads), (unsigned)((pos0 + L - 1) / AQ - pos0 / AQ + 1));      // blocks pos0 / 64 .. (pos0 + L - 1) / 64
+    const bool grouped = kv_heads != heads;
+    if (grouped && starts)
+        hipLaunchKernelGGL((llm_prefill_attn_kernel<true, true, true>), grid, dim3(256), 0, stream, qkv, L, hidden, heads, Kc, Vc, len_stride,
+                           out, starts, kv_heads, pos0);
+    else if (grouped)
+        hipLaunchKernelGGL((llm_prefill_attn_kernel<false, true, true>), grid, dim3(256), 0, stream, qkv, L, hidden, heads, Kc, Vc, len_stride,
+                           out, nullptr, kv_heads, pos0);
+    else if (starts)
+        hipLaunchKernelGGL((llm_prefill_attn_kernel<true, false, true>), grid, dim3(256), 0, stream, qkv, L, hidden, heads, Kc, Vc, len_stride,
+                           out, starts, heads, pos0);
+    else
+        hipLaunchKernelGGL((llm_prefill_attn_kernel<false, false, true>), grid, dim3(256), 0, stream, qkv, L, hidden, heads, Kc, Vc, len_stride,
+                           out, nullptr, heads, pos0);
+    return hipGetLastError();
+}
+
+hipError_t launch_kv_broadcast(const half_t* srcK, const half_t* srcV, int64_t src_stride, int P, int B, int kv_heads, const int32_t* starts,
+                               half_t* dstK, half_t* dstV, int64_t dst_stride, hipStream_t stream) {
+    if (B < 1 || kv_heads < 1 || P < 1 || P > src_stride || P > dst_stride || !srcK || !srcV || !dstK || !dstV) return hipErrorInvalidValue;
+    const int64_t threads = (int64_t)B * kv_heads * P * 16;
+    hipLaunchKernelGGL(llm_kv_broadcast_kernel, dim3((unsigned)((threads + 255) / 256), 2), dim3(256), 0, stream, srcK, srcV, src_stride, P, B,
+                       kv_heads, starts, dstK, dstV, dst_stride);
     return hipGetLastError();
 }
 

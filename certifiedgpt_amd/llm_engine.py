@@ -318,6 +318,37 @@ class _HipDecoder:
         self._call("prefill", starts, C.c_void_p(embs.data_ptr()), B, int(L), kp, vp, stride, C.c_void_p(logits.data_ptr()), self._stream())
         return logits
 
+    def prefill_from(self, embs, pos0, k_bufs, v_bufs, starts=None):
+        """The continuation prefill (cgpt_llm_prefill_from): embs [B, Ln, hidden] fp16 are positions pos0 .. pos0+Ln-1 of rows whose
+        cache rows 0 .. pos0-1 exist (an earlier `prefill` / `prefill_from`, steps, or `kv_broadcast`) -> the logits of position
+        pos0+Ln-1, [B, vocab] fp32; cache rows pos0 .. pos0+Ln-1 of every layer filled in place, bit for bit what `prefill` leaves for
+        the whole prompt.  The workspace is reserved as in `prefill`, for `max_batch` rows of Ln positions.
+        starts (or None): the left padding of the Ln-position buffer; the cache layout is then the ragged prefill's of pos0+Ln buffer
+        positions under the same starts (the earlier rows of row b sit at starts[b] .. starts[b]+pos0-1)."""
+        C = self._C
+        B, Ln, hidden = embs.shape
+        pos0 = int(pos0)
+        assert (embs.dtype == torch.float16 and embs.device == self.device and embs.is_contiguous() and hidden == self.heads * 128
+                and 1 <= B <= self.max_batch and Ln >= 1 and pos0 >= 0)
+        kp, vp, stride = self._cache_tables(k_bufs, v_bufs, B, pos0 + Ln)
+        if not torch.cuda.is_current_stream_capturing():
+            self._lib_mod.check(self.L.cgpt_llm_prefill_reserve(self.handle, self.max_batch, Ln))
+        logits = torch.empty((B, self.vocab), dtype=torch.float32, device=self.device)
+        self._lib_mod.check(self.L.cgpt_llm_prefill_from(self.handle, C.c_void_p(embs.data_ptr()), B, pos0, int(Ln),
+                                                         None if starts is None else self._starts_ptr(starts, B), kp, vp, stride,
+                                                         C.c_void_p(logits.data_ptr()), self._stream()))
+        return logits
+
+    def kv_broadcast(self, src_k, src_v, P, k_bufs, v_bufs, starts=None):
+        """cgpt_llm_kv_broadcast: rows 0 .. P-1 of the one-row caches src_k / src_v (per layer, [1, kv_heads, src_stride, 128]) into rows
+        starts[b] .. starts[b]+P-1 (0 .. P-1 without starts) of every row of k_bufs / v_bufs; no other row is written."""
+        B = int(k_bufs[0].shape[0])
+        skp, svp, sstride = self._cache_tables(src_k, src_v, 1, int(P))
+        kp, vp, stride = self._cache_tables(k_bufs, v_bufs, B, int(P))
+        self._lib_mod.check(self.L.cgpt_llm_kv_broadcast(self.handle, skp, svp, sstride, int(P), B,
+                                                         None if starts is None else self._starts_ptr(starts, B), kp, vp, stride,
+                                                         self._stream()))
+
     def _decode(self, entry, first_logits, prompt_len, num_new, min_new, eos_ids, pad_id, k_bufs, v_bufs, return_logits, starts, extra=()):
         """The one body of `greedy` and `sample`: cgpt_llm_<entry>, whose arguments between the step-logits pointer and the stream
         are `extra`."""

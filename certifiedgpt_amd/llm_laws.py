@@ -192,12 +192,27 @@ def stop_sequences_criteria(stop_seqs):
     return StoppingCriteriaList([StopSequences(stop_seqs)])
 
 
-def left_pad_embeds(batch_embs, bucket=None):
+def shared_prefix_len(first_segment_ids):
+    """shared_prefix=True: the positions every row of a call shares in front of its image tokens.  `first_segment_ids` holds one
+    sequence of token ids per row -- the tokens of the prompt's first segment (everything before <ImageHere>: <s>, the template's
+    opening, "<Img>", a system text) -- and the result is P, their common length, when every row's ids are equal, and 0 otherwise
+    (no row, an empty segment, or rows that differ anywhere: the call then takes the whole-prompt prefill).  Equal TOKENS, not equal
+    lengths: under causal attention the hidden states and K/V rows of those positions are then the same in every layer for every row,
+    which is what lets one prefill on one row stand for all of them.  Pure: sequences of ints in, an int out."""
+    rows = [tuple(int(t) for t in ids) for ids in first_segment_ids]
+    if not rows or not rows[0] or any(r != rows[0] for r in rows[1:]):
+        return 0
+    return len(rows[0])
+
+
+def left_pad_embeds(batch_embs, bucket=None, prefix=0):
     """Left padding of prompts of different lengths (minigpt_base.py:407-416): `batch_embs` is a list of tensors [n_i, len_i, hidden]
     (n_i rows that share one length; the reference's loop has n_i = 1) -> (embeds [B, L, hidden] with zeros on the pad positions,
     attention mask [B, L] int, starts [B] int32 = pad positions per row), B = sum n_i, L = the longest length, rounded up to a
     multiple of `bucket` when that is set.  Row b's real tokens sit at positions starts[b] .. L-1.  Pure tensor arithmetic on the
-    inputs' device (CPU tensors work); a row with no real token is a ValueError."""
+    inputs' device (CPU tensors work); a row with no real token is a ValueError.
+    prefix = P (shared_prefix=True): the rows are SUFFIXES that follow P positions held elsewhere; it is P + L that is rounded up to
+    the bucket, so P + L is the padded length, and starts are the starts, of the same call on the whole prompts."""
     if bucket is not None and (isinstance(bucket, bool) or not isinstance(bucket, int) or bucket < 1):
         raise ValueError(f"bucket={bucket!r}: expected None or an int >= 1")
     if not batch_embs:
@@ -205,9 +220,11 @@ def left_pad_embeds(batch_embs, bucket=None):
     lens = [int(e.shape[1]) for e in batch_embs]
     if min(lens) < 1:
         raise ValueError(f"left_pad_embeds: row group {lens.index(min(lens))} has no real token (length 0)")
+    if isinstance(prefix, bool) or not isinstance(prefix, int) or prefix < 0:
+        raise ValueError(f"prefix={prefix!r}: expected an int >= 0")
     L = max(lens)
     if bucket:
-        L = (L + bucket - 1) // bucket * bucket
+        L = (prefix + L + bucket - 1) // bucket * bucket - prefix
     first = batch_embs[0]
     B = sum(int(e.shape[0]) for e in batch_embs)
     embs = torch.zeros([B, L, first.shape[2]], dtype=first.dtype, device=first.device)

@@ -31,8 +31,8 @@ from .llm_laws import (GQA_RATIOS, LAYER_LINEARS, MAX_STOP_LEN, MAX_STOP_SEQS, P
                        SAMPLE_HF_DEFAULTS, _ActInt8Linear, _as_rows, _philox4x32_10, act_int8_twin, apply_stop_sequences,
                        check_sample_settings, check_stop_words_ids, dequantize_rows_int8, expand_kv_state_dict, fp16_ulp,
                        greedy_decode_parity, int8_state_dict, left_pad_embeds, llm_int8_linear, pack_row_candidates,
-                       quantize_act_rows_int8, quantize_rows_int8, sample_token_law, sample_uniform, stop_finish_columns,
-                       stop_sequences_criteria)
+                       quantize_act_rows_int8, quantize_rows_int8, sample_token_law, sample_uniform, shared_prefix_len,
+                       stop_finish_columns, stop_sequences_criteria)
 
 IMAGE_PLACEHOLDER = "<ImageHere>"
 
@@ -96,6 +96,28 @@ class WordHashTokenizer:
         return " ".join(out)
 
 
+class _Prefix:
+    """shared_prefix: the P positions every row of a call shares -- their token `ids` (a tuple, the LRU key) and their one-row caches,
+    per layer `k` / `v` [1, kv_heads, P, 128]."""
+
+    def __init__(self, ids, k, v):
+        self.ids, self.k, self.v = ids, list(k), list(v)
+
+    @property
+    def P(self):
+        return len(self.ids)
+
+    def clone(self):
+        return _Prefix(self.ids, [t.clone() for t in self.k], [t.clone() for t in self.v])
+
+    def hold(self, other):
+        """Take `other`'s caches (same P) in place -- the static copy a captured graph reads; nothing is copied when it holds them."""
+        if self.ids != other.ids:
+            for dst, src in zip(self.k + self.v, other.k + other.v):
+                dst.copy_(src)
+            self.ids = other.ids
+
+
 class MiniGPT4Classifier:
     """:param encoder: a `HipClassifier(mode="encode_img")` (or any object with `encode_img(images) -> (emb, atts)` and
                `encode_img_noisy(x, first_sample, num, sigma, seed) -> emb`, emb = [B, queries, llm_hidden])
@@ -113,6 +135,8 @@ class MiniGPT4Classifier:
        :param early_stop: False (default) | True (with decode="hip") -- the native token steps do no work once every row has its EOS
        :param grouped_kv: False (default) | True (with decode="hip") -- the native engine takes a grouped-query decoder; see __init__
        :param sample: "hf" (default) | "hip" (with decode="hip") -- who decodes a call with do_sample / a repetition penalty; see __init__
+       :param shared_prefix: False (default) | True (with decode="hip" and prefill="hip") -- the positions in front of the image tokens
+               are prefilled once per template instead of once per row; same tokens; see __init__
        :param stop_words_ids: None (default) | up to 8 token-id sequences of 1..8 tokens -- a row finishes when its answer ends in one
        :param stop_text: None (default) | str -- every decoded answer is cut at its first occurrence (the reference's "###")
        :param end_sym: text appended to every candidate answer of `multi_select` ("\n": the reference's default; its VQA configs: "###")
@@ -132,7 +156,7 @@ class MiniGPT4Classifier:
                  generate_kwargs=None, decode="hf", prefill_linear="torch", prefill="model", ragged="hf", prompt_bucket=None,
                  weights="fp16", end_sym="\n", label_smoothing=0.1, score="hf", classify="generate", candidates=None,
                  early_stop=False, grouped_kv=False, activations="fp16", int8_threshold=6.0, outlier_cap=64, stop_words_ids=None,
-                 stop_text=None, sample="hf"):
+                 stop_text=None, sample="hf", shared_prefix=False):
         self.encoder = encoder
         self.llama_model = llama_model
         self.llama_tokenizer = llama_tokenizer
@@ -218,6 +242,18 @@ class MiniGPT4Classifier:
         #   batch size or on how the range is split; `generate` / `__call__` take ids from a running counter (`reset_draws`).  Works
         #   with either prefill, ragged = "hip", weights / activations = "int8", grouped_kv, early_stop and stop_words_ids; counted in
         #   decode_stats["hip_sampled"].  sample = "hf" (default): such calls take HF `generate` and torch's generator, as before.
+        # shared_prefix = True (with decode = "hip" AND prefill = "hip" only; anything else is a ValueError): a prompt is
+        #   segs[0] | image tokens | segs[1], and everything in segs[0] -- <s>, the template's opening, "<Img>", a system text --
+        #   precedes the image, so under causal attention its hidden states and K/V rows are the same for every row of a call and for
+        #   every image asked through the same template.  A native call whose rows share their first segment's TOKENS
+        #   (`shared_prefix_len`; a shared prompt always, per-row texts under ragged = "hip" when their first segments agree) prefills
+        #   those P positions ONCE, on one row, into a one-row cache kept in an LRU of `max_prefixes` entries keyed by the token ids
+        #   (eagerly, outside any capture), and the captured graph copies it into every row (cgpt_llm_kv_broadcast) and prefills only
+        #   image tokens + segs[1] on top of it (cgpt_llm_prefill_from).  Tokens, logits and caches are bit for bit
+        #   those without the flag (tests/test_gpu_llm_prefix.py): the steps, early_stop, stop sequences and the sampler see a complete
+        #   cache.  The suffix is padded so that P + its length is the padded length without the flag: the K/V pool and "one graph
+        #   per bucket" stay.  Counted in decode_stats["hip_prefix_prefills"] (misses) / ["hip_prefix_hits"].  The scoring paths keep
+        #   their whole-prompt prefill.  shared_prefix = False (default): every path launches what it launched before.
         # stop_text = "###": `_decode_outputs` cuts every decoded text at its first occurrence before `clean_answer`
         #   (`Chat.answer`'s `split('###')[0]`) -- at the text level because "###" tokenises differently after different words.
         # score = "hf" (default): `multi_select` / `answer_losses_from_embeds` run the model's own forward once per candidate over the
@@ -279,6 +315,11 @@ class MiniGPT4Classifier:
         if sample == "hip" and decode != "hip":
             raise ValueError(f'sample="hip" needs decode="hip" (got decode={decode!r}): the sampler takes the place of the native '
                              "engine's token select")
+        if not isinstance(shared_prefix, bool):
+            raise ValueError(f"shared_prefix={shared_prefix!r}: expected False or True")
+        if shared_prefix and (decode != "hip" or prefill != "hip"):
+            raise ValueError(f'shared_prefix=True needs decode="hip" and prefill="hip" (got decode={decode!r}, prefill={prefill!r}): '
+                             "the prefix cache is filled and continued by the native prefill")
         stops = check_stop_words_ids(stop_words_ids)
         if stop_text is not None and (not isinstance(stop_text, str) or not stop_text):
             raise ValueError(f"stop_text={stop_text!r}: expected None or a non-empty str")
@@ -324,6 +365,7 @@ class MiniGPT4Classifier:
         self.stop_words_ids = stops or None                 # the validated tuple of tuples; None when there is none
         self.stop_text = stop_text
         self.grouped_kv = grouped_kv
+        self.shared_prefix = shared_prefix
         self.sample = sample
         self._draw_next, self._draw_seed = 0, 0             # `reset_draws`: the ids and the seed of calls that name no sample index
         self._draw_bufs = None                              # (ids [max_batch] int64, seed [1] int64) on the device, made at first use
@@ -342,6 +384,8 @@ class MiniGPT4Classifier:
         import collections
         self._graphs = collections.OrderedDict()            # LRU of captured decode graphs, see _generate_graph
         self.max_graphs = 4
+        self._prefixes = collections.OrderedDict()          # shared_prefix: LRU of one-row prefix caches, see _prefix_entry
+        self.max_prefixes = 4
         self._eos_mask = None
         self.decode_stats = {"graph_replays": 0, "graph_captures": 0, "graph_evictions": 0, "hf_calls": 0, "hf_fallback_kwargs": 0,
                              "hip_steps": 0,                      # token steps enqueued on the native engine (decode = "hip")
@@ -351,6 +395,8 @@ class MiniGPT4Classifier:
                              "hip_ragged_scores": 0,              # native per-row scoring passes (score = "hip", ragged = "hip")
                              "hf_score_fallbacks": 0,             # score = "hip" calls that took the "hf" path (see __init__)
                              "hip_sampled": 0,                    # decodes of the native sampler (sample = "hip"): one per call
+                             "hip_prefix_prefills": 0,            # shared_prefix: one-row prefills of a prefix (LRU misses)
+                             "hip_prefix_hits": 0,                # shared_prefix: calls that found their prefix in the LRU
                              # bytes the native engine holds for weights, scales and scratch (None without one)
                              "weight_bytes": self._hip.weight_bytes if self._hip is not None else None}
 
@@ -376,11 +422,35 @@ class MiniGPT4Classifier:
         return self.llama_model.get_input_embeddings()(token_ids)
 
     # ---- minigpt_base.py:75-89
-    def _segment_embeddings(self, prompt, device):
+    def _segment_ids(self, prompt):
+        """The token ids of the prompt's segments as the tokenizer returns them (host tensors [1, n])."""
         segs = prompt.split(IMAGE_PLACEHOLDER)
-        toks = [self.llama_tokenizer(seg, return_tensors="pt", add_special_tokens=(i == 0)).input_ids.to(device)
+        return [self.llama_tokenizer(seg, return_tensors="pt", add_special_tokens=(i == 0)).input_ids
                 for i, seg in enumerate(segs)]                         # only add bos to the first seg
-        return [self.embed_tokens(t) for t in toks]
+
+    def _segment_tokens(self, prompt, device):
+        return [t.to(device) for t in self._segment_ids(prompt)]
+
+    def _segment_embeddings(self, prompt, device):
+        return [self.embed_tokens(t) for t in self._segment_tokens(prompt, device)]
+
+    def _prefix_entry(self, ids, device):
+        """shared_prefix: the `_Prefix` whose token ids are `ids` (a tuple of ints, taken from the tokenizer's host output), from
+        the LRU (`max_prefixes` entries, keyed by the ids) or, on a miss, from ONE native prefill of that row -- eager: the caller
+        is outside any capture."""
+        entry = self._prefixes.get(ids)
+        if entry is not None:
+            self._prefixes.move_to_end(ids)
+            self.decode_stats["hip_prefix_hits"] += 1
+            return entry
+        while len(self._prefixes) >= max(1, int(self.max_prefixes)):
+            self._prefixes.popitem(last=False)
+        embs = self.embed_tokens(torch.tensor([list(ids)], dtype=torch.long, device=device)).contiguous()
+        k_bufs, v_bufs = self._kv_buffers(embs, 1, len(ids))
+        self._hip.prefill(embs, k_bufs, v_bufs)
+        self.decode_stats["hip_prefix_prefills"] += 1
+        entry = self._prefixes[ids] = _Prefix(ids, k_bufs, v_bufs)
+        return entry
 
     def get_context_emb(self, prompt, img_list):
         seg_embs = self._segment_embeddings(prompt, img_list[0].device)
@@ -400,27 +470,48 @@ class MiniGPT4Classifier:
         # the native engine takes left-padded rows only where it would take a shared prompt: on the device, greedy arguments
         native_pad = self.ragged == "hip" and img_embeds.is_cuda and self._greedy_defaults()
         starts = None
+        # shared_prefix: on the calls the native engine takes, the rows' common first segment is held once (`prefix`, a `_Prefix`)
+        # and `embs` are the suffixes: image tokens + second segment
+        use_prefix = self.shared_prefix and img_embeds.is_cuda and bool(self._greedy_defaults()) and (shared or bool(native_pad))
+        prefix = None
         if shared:
             # shared prompt: segments embedded once and broadcast; equal lengths -> no padding, all-ones mask
             prompt = texts if isinstance(texts, str) else texts[0]
-            segs = self._segment_embeddings(prompt, img_embeds.device)
-            assert len(segs) == 2, "Unmatched numbers of image placeholders and images."
-            embs = torch.cat([segs[0].expand(B, -1, -1), img_embeds, segs[1].expand(B, -1, -1)], dim=1)
+            toks = self._segment_ids(prompt) if use_prefix else []     # host tensors: reading the ids costs no device sync
+            ids = tuple(toks[0][0].tolist()) if toks else ()
+            if shared_prefix_len([ids]):
+                assert len(toks) == 2, "Unmatched numbers of image placeholders and images."
+                prefix = self._prefix_entry(ids, img_embeds.device)
+                embs = torch.cat([img_embeds, self.embed_tokens(toks[1].to(img_embeds.device)).expand(B, -1, -1)], dim=1)
+            else:
+                segs = self._segment_embeddings(prompt, img_embeds.device)
+                assert len(segs) == 2, "Unmatched numbers of image placeholders and images."
+                embs = torch.cat([segs[0].expand(B, -1, -1), img_embeds, segs[1].expand(B, -1, -1)], dim=1)
             if native_pad and self.prompt_bucket:                      # padded up to the bucket: one graph for every length in it
-                embs, attn_mask, starts = left_pad_embeds([embs], self.prompt_bucket)
+                embs, attn_mask, starts = left_pad_embeds([embs], self.prompt_bucket, prefix=prefix.P if prefix else 0)
             else:
                 attn_mask = torch.ones(embs.shape[:2], dtype=torch.int, device=embs.device)
         else:
             assert len(texts) == B
-            batch_embs = [self.get_context_emb(t, [img_embeds[i][None]]) for i, t in enumerate(texts)]
-            embs, attn_mask, starts = left_pad_embeds(batch_embs, self.prompt_bucket if native_pad else None)     # minigpt_base.py:407-416
+            row_toks = [self._segment_ids(t) for t in texts] if use_prefix else []       # host tensors, as above
+            ids = tuple(row_toks[0][0][0].tolist()) if row_toks else ()
+            if shared_prefix_len([t[0][0].tolist() for t in row_toks]):     # every row's first segment is `ids`
+                assert all(len(t) == 2 for t in row_toks), "Unmatched numbers of image placeholders and images."
+                prefix = self._prefix_entry(ids, img_embeds.device)
+                batch_embs = [torch.cat([img_embeds[i][None], self.embed_tokens(t[1].to(img_embeds.device))], dim=1)
+                              for i, t in enumerate(row_toks)]
+            else:
+                batch_embs = [self.get_context_emb(t, [img_embeds[i][None]]) for i, t in enumerate(texts)]
+            embs, attn_mask, starts = left_pad_embeds(batch_embs, self.prompt_bucket if native_pad else None,
+                                                      prefix=prefix.P if prefix else 0)                        # minigpt_base.py:407-416
             if not native_pad:
                 starts = None
         if self.decode in ("graph", "hip") and (shared or native_pad) and embs.is_cuda and self._greedy_defaults():
             if self._sample_settings() is not None:                     # written before the replay: the kernels read them when they run
                 self._write_draws(B, draws, embs.device)
                 self.decode_stats["hip_sampled"] += 1
-            outputs = self._generate_graph(embs, starts)
+            # without a prefix the call is the two-argument one it always was (callers wrap this method with that signature)
+            outputs = self._generate_graph(embs, starts, prefix) if prefix else self._generate_graph(embs, starts)
             if self.activations == "int8":                              # the tokens are read next: the same sync
                 self.last_act_stats()
         else:
@@ -578,13 +669,16 @@ class MiniGPT4Classifier:
         shape = (B, self._hip.kv_heads, length, 128)
         return ([embs.new_empty(shape) for _ in range(self._hip.layers)], [embs.new_empty(shape) for _ in range(self._hip.layers)])
 
-    def greedy_tokens(self, embs, return_logits=False, starts=None):
+    def greedy_tokens(self, embs, return_logits=False, starts=None, prefix=None):
         """What `generate(inputs_embeds=embs, attention_mask=ones, max_new_tokens=n, do_sample=False, min_length=1, ...)` returns for
         prompts without padding, as a straight loop of the model's own forward calls: [B, n] token ids, pad_token_id after a row's
         EOS.  (HF additionally stops, and truncates, at the step where every row has finished; the extra columns here are pad ids,
         which decode to nothing.)  No data-dependent control flow: capturable as one graph.
         starts ([B] int32 on the device, prefill = "hip" only): row b of `embs` is left-padded by starts[b] positions (zeros); the
-        result is what each row gives without its padding."""
+        result is what each row gives without its padding.
+        prefix (a `_Prefix`, prefill = "hip" only): `embs` are the positions AFTER P positions
+        every row shares; their one-row caches are copied into every row, the prefill continues at position P, and the result is
+        what the whole prompts give."""
         from transformers import DynamicCache
         from transformers.cache_utils import DynamicLayer
 
@@ -614,10 +708,18 @@ class MiniGPT4Classifier:
         eos_ids, pad = self._eos_and_pad_ids()
         B, L, _ = embs.shape
         assert starts is None or self.prefill == "hip", 'left-padded rows need prefill="hip"'
+        assert prefix is None or self.prefill == "hip", 'a shared prefix needs prefill="hip"'
         if self.prefill == "hip":                                      # the whole decode in this library: no HF forward, no DynamicCache
             assert B <= self.max_batch, f"{B} rows > max_batch {self.max_batch} (the native decoder's workspace)"
+            if prefix is not None:                                     # the prompt is the P shared positions + these L
+                P, pk, pv = prefix.P, prefix.k, prefix.v
+                L += P
             k_bufs, v_bufs = self._kv_buffers(embs, B, L + self.max_new_tokens)      # what PreallocLayer allocates on the other path
-            logits = self._hip.prefill(embs.contiguous(), k_bufs, v_bufs, starts=starts)
+            if prefix is not None:
+                self._hip.kv_broadcast(pk, pv, P, k_bufs, v_bufs, starts=starts)
+                logits = self._hip.prefill_from(embs.contiguous(), P, k_bufs, v_bufs, starts=starts)
+            else:
+                logits = self._hip.prefill(embs.contiguous(), k_bufs, v_bufs, starts=starts)
             self.decode_stats["hip_prefills"] += 1
             self.decode_stats["hip_steps"] += self.max_new_tokens - 1
             return self._select(logits, L, self.min_new_tokens() if eos_ids else 0, eos_ids, pad, k_bufs, v_bufs, return_logits, starts)
@@ -665,10 +767,11 @@ class MiniGPT4Classifier:
             return torch.stack(tokens, dim=1), torch.stack(step_logits, dim=1)
         return torch.stack(tokens, dim=1)
 
-    def _graph_key(self, embs, ragged=False):
+    def _graph_key(self, embs, ragged=False, prefix=0):
         key = (embs.shape[0], embs.shape[1], embs.dtype, embs.device.index, self.max_new_tokens, bool(self.routed_linears), self.decode,
                self.prefill)
         key = key + ("ragged",) if ragged else key                    # a graph of the _ragged entries is never an unpadded one's
+        key = key + ("prefix", int(prefix)) if prefix else key        # nor is one that continues P shared positions (`embs`: the rest)
         key = key + ("grouped_kv",) if self.grouped_kv else key
         key = key + ("early_stop",) if self.early_stop else key       # nor is one captured with early stop on one captured without
         key = key + ("stop", self.stop_words_ids) if self.stop_words_ids else key      # nor under one set of stop sequences another's
@@ -683,14 +786,17 @@ class MiniGPT4Classifier:
             raise RuntimeError('last_live_steps: no native engine (decode="hip") on this classifier')
         return self._hip.live_steps()
 
-    def _generate_graph(self, embs, starts=None):
+    def _generate_graph(self, embs, starts=None, prefix=None):
         """One captured hipGraph per (batch, prompt length, dtype, device, max_new_tokens, routed prefill, engine, prefill engine), kept in an LRU of
         `max_graphs` entries: a graph pins its private pool -- the pre-allocated K / V of every layer plus activations, ~6.7 GB of K / V
         alone at 200 rows x 32 layers x 64 positions -- and ragged last batches or new prompt lengths add entries; the least recently
         used one is dropped (graph and static tensors freed) before a new capture.
         starts (left-padded rows, see greedy_tokens): the graph is captured on a static copy that is refreshed before every replay, like
-        the embeds -- the kernels read it when they run, so one graph per (batch, PADDED length) serves every mix of prompt lengths."""
-        key = self._graph_key(embs, ragged=starts is not None)
+        the embeds -- the kernels read it when they run, so one graph per (batch, PADDED length) serves every mix of prompt lengths.
+        prefix (shared_prefix, see greedy_tokens): the graph reads the prefix caches from static tensors of its own, which are
+        refreshed before a replay only when they hold another prefix than the wanted one (the ids are compared on the host): with one
+        template for a whole dataset nothing is copied."""
+        key = self._graph_key(embs, ragged=starts is not None, prefix=prefix.P if prefix else 0)
         entry = self._graphs.get(key)
         if entry is not None:
             self._graphs.move_to_end(key)
@@ -702,6 +808,8 @@ class MiniGPT4Classifier:
                 torch.cuda.empty_cache()                                # return the evicted graph's pool before capturing again
             static_in = embs.clone()
             static_starts = None if starts is None else starts.clone()
+            static_prefix = None if prefix is None else prefix.clone()
+            extra = {} if prefix is None else {"prefix": static_prefix}
             side = torch.cuda.Stream(device=embs.device)
             side.wait_stream(torch.cuda.current_stream())
             import contextlib
@@ -710,7 +818,7 @@ class MiniGPT4Classifier:
             hip_prefills = self.decode_stats["hip_prefills"]
             with route:
                 with torch.cuda.stream(side):                          # warm-up outside the capture (lazy initialisations)
-                    self.greedy_tokens(static_in, starts=static_starts)
+                    self.greedy_tokens(static_in, starts=static_starts, **extra)
                 torch.cuda.current_stream().wait_stream(side)
                 graph = torch.cuda.CUDAGraph()
                 # No cyclic garbage may be finalised INSIDE the capture: a dropped classifier that sits in a reference cycle still owns
@@ -722,19 +830,21 @@ class MiniGPT4Classifier:
                 gc.disable()
                 try:
                     with torch.cuda.graph(graph):
-                        static_out = self.greedy_tokens(static_in, starts=static_starts)
+                        static_out = self.greedy_tokens(static_in, starts=static_starts, **extra)
                 finally:
                     if gc_was_on:
                         gc.enable()
             self.decode_stats["hip_steps"] = hip_steps
             self.decode_stats["hip_prefills"] = hip_prefills
-            entry = (graph, static_in, static_out, static_starts)
+            entry = (graph, static_in, static_out, static_starts, static_prefix)
             self._graphs[key] = entry
             self.decode_stats["graph_captures"] += 1
-        graph, static_in, static_out, static_starts = entry
+        graph, static_in, static_out, static_starts, static_prefix = entry
         static_in.copy_(embs)
         if static_starts is not None:
             static_starts.copy_(starts)
+        if static_prefix is not None:
+            static_prefix.hold(prefix)
         graph.replay()
         self.decode_stats["graph_replays"] += 1
         if self._hip is not None:

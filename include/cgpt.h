@@ -464,6 +464,38 @@ cgpt_status cgpt_llm_greedy_ragged(cgpt_llm_handle h, const float* first_logits_
                                    int32_t num_eos, int64_t pad_id, void* const* k_ptrs_host, void* const* v_ptrs_host,
                                    int64_t kv_len_stride, int64_t* tokens_out_dev, float* step_logits_out_dev, void* stream);
 
+/* ---- Continuation prefill: Ln positions on top of a cache that already holds the pos0 positions before them ----
+ * cgpt_llm_prefill_from is cgpt_llm_prefill for positions pos0 .. pos0+Ln-1 of every row: embeds_dev is [B, Ln, hidden] fp16 (the NEW
+ * positions only), rows 0 .. pos0-1 of every layer's K / V buffer MUST ALREADY HOLD the row's keys and values (an earlier
+ * cgpt_llm_prefill / cgpt_llm_prefill_from / steps, or cgpt_llm_kv_broadcast below); layer l writes rows pos0 .. pos0+Ln-1 and no
+ * other cache row; logits_dev receives the logits of position pos0+Ln-1, [B, vocab] fp32.  The attention tiles the queries by their
+ * absolute position, so logits and cache rows are bit for bit those of cgpt_llm_prefill on the whole prompt of pos0+Ln positions
+ * (DESIGN.md 4.4.11): a prompt may be prefilled in chunks with a workspace reserved for B x Ln rows, or a turn appended to an
+ * earlier turn's cache.  pos0 = 0 is cgpt_llm_prefill (cgpt_llm_prefill_ragged with starts_dev).
+ * starts_dev (or NULL: no padding) is the left padding of the Ln-position buffer, clamped into 0 .. Ln-1: row b's pad positions
+ * 0 .. start[b]-1 are left alone (not rotated, not written to the cache, attention output zeros), its real position j >= start[b] is
+ * rotated at pos0 + (j - start[b]) and written to cache row pos0 + j.  The row's cache is then [start[b] rows never touched]
+ * [pos0 earlier rows at start[b] .. start[b]+pos0-1][its real new rows]: the layout cgpt_llm_prefill_ragged gives the whole prompt
+ * of pos0+Ln buffer positions under the same starts, so the _ragged step / greedy / sample / score entries follow with
+ * prompt_len = pos0+Ln and the same starts_dev.  Read when the kernels run.
+ * Contracts of cgpt_llm_prefill: enqueues only, no allocation, no host sync, capturable; the workspace is
+ * cgpt_llm_prefill_reserve's, for B x Ln rows.  CGPT_ERR_INVALID for a null handle, table or buffer, B outside 1..max_batch, Ln < 1,
+ * pos0 < 0, pos0+Ln > kv_len_stride or pos0+Ln > max_len; CGPT_ERR_STATE while weights are missing or the reservation is too small;
+ * all checked before the first launch. */
+cgpt_status cgpt_llm_prefill_from(cgpt_llm_handle h, const void* embeds_dev, int32_t B, int32_t pos0, int32_t Ln, const int32_t* starts_dev,
+                                  void* const* k_ptrs_host, void* const* v_ptrs_host, int64_t kv_len_stride, float* logits_dev,
+                                  void* stream);
+/* Copies a prefix that B rows share into each of them: rows 0 .. P-1 of every head of the ONE-row caches src_k_ptrs_host[l] /
+ * src_v_ptrs_host[l] ([1, kv_heads, src_len_stride, 128], e.g. what cgpt_llm_prefill with B = 1 left) go to rows s_b .. s_b+P-1 of
+ * every row b of dst_k_ptrs_host[l] / dst_v_ptrs_host[l] ([B, kv_heads, dst_len_stride, 128]), for every layer; s_b = 0 with a NULL
+ * starts_dev, otherwise start[b] clamped into 0 .. dst_len_stride-P (read when the kernels run).  No other cache row is written.
+ * One launch per layer, 16-byte loads and stores.  Followed by cgpt_llm_prefill_from(pos0 = P) with the same starts_dev it gives
+ * the cache of the whole prompt.  Enqueues only, capturable, needs no workspace and no weights.  CGPT_ERR_INVALID for a null handle,
+ * table or buffer, B outside 1..max_batch, P < 1, P > src_len_stride, P > dst_len_stride or P > max_len. */
+cgpt_status cgpt_llm_kv_broadcast(cgpt_llm_handle h, void* const* src_k_ptrs_host, void* const* src_v_ptrs_host, int64_t src_len_stride,
+                                  int32_t P, int32_t B, const int32_t* starts_dev, void* const* dst_k_ptrs_host,
+                                  void* const* dst_v_ptrs_host, int64_t dst_len_stride, void* stream);
+
 /* ---- Early stop: the greedy entries do no work once every row has produced an EOS ----
  * cgpt_llm_set_early_stop(h, 1): handle state, read when cgpt_llm_greedy / cgpt_llm_greedy_ragged ENQUEUE (as cgpt_set_noise_law is):
  * a captured graph keeps the setting it was captured under, whatever the handle says at replay.  Off (0) is the state after

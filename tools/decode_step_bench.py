@@ -58,7 +58,18 @@ decode="hip", prefill="hip", no EOS id (every row runs every step):
     sampled     `Chat.answer`'s settings on the native sampler: do_sample, top_p 0.9, repetition_penalty 1.05, temperature 1.0 and
                 HF's default top_k 50; draw ids 0 .. rows - 1, seed 0
     parent      `greedy` on another build of the library (--parent-lib PATH), as under --ragged
-sampler_ms_per_select = (generate(sampled) - generate(greedy)) / --new, from the medians: what the sampler costs beyond the arg-max."""
+sampler_ms_per_select = (generate(sampled) - generate(greedy)) / --new, from the medians: what the sampler costs beyond the arg-max.
+
+--shared-prefix runs the shared-prefix leg instead (shared_prefix=True), same protocol with the rotated leg order,
+every engine decode="hip", prefill="hip".  A prompt is P positions every row shares (random tokens, one row's) + L - P positions of
+the row's own, at two shapes: (--prefix-len, --prompt), default (7, 44), and (--prefix-len2, --prompt2), default (40, 80):
+    plain_L     the whole prompt of L positions on the plain entries, flag off (today's path)
+    prefix_L    flag on: the graph copies the one-row prefix cache into every row (cgpt_llm_kv_broadcast) and prefills the L - P
+                other positions on top of it (cgpt_llm_prefill_from); the one-row prefill of the prefix ran once, before the timing
+    parent      `plain` at the first shape on another build of the library (--parent-lib PATH), as under --ragged
+A speed-up is stated only where the slowest flagged repetition beats the fastest plain one (`slowest_prefix_beats_fastest_plain`).
+broadcast_ms is the broadcast alone, eagerly (one launch per layer) on caches of the call's shape, by HIP events; prefix_miss_ms the
+one-row prefill of the prefix, alike."""
 import argparse
 import json
 import os
@@ -543,6 +554,122 @@ def sample_leg(args, llm, embs, tok, lm):
     print(json.dumps(line))
 
 
+def shared_prefix_leg(args, llm, tok, lm):
+    rows, new, dev = args.rows, args.new, "cuda:0"
+    shapes = [(args.prefix_len, args.prompt), (args.prefix_len2, args.prompt2)]
+    assert all(1 <= P < L for P, L in shapes)
+
+    def build(n, **kw):
+        return MiniGPT4Classifier(_Rows(rows), llm, tok, "<ImageHere>", lm, max_new_tokens=n, max_batch=rows, decode="hip", prefill="hip", **kw)
+
+    clfs = {("plain", n): build(n) for n in (new, 1)}
+    clfs.update({("prefix", n): build(n, shared_prefix=True) for n in (new, 1)})
+    legs, inputs, which = [], {}, {}
+    g = torch.Generator(device="cpu").manual_seed(1)
+    embed = llm.get_input_embeddings()
+    with torch.no_grad():
+        for P, L in shapes:
+            ids = tuple(torch.randint(3, 32000, (P,), generator=g).tolist())
+            suffix = embed(torch.randint(3, 32000, (rows, L - P), generator=g).to(dev)).contiguous()
+            whole = torch.cat([embed(torch.tensor([ids], device=dev)).expand(rows, -1, -1), suffix], dim=1).contiguous()
+            legs += [f"plain_{L}", f"prefix_{L}"]
+            inputs[f"plain_{L}"], which[f"plain_{L}"] = (lambda clf, whole=whole: (whole,)), "plain"
+            inputs[f"prefix_{L}"] = lambda clf, suffix=suffix, ids=ids, P=P: (suffix, None, clf._prefix_entry(ids, dev))
+            which[f"prefix_{L}"] = "prefix"
+    if args.parent_lib:
+        with _other_library(args.parent_lib):
+            clfs.update({("parent", n): build(n) for n in (new, 1)})
+        legs.append("parent")
+        inputs["parent"], which["parent"] = inputs[f"plain_{shapes[0][1]}"], "parent"
+
+    def timed(leg, n):
+        clf = clfs[(which[leg], n)]
+        call = inputs[leg](clf)                                        # a prefix miss (the one-row prefill) happens here, untimed
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = clf._generate_graph(*call)
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b), out
+
+    def eager_ms(fn, reps=5):
+        out = []
+        for _ in range(2 + reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            out.append(a.elapsed_time(b))
+        return out[2:]
+
+    clock_before = _clock()
+    res = {e: {"generate_ms": [], "prefill_ms": [], "order": []} for e in legs}
+    tokens = {}
+    with torch.no_grad():
+        for rep_i in range(args.warmup + args.reps):                   # interleaved, and rotated: every leg takes every place in turn
+            k = rep_i % len(legs)
+            for place, e in enumerate(legs[k:] + legs[:k]):
+                t, out = timed(e, new)
+                tp = timed(e, 1)[0]
+                print(f"decode_step_bench: repetition {rep_i} {e} generate {t:.1f} ms prefill {tp:.1f} ms", file=sys.stderr, flush=True)
+                if rep_i >= args.warmup:
+                    res[e]["generate_ms"].append(t)
+                    res[e]["prefill_ms"].append(tp)
+                    res[e]["order"].append(place)
+                    tokens[e] = out
+        # the two costs the flag adds, alone: the broadcast on caches of the call's shape, and the one-row prefill of a miss
+        clf = clfs[("prefix", new)]
+        alone = {}
+        for P, L in shapes:
+            ids = next(i for i in clf._prefixes if len(i) == P)
+            pk, pv = clf._prefixes[ids].k, clf._prefixes[ids].v
+            kb, vb = clf._kv_buffers(pk[0], rows, L + new)
+            embs1 = embed(torch.tensor([ids], device=dev)).contiguous()
+            alone[str(L)] = {"broadcast_ms": eager_ms(lambda: clf._hip.kv_broadcast(pk, pv, P, kb, vb)),
+                             "broadcast_bytes_written": 2 * 2 * rows * len(pk) * clf._hip.kv_heads * 128 * P,
+                             "prefix_miss_ms": eager_ms(lambda: clf._hip.prefill(embs1, pk, pv))}
+            del kb, vb
+    clock_after = _clock()
+    steps = new - 1
+    for r in res.values():
+        r["step_ms"] = [(gm - pm) / steps for gm, pm in zip(r["generate_ms"], r["prefill_ms"])]
+        for k in ("generate_ms", "prefill_ms", "step_ms"):
+            r[k + "_min_max"] = [min(r[k]), max(r[k])]
+
+    def overlap(a, b, k):
+        (a0, a1), (b0, b1) = res[a][k + "_min_max"], res[b][k + "_min_max"]
+        return a0 <= b1 and b0 <= a1
+
+    def med(e, k):
+        return sorted(res[e][k])[len(res[e][k]) // 2]
+
+    keys = ("prefill_ms", "step_ms", "generate_ms")
+    line = {"tool": "decode_step_bench", "leg": "shared_prefix", "rows": rows, "shapes_prefix_prompt": shapes, "new_tokens": new,
+            "layers": args.layers, "reps": args.reps, "warmup": args.warmup, "leg_order": "rotated by one place per repetition",
+            "engines": res, "alone": alone, "shader_clock_mhz_before_after": [clock_before, clock_after],
+            "device": torch.cuda.get_device_name(0)}
+    for P, L in shapes:
+        a, b = f"prefix_{L}", f"plain_{L}"
+        bc = sorted(alone[str(L)]["broadcast_ms"])[len(alone[str(L)]["broadcast_ms"]) // 2]
+        line[f"shape_{P}_{L}"] = {
+            "prefix_over_plain_median": {k: med(a, k) / med(b, k) for k in keys},
+            "slowest_prefix_beats_fastest_plain": {k: max(res[a][k]) < min(res[b][k]) for k in ("prefill_ms", "generate_ms")},
+            "prefix_share_of_positions": P / L,
+            "broadcast_ms_median": bc, "broadcast_share_of_flagged_prefill": bc / med(a, "prefill_ms"),
+            "rows_with_plain_tokens": int((tokens[a] == tokens[b]).all(dim=1).sum())}
+    stats = clfs[("prefix", new)].decode_stats
+    line["prefix_prefills_hits_captures_replays"] = [stats["hip_prefix_prefills"], stats["hip_prefix_hits"], stats["graph_captures"],
+                                                     stats["graph_replays"]]
+    if "parent" in res:
+        first = f"plain_{shapes[0][1]}"
+        line["parent_lib"] = os.path.basename(args.parent_lib)
+        line["plain_and_parent_ranges_overlap"] = {k: overlap(first, "parent", k) for k in keys}
+        line["plain_over_parent_median"] = {k: med(first, k) / med("parent", k) for k in keys}
+        line["plain_rows_with_parent_tokens"] = int((tokens[first] == tokens["parent"]).all(dim=1).sum())
+    print(json.dumps(line))
+
+
 def gqa_leg(args, dev):
     rows, new = args.rows, args.new
     lm = AnswerLabelMap(4, ())
@@ -644,9 +771,13 @@ def main():
     ap.add_argument("--stop", action="store_true", help="the stop-sequence leg (see the module docstring)")
     ap.add_argument("--gqa", action="store_true", help="the grouped-query leg (see the module docstring)")
     ap.add_argument("--sample", action="store_true", help="the sampled-decode leg (see the module docstring)")
+    ap.add_argument("--shared-prefix", action="store_true", help="the shared-prefix leg (see the module docstring)")
+    ap.add_argument("--prefix-len", type=int, default=7, help="P of the first shape (with --prompt)")
+    ap.add_argument("--prefix-len2", type=int, default=40, help="P of the second shape (with --prompt2)")
+    ap.add_argument("--prompt2", type=int, default=80)
     ap.add_argument("--gqa-vocab", type=int, default=128256)
     ap.add_argument("--parent-lib", default=None,
-                    help="another build of libcgpt.so for the plain-path A/B of --ragged / --int8 / --early-stop / --stop / --gqa / --sample")
+                    help="another build of libcgpt.so for the plain-path A/B of --ragged / --int8 / --early-stop / --stop / --gqa / --sample / --shared-prefix")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "this benchmark measures device time: it needs the GPU"
     assert 1 <= args.rows <= 256 and args.new >= 2 and args.prompt >= 1
@@ -668,6 +799,8 @@ def main():
         return stop_leg(args, llm, embs, tok, lm)
     if args.sample:
         return sample_leg(args, llm, embs, tok, lm)
+    if args.shared_prefix:
+        return shared_prefix_leg(args, llm, tok, lm)
     how = {"graph": dict(decode="graph"), "hip": dict(decode="hip", prefill="model"), "hip_native": dict(decode="hip", prefill="hip")}
     clfs = {(e, n): MiniGPT4Classifier(_Rows(args.rows), llm, tok, "<ImageHere>", lm, max_new_tokens=n, max_batch=args.rows,
                                        prefill_linear="cgpt", **how[e]) for e in engines for n in (args.new, 1)}
