@@ -97,6 +97,7 @@ SIGNATURES = {
     "cgpt_noise_batch_law": (_I32, [_P, _I64, _I64, _I64, _F, _I32, _U64, _P, _P]),
     "cgpt_rgf_step": (_I32, [_P, _P, _I64, _I64, _I32, _P, _F, _F, _U64, _P, _P]),
     "cgpt_vote": (_I32, [_P, _I64, _I32, _P, _P]),
+    "cgpt_vote_labels": (_I32, [_P, _I64, _I32, _P, _P]),
     "cgpt_allreduce_counts": (_I32, [_P, _P, _I64, _P]),
     "cgpt_allreduce_counts_fn": (_I32, [_P, _P, _P, _I64, _P]),
     "cgpt_certify_from_counts": (_I32, [_P, _P, _I32, _I64, _D, _D, C.POINTER(_I32), C.POINTER(_D)]),
@@ -147,6 +148,11 @@ SIGNATURES = {
                                       _P]),
     "cgpt_llm_sample_logits": (_I32, [_P, _I64, _I32, _I32, _P, _I64, _I32, _I32, _I32, _P, _I32, _I64, _P, LlmSampleParams, _P, _P, _P,
                                       _P, _P, _P, _P, _P]),
+    "cgpt_llm_trie_check": (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, C.POINTER(_I32)]),
+    "cgpt_llm_set_trie": (_I32, [_P, _P, _P, _P, _P, _I32, _I32]),
+    "cgpt_llm_constrained": (_I32, [_P, _P, _I32, _I32, _I32, _I64, _P, _P, _I64, _P, _P, _P, _P]),
+    "cgpt_llm_constrained_ragged": (_I32, [_P, _P, _I32, _I32, _P, _I32, _I64, _P, _P, _I64, _P, _P, _P, _P]),
+    "cgpt_llm_trie_select_logits": (_I32, [_P, _I64, _I32, _I32, _P, _P, _P, _P, _I32, _I64, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

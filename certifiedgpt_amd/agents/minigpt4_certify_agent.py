@@ -33,6 +33,9 @@ Config (a plain dict or any mapping; the reference's YAMLs define no smoothing k
             #          also: sample: "hf" | "hip" (with decode "hip": a sampled decode -- do_sample, temperature, top_k, top_p,
             #          repetition_penalty, the five generation fields that may be given beside it -- stays on the native engine and draws
             #          from a counter-based stream: votes are a function of (image, seed, sample index), whatever the batch size or rank)
+            #          also: classify: "constrained" (the greedy decode restricted to `answers` through a token trie: as many tokens as the
+            #          longest answer + end_sym has, whatever the number of answers; every noisy copy votes for one of them),
+            #          constrain: "hf" | "hip" (who runs it; "hip" needs decode "hip" and votes from device labels, no per-batch read)
             mode: vit_head | encode_img, weights: <path to a torch state_dict saved with torch.save> | null, dims: {...},
             partial_weights: false}   # true: load what the checkpoint has on top of the synthetic initialisation
     data:  {num_images: 10, seed: 1234}      # synthetic CLIP-normalised images unless `dataset` is passed to the agent
@@ -258,6 +261,7 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
                               int8_threshold=gen_cfg.get("int8_threshold", 6.0), outlier_cap=gen_cfg.get("outlier_cap", 64),
                               stop_words_ids=gen_cfg.get("stop_words_ids"), stop_text=gen_cfg.get("stop_text"),
                               sample=gen_cfg.get("sample", "hf"), shared_prefix=gen_cfg.get("shared_prefix", False),
+                              constrain=gen_cfg.get("constrain", "hf"),
                               generate_kwargs=fields or None)
 
 

@@ -268,3 +268,15 @@ def vote(logits, counts):
     _lib.check(L.cgpt_vote(C.c_void_p(logits.data_ptr()), logits.shape[0], logits.shape[1],
                            C.c_void_p(counts.data_ptr()), _stream_ptr()))
     return counts
+
+
+def vote_labels(labels, counts):
+    """counts[labels[b]] += 1 on the device for int32 labels whose class is already known (the constrained decode's); a label outside
+    0 .. len(counts)-1 is not counted."""
+    L = _lib.lib()
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and counts.dtype == torch.int64 and counts.is_contiguous()
+    if labels.numel() == 0:                                            # an empty tensor has no address to hand over
+        return counts
+    _lib.check(L.cgpt_vote_labels(C.c_void_p(labels.data_ptr()), labels.numel(), counts.numel(),
+                                  C.c_void_p(counts.data_ptr()), _stream_ptr()))
+    return counts

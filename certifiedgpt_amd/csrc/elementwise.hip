@@ -366,6 +366,16 @@ __global__ __launch_bounds__(256) void vote_kernel(const float* __restrict__ log
     if (lane == 0) atomicAdd((j < na ? counts : counts_b) + im * 2 * K + bi, 1ull);   // rows >= na belong to the second range
 }
 
+// The vote of rows whose class is already known (the labels of the trie-constrained decode): counts[labels[i]] += 1, one thread per
+// label, one 64-bit atomic each.  A label outside 0 .. K-1 is not counted.
+__global__ __launch_bounds__(256) void vote_labels_kernel(const int* __restrict__ labels, int64_t num, int K,
+                                                          unsigned long long* __restrict__ counts) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= num) return;
+    const int l = labels[i];
+    if (l >= 0 && l < K) atomicAdd(counts + l, 1ull);
+}
+
 
 // ------------------------------------------------------------------- device-side finalisation of certify / predict
 // One wave.  Smooth.certify lines 46-56 (smoothing.py): cAHat = first maximal index of the selection histogram
@@ -562,6 +572,13 @@ hipError_t launch_vote(const float* logits, int64_t ld, int64_t num, int K, int6
     if (num <= 0) return hipSuccess;
     hipLaunchKernelGGL(vote_kernel, dim3((unsigned)((num + 3) / 4)), dim3(256), 0, stream, logits, ld, num, K,
                        reinterpret_cast<unsigned long long*>(counts), na, reinterpret_cast<unsigned long long*>(counts_b), per, row0);
+    return hipGetLastError();
+}
+
+hipError_t launch_vote_labels(const int* labels, int64_t num, int K, int64_t* counts, hipStream_t stream) {
+    if (num <= 0) return hipSuccess;
+    hipLaunchKernelGGL(vote_labels_kernel, dim3(blocks_for(num)), dim3(256), 0, stream, labels, num, K,
+                       reinterpret_cast<unsigned long long*>(counts));
     return hipGetLastError();
 }
 

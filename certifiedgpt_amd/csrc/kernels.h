@@ -106,6 +106,8 @@ hipError_t launch_mean_rows(const float* src, int64_t lds, int rows, int D, int 
 // per > 0 (several images, see launch_noise_im2col): image i = row / per votes into counts + i*2K / counts_b + i*2K.
 hipError_t launch_vote(const float* logits, int64_t ld, int64_t num, int K, int64_t* counts, int64_t na, int64_t* counts_b,
                        hipStream_t stream, int per = 0, int64_t row0 = 0);
+// counts[labels[i]] += 1 for i < num; a label outside 0 .. K-1 is not counted.
+hipError_t launch_vote_labels(const int* labels, int64_t num, int K, int64_t* counts, hipStream_t stream);
 // Smooth.certify lines 46-56 (predict = 0) or Smooth.predict lines 73-79 (predict = 1) on device histograms; one wave.
 // out[0] = label, out[1] = radius | p-value (float64); the radius is stats.h radius(law, pABar, sigma).
 hipError_t launch_finalize(const int64_t* csel, const int64_t* cest, int K, int64_t n, double alpha, double sigma, int predict,

@@ -551,6 +551,11 @@ struct cgpt_llm {
     int *live = nullptr, *live_steps = nullptr;
     int early_stop = 0, last_on = 0, off_steps = 0;
     StopSeqs stop{};                       // cgpt_llm_set_stop_sequences: n = 0 (none) after create; read when a greedy call enqueues
+    // cgpt_llm_set_trie: the candidate trie of the constrained decode, four int32 tables in one allocation; t_nodes = 0 (none) after
+    // create; read when a constrained call enqueues.  Replaced tables stay in `allocs`: a captured call replays on their addresses.
+    const int *t_begin = nullptr, *t_tok = nullptr, *t_node = nullptr, *t_leaf = nullptr;
+    int t_nodes = 0, t_depth = 0;
+    int* trie_node = nullptr;              // [max_batch]: the trie node every row of the running constrained call stands on
     std::set<std::string> loaded;
     size_t expected = 0;
     std::vector<void*> allocs;
@@ -1099,9 +1104,16 @@ static cgpt_status llm_greedy_entry(const char* who_c, cgpt_llm_handle h, const 
                                     int32_t num_eos, int64_t pad_id, void* const* k_ptrs_host, void* const* v_ptrs_host,
                                     int64_t kv_len_stride, int64_t* tokens_out_dev, float* step_logits_out_dev, void* stream,
                                     const cgpt_llm_sample_params* sample = nullptr, const int64_t* draw_ids_dev = nullptr,
-                                    const uint64_t* seed_dev = nullptr) {
+                                    const uint64_t* seed_dev = nullptr, bool constrained = false, int32_t* labels_out_dev = nullptr) {
     const std::string who(who_c);
     if (!h || !first_logits_dev || !tokens_out_dev) return cgpt_fail(CGPT_ERR_INVALID, who + ": null argument");
+    if (constrained) {                                     // the constrained entries: only the select launch differs
+        if (!labels_out_dev) return cgpt_fail(CGPT_ERR_INVALID, who + ": null labels_out_dev");
+        if (h->t_nodes == 0) return cgpt_fail(CGPT_ERR_INVALID, who + ": no trie is set on the handle (cgpt_llm_set_trie)");
+        if (num_new != h->t_depth)
+            return cgpt_fail(CGPT_ERR_INVALID, who + ": num_new " + std::to_string(num_new) + " is not the trie's depth " +
+                                                   std::to_string(h->t_depth));
+    }
     SampleLaw law{};                                       // the sampling entries (sample != null): only the select launch differs
     if (sample) {
         if (!draw_ids_dev || !seed_dev) return cgpt_fail(CGPT_ERR_INVALID, who + ": null draw_ids_dev or seed_dev");
@@ -1134,7 +1146,15 @@ static cgpt_status llm_greedy_entry(const char* who_c, cgpt_llm_handle h, const 
         float* dst = nullptr;
         if (step_logits_out_dev && (i == 0 || mask)) dst = step_logits_out_dev + (int64_t)i * V;
         stop.col = i;
-        if (sample) {
+        if (constrained) {                                 // tables as the handle holds them now: a captured call keeps them
+            if (i == 0 && step_logits_out_dev) HIPCHK(launch_llm_copy_rows(first_logits_dev, V, step_logits_out_dev, ld_out, V, B, st));
+            TrieArgs a{src, lds, h->t_begin, h->t_tok, h->t_node, h->t_leaf, h->t_nodes, (long long)pad_id, i == 0 ? 1 : 0, h->trie_node,
+                       h->unfinished, (long long*)tokens_out_dev + i, (int64_t)num_new, h->tok, labels_out_dev, early ? h->live : nullptr};
+            HIPCHK(launch_llm_trie_select(early, a, B, st));
+            if (early)
+                hipLaunchKernelGGL(llm_live_kernel, dim3(1), dim3(256), 0, st, h->unfinished, B, i == 0 ? 1 : 0, i + 1 < num_new ? 1 : 0,
+                                   h->live, h->live_steps);
+        } else if (sample) {
             SelectArgs a{src, lds, dst, ld_out, V, mask, eos, (long long)pad_id, i == 0 ? 1 : 0, h->unfinished,
                          (long long*)tokens_out_dev + i, (int64_t)num_new, h->tok, early ? h->live : nullptr};
             SampleIo io{(const long long*)tokens_out_dev, (int64_t)num_new, i, i, (const long long*)draw_ids_dev,
@@ -1212,6 +1232,51 @@ cgpt_status cgpt_llm_sample_ragged(cgpt_llm_handle h, const float* first_logits_
     return llm_greedy_entry("cgpt_llm_sample_ragged", h, first_logits_dev, B, prompt_len, starts_dev, num_new, min_new, eos_ids_host,
                             num_eos, pad_id, k_ptrs_host, v_ptrs_host, kv_len_stride, tokens_out_dev, step_logits_out_dev, stream, &params,
                             draw_ids_dev, seed_dev);
+}
+
+cgpt_status cgpt_llm_constrained(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len, int32_t num_new,
+                                 int64_t pad_id, void* const* k_ptrs_host, void* const* v_ptrs_host, int64_t kv_len_stride,
+                                 int64_t* tokens_out_dev, float* step_logits_out_dev, int32_t* labels_out_dev, void* stream) {
+    return llm_greedy_entry("cgpt_llm_constrained", h, first_logits_dev, B, prompt_len, nullptr, num_new, 0, nullptr, 0, pad_id, k_ptrs_host,
+                            v_ptrs_host, kv_len_stride, tokens_out_dev, step_logits_out_dev, stream, nullptr, nullptr, nullptr, true,
+                            labels_out_dev);
+}
+
+cgpt_status cgpt_llm_constrained_ragged(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len,
+                                        const int32_t* starts_dev, int32_t num_new, int64_t pad_id, void* const* k_ptrs_host,
+                                        void* const* v_ptrs_host, int64_t kv_len_stride, int64_t* tokens_out_dev,
+                                        float* step_logits_out_dev, int32_t* labels_out_dev, void* stream) {
+    if (!starts_dev) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_constrained_ragged: null starts_dev");
+    return llm_greedy_entry("cgpt_llm_constrained_ragged", h, first_logits_dev, B, prompt_len, starts_dev, num_new, 0, nullptr, 0, pad_id,
+                            k_ptrs_host, v_ptrs_host, kv_len_stride, tokens_out_dev, step_logits_out_dev, stream, nullptr, nullptr, nullptr,
+                            true, labels_out_dev);
+}
+
+cgpt_status cgpt_llm_set_trie(cgpt_llm_handle h, const int32_t* child_begin, const int32_t* child_tok, const int32_t* child_node,
+                              const int32_t* leaf_class, int32_t nodes, int32_t edges) {
+    const std::string who = "cgpt_llm_set_trie";
+    if (!h) return cgpt_fail(CGPT_ERR_INVALID, who + ": null handle");
+    if (nodes == 0) {                                      // cleared; the old tables stay allocated for the graphs that hold them
+        h->t_begin = h->t_tok = h->t_node = h->t_leaf = nullptr;
+        h->t_nodes = h->t_depth = 0;
+        return CGPT_OK;
+    }
+    int32_t depth = 0;                                     // the tables are checked first: it takes no device to refuse them
+    CGCHK(cgpt_llm_trie_check(child_begin, child_tok, child_node, leaf_class, nodes, edges, h->cfg.vocab, &depth));
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (!h->trie_node) CGCHK(dev_zalloc(h, (size_t)h->cfg.max_batch * sizeof(int), (void**)&h->trie_node));
+    int* t = nullptr;                                      // [nodes + 1 | edges | edges | nodes]
+    const size_t n1 = (size_t)nodes + 1, ne = (size_t)edges;
+    CGCHK(dev_zalloc(h, (n1 + 2 * ne + (size_t)nodes) * sizeof(int), (void**)&t));
+    HIPCHK(hipMemcpy(t, child_begin, n1 * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(t + n1, child_tok, ne * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(t + n1 + ne, child_node, ne * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(t + n1 + 2 * ne, leaf_class, (size_t)nodes * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipDeviceSynchronize());
+    h->t_begin = t; h->t_tok = t + n1; h->t_node = t + n1 + ne; h->t_leaf = t + n1 + 2 * ne;   // complete or not at all
+    h->t_nodes = nodes;
+    h->t_depth = depth;
+    return CGPT_OK;
 }
 
 cgpt_status cgpt_llm_set_early_stop(cgpt_llm_handle h, int32_t on) {

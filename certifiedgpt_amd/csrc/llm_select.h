@@ -75,4 +75,19 @@ hipError_t launch_llm_sample(bool guard, const StopSeqs* stop, const SelectArgs&
 cgpt_status check_sample_params(const std::string& who, const cgpt_llm_sample_params& p, int vocab, int num_prev, int num_eos,
                                 SampleLaw* out);
 
+// ------------------------------------------------------------------------------------- trie-constrained select (llm_trie.hip)
+// The law is stated once in llm_laws.py (`constrained_select_law`) and in DESIGN.md 4.4.12.  The tables are the CSR trie
+// cgpt_llm_trie_check validates (device pointers here); `node` is the row's position in it, [rows] int32 like `unfinished`.
+constexpr int TRIE_MAX_NODES = 1 << 20, TRIE_MAX_DEPTH = 32;
+struct TrieArgs {
+    const float* src; int64_t lds;                                               // the logits select reads: src[row * lds + token]
+    const int *child_begin, *child_tok, *child_node, *leaf_class; int nodes;
+    long long pad; int first;
+    int* node; int* unfinished; long long* tokens_out; int64_t ld_tokens; long long* next_tok; int* labels_out; const int* live;
+};
+// One workgroup per row.  guard: the early-stop instantiation (reads *live).
+hipError_t launch_llm_trie_select(bool guard, const TrieArgs& a, int rows, hipStream_t stream);
+// dst[r * ldd + 0 .. cols) = src[r * lds + 0 .. cols) for r < rows (fp32)
+hipError_t launch_llm_copy_rows(const float* src, int64_t lds, float* dst, int64_t ldd, int cols, int rows, hipStream_t stream);
+
 }  // namespace cgpt

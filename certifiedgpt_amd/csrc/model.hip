@@ -750,6 +750,12 @@ cgpt_status cgpt_vote(const float* logits_dev, int64_t num, int32_t num_classes,
     return CGPT_OK;
 }
 
+cgpt_status cgpt_vote_labels(const int32_t* labels_dev, int64_t num, int32_t num_classes, int64_t* counts_dev, void* stream) {
+    if (!labels_dev || !counts_dev || num < 0 || num_classes < 1) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_vote_labels: bad argument");
+    HIPCHK(launch_vote_labels(labels_dev, num, num_classes, counts_dev, (hipStream_t)stream));
+    return CGPT_OK;
+}
+
 // The one collective of the path: sum the int64 vote histograms of all ranks in place.  RCCL is not linked into
 // this library.  A communicator is only valid inside the RCCL instance that created it, so ncclAllReduce is taken from a library
 // that is ALREADY MAPPED in the process and never from a freshly loaded one: the caller either hands the function over

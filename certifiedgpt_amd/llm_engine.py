@@ -165,6 +165,7 @@ class _HipDecoder:
         self.early_stop = bool(early_stop)
         self._greedy_ran = False                                       # live_steps has nothing to report before the first `greedy`
         self.stop_sequences = ()                                       # none is the handle's state at create
+        self.trie = None                                               # likewise (set_trie)
         self.grouped_kv = bool(grouped_kv)
         bad = hip_decode_unsupported(llama_model, max_batch, grouped_kv=self.grouped_kv, activations=activations)
         if bad:
@@ -350,17 +351,18 @@ class _HipDecoder:
                                                          self._stream()))
 
     def _decode(self, entry, first_logits, prompt_len, num_new, min_new, eos_ids, pad_id, k_bufs, v_bufs, return_logits, starts, extra=()):
-        """The one body of `greedy` and `sample`: cgpt_llm_<entry>, whose arguments between the step-logits pointer and the stream
-        are `extra`."""
+        """The one body of `greedy`, `sample` and `constrained`: cgpt_llm_<entry>, whose arguments between the step-logits pointer and
+        the stream are `extra`."""
         C = self._C
         B, V = self._check_first_logits(first_logits)
-        assert num_new >= 1 and len(eos_ids) <= 8
+        assert num_new >= 1 and (eos_ids is None or len(eos_ids) <= 8)
         kp, vp, stride = self._cache_tables(k_bufs, v_bufs, B, prompt_len + num_new - 1)
         tokens = torch.empty((B, num_new), dtype=torch.int64, device=self.device)
         steps = torch.empty((B, num_new, V), dtype=torch.float32, device=self.device) if return_logits else None
-        eos = (C.c_int64 * max(1, len(eos_ids)))(*[int(e) for e in eos_ids])
+        # the constrained entries (eos_ids None) take neither min_new nor EOS ids: the trie ends the rows
+        stop = () if eos_ids is None else (int(min_new), (C.c_int64 * max(1, len(eos_ids)))(*[int(e) for e in eos_ids]), len(eos_ids))
         self._greedy_ran = True
-        self._call(entry, starts, C.c_void_p(first_logits.data_ptr()), B, int(prompt_len), int(num_new), int(min_new), eos, len(eos_ids),
+        self._call(entry, starts, C.c_void_p(first_logits.data_ptr()), B, int(prompt_len), int(num_new), *stop,
                    int(pad_id), kp, vp, stride, C.c_void_p(tokens.data_ptr()), C.c_void_p(steps.data_ptr()) if return_logits else None,
                    *extra, self._stream())
         return (tokens, steps) if return_logits else tokens
@@ -383,6 +385,30 @@ class _HipDecoder:
         params = self._lib_mod.sample_params(*check_sample_settings(settings))
         return self._decode("sample", first_logits, prompt_len, num_new, min_new, eos_ids, pad_id, k_bufs, v_bufs, return_logits, starts,
                             extra=(params, C.c_void_p(draw_ids.data_ptr()), C.c_void_p(seed.data_ptr())))
+
+    def set_trie(self, trie):
+        """cgpt_llm_set_trie: the candidate trie (`build_answer_trie`; None clears it) of the next `constrained`; validated by the
+        library, copied to the device, read when a constrained call enqueues -- a captured call keeps what it was captured under.
+        Synchronises and allocates: outside any capture."""
+        C = self._C
+        if trie is None:
+            self._lib_mod.check(self.L.cgpt_llm_set_trie(self.handle, None, None, None, None, 0, 0))
+        else:
+            tabs = [t.to(dtype=torch.int32, device="cpu").contiguous() for t in trie.tables()]
+            self._lib_mod.check(self.L.cgpt_llm_set_trie(self.handle, *[C.c_void_p(t.data_ptr()) for t in tabs], trie.nodes, trie.edges))
+        self.trie = trie
+
+    def constrained(self, first_logits, prompt_len, pad_id, k_bufs, v_bufs, return_logits=False, starts=None):
+        """The constrained loop after the prefill (cgpt_llm_constrained / _ragged; `constrained_decode_law`): `depth` selects over the
+        trie `set_trie` handed over -> (tokens [B, depth] int64, labels [B] int32[, the raw logits each select read])."""
+        C = self._C
+        if self.trie is None:
+            raise RuntimeError("constrained: no trie is set on this engine (set_trie)")
+        B = int(first_logits.shape[0])
+        labels = torch.empty((B,), dtype=torch.int32, device=self.device)
+        out = self._decode("constrained", first_logits, prompt_len, self.trie.depth, None, None, pad_id, k_bufs, v_bufs, return_logits,
+                           starts, extra=(C.c_void_p(labels.data_ptr()),))
+        return (out[0], labels, out[1]) if return_logits else (out, labels)
 
     def set_early_stop(self, on):
         """cgpt_llm_set_early_stop: read by the next `greedy` when it enqueues; a captured call keeps what it was captured under."""

@@ -7,6 +7,7 @@
     the int8 weight law and the int8 activation law with its outlier split       quantize_rows_int8, llm_int8_linear, act_int8_twin, ...
     the multi-head twin of a grouped-query decoder                               expand_kv_state_dict
     left padding and per-row candidate packing                                   left_pad_embeds, pack_row_candidates
+    the trie-constrained select over a vocabulary of candidate answers           build_answer_trie, constrained_select_law, ...
 
 Nothing here touches the library or a device API: torch and the standard library only (`transformers` lazily, where a law is handed
 to HF).  Dependencies point one way: llm_laws <- llm_engine <- minigpt4.
@@ -446,3 +447,164 @@ def expand_kv_state_dict(llama_model):
         else:
             out[name] = w.detach().clone()
     return out
+
+
+# ---- trie-constrained answer decoding (classify="constrained"; csrc/llm_trie.hip; include/cgpt.h), stated once
+TRIE_MAX_NODES, TRIE_MAX_DEPTH = 2 ** 20, 32                            # TRIE_MAX_NODES, TRIE_MAX_DEPTH of csrc/llm_select.h
+
+
+class AnswerTrie:
+    """The candidates' token sequences as a CSR trie of int32 CPU tensors (`build_answer_trie`): the edges of node n are
+    child_begin[n] .. child_begin[n + 1], edge e carries token child_tok[e] and leads to node child_node[e]; leaf_class[n] is the
+    candidate's index at a leaf and -1 on an inner node; `depth` is the longest candidate."""
+
+    def __init__(self, child_begin, child_tok, child_node, leaf_class, depth):
+        self.child_begin, self.child_tok, self.child_node, self.leaf_class, self.depth = child_begin, child_tok, child_node, leaf_class, int(depth)
+
+    @property
+    def nodes(self):
+        return int(self.leaf_class.numel())
+
+    @property
+    def edges(self):
+        return int(self.child_tok.numel())
+
+    def tables(self):
+        return self.child_begin, self.child_tok, self.child_node, self.leaf_class
+
+    def to(self, device):
+        return AnswerTrie(*[t.to(device) for t in self.tables()], self.depth)
+
+
+def build_answer_trie(seqs, vocab_size, names=None):
+    """seqs[c] = the token ids of candidate c -> `AnswerTrie`.  Node 0 is the root; nodes are numbered breadth-first (the child of
+    edge e is node e + 1, so a child's index is greater than its parent's); the edges of one node ascend strictly by token id, which
+    is what makes "first maximum" mean "lowest token id".  The tables depend on the SET of sequences alone (every rank of a
+    distributed run builds the same ones); leaf_class follows the input order.
+    ValueError naming the candidates (names[c], default: the index) for: an empty sequence, a token outside 0 .. vocab_size-1, two equal
+    sequences, a sequence that is a proper prefix of another (a leaf has no children), fewer than 2 candidates, more than 2**20 nodes,
+    depth over 32."""
+    seqs = [tuple(int(t) for t in (s.tolist() if hasattr(s, "tolist") else s)) for s in seqs]
+    name = (lambda c: repr(names[c])) if names is not None else (lambda c: f"#{c}")
+    if len(seqs) < 2:
+        raise ValueError(f"a constrained decode needs at least 2 candidates (got {len(seqs)})")
+    seen = {}
+    for c, s in enumerate(seqs):
+        if not s:
+            raise ValueError(f"candidate {name(c)} has no token")
+        bad = [t for t in s if not 0 <= t < int(vocab_size)]
+        if bad:
+            raise ValueError(f"candidate {name(c)} holds token {bad[0]} outside 0..{int(vocab_size) - 1}")
+        if s in seen:
+            raise ValueError(f"candidates {name(seen[s])} and {name(c)} have the same tokens {list(s)}")
+        seen[s] = c
+    depth = max(len(s) for s in seqs)
+    if depth > TRIE_MAX_DEPTH:
+        c = max(range(len(seqs)), key=lambda i: len(seqs[i]))
+        raise ValueError(f"candidate {name(c)} has {depth} tokens (at most {TRIE_MAX_DEPTH})")
+    order = sorted(range(len(seqs)), key=lambda c: seqs[c])            # lexicographic: a prefix sorts right before its extensions
+    for a, b in zip(order, order[1:]):
+        if seqs[b][:len(seqs[a])] == seqs[a]:
+            raise ValueError(f"candidate {name(a)} (tokens {list(seqs[a])}) is a prefix of candidate {name(b)} (tokens {list(seqs[b])}): "
+                             "a row would end at the shorter one")
+    # breadth-first over groups of candidates that share a prefix; within a node the groups come in ascending token order
+    child_begin, child_tok, child_node, leaf_class = [0], [], [], [-1]
+    queue, head = [(order, 0)], 0                                      # (sorted candidates below the node, the node's depth)
+    while head < len(queue):
+        members, d = queue[head]
+        head += 1
+        if len(members) == 1 and len(seqs[members[0]]) == d:           # a leaf
+            leaf_class[head - 1] = members[0]
+            child_begin.append(len(child_tok))
+            continue
+        i = 0
+        while i < len(members):
+            tok = seqs[members[i]][d]
+            j = i
+            while j < len(members) and seqs[members[j]][d] == tok:
+                j += 1
+            child_tok.append(tok)
+            child_node.append(len(queue))
+            queue.append((members[i:j], d + 1))
+            leaf_class.append(-1)
+            i = j
+        child_begin.append(len(child_tok))
+        if len(queue) > TRIE_MAX_NODES:
+            raise ValueError(f"the candidates' trie has more than {TRIE_MAX_NODES} nodes")
+    as_i32 = lambda v: torch.tensor(v, dtype=torch.int32)              # noqa: E731
+    return AnswerTrie(as_i32(child_begin), as_i32(child_tok), as_i32(child_node), as_i32(leaf_class), depth)
+
+
+def constrained_select_law(logits, node, unfinished, trie, pad):
+    """One select of the constrained decode over logits [B, V] (fp32, finite by contract), node [B] and unfinished [B] (ints) ->
+    (token [B] int64, node' [B] int32, unfinished' [B] int32, label [B] int32).  A finished row gives `pad` and keeps its node; an
+    unfinished row takes the FIRST maximum of logits[b, child_tok[e]] over its node's edges (ascending tokens: the lowest token id
+    among the maxima) and moves to that child; if the child is a leaf the row finishes with label = leaf_class, else label is -1."""
+    cb, ct, cn, lc = [t.tolist() for t in trie.tables()]
+    rows = logits.detach().float().cpu()
+    token, node2, unf2, label = [], [], [], []
+    for b, (n, u) in enumerate(zip([int(v) for v in node.tolist()], [int(v) for v in unfinished.tolist()])):
+        if not u:
+            token.append(int(pad)); node2.append(n); unf2.append(0); label.append(-1)
+            continue
+        e0, e1 = cb[n], cb[n + 1]
+        vals = rows[b, torch.tensor(ct[e0:e1], dtype=torch.long)]
+        e = e0 + int((vals == vals.max()).nonzero()[0])                # the first maximum
+        child = cn[e]
+        token.append(ct[e]); node2.append(child); unf2.append(0 if lc[child] >= 0 else 1); label.append(lc[child] if lc[child] >= 0 else -1)
+    dev = logits.device
+    return (torch.tensor(token, dtype=torch.int64, device=dev), torch.tensor(node2, dtype=torch.int32, device=dev),
+            torch.tensor(unf2, dtype=torch.int32, device=dev), torch.tensor(label, dtype=torch.int32, device=dev))
+
+
+def constrained_decode_law(step_logits, trie, pad):
+    """`constrained_select_law` over step_logits [B, depth, V], teacher-forced on the given per-step logits: every row starts
+    unfinished at the root -> (tokens [B, depth] int64, labels [B] int32).  The test oracle of the native loop and of HF's."""
+    B, depth, _ = step_logits.shape
+    assert depth == trie.depth, (depth, trie.depth)
+    dev = step_logits.device
+    node = torch.zeros(B, dtype=torch.int32, device=dev)
+    unfinished = torch.ones(B, dtype=torch.int32, device=dev)
+    labels = torch.full((B,), -1, dtype=torch.int32, device=dev)
+    tokens = []
+    for i in range(depth):
+        tok, node, unfinished, lab = constrained_select_law(step_logits[:, i], node, unfinished, trie, pad)
+        labels = torch.where(lab >= 0, lab, labels)
+        tokens.append(tok)
+    return torch.stack(tokens, dim=1), labels
+
+
+def trie_walk(tokens, trie):
+    """The leaf class each row of `tokens` [B, n] (tensor or nested lists) spells from the root, reading tokens until a leaf; -1 for
+    a row that leaves the trie or ends on an inner node."""
+    cb, ct, cn, lc = [t.tolist() for t in trie.tables()]
+    out = []
+    for row in _as_rows(tokens):
+        n = 0
+        for t in row:
+            if lc[n] >= 0:
+                break
+            edge = {ct[e]: cn[e] for e in range(cb[n], cb[n + 1])}
+            if t not in edge:
+                n = -1
+                break
+            n = edge[t]
+        out.append(lc[n] if n >= 0 else -1)
+    return out
+
+
+def allowed_tokens_fn(trie, pad=0):
+    """The `prefix_allowed_tokens_fn(batch_id, input_ids)` of HF `generate` for `trie`: walks the GENERATED ids (the prompt is
+    embeddings, so `input_ids` holds generated tokens only) from the root and returns the tokens of the node's edges; [pad] after a
+    leaf, and for ids that left the trie."""
+    cb, ct, cn, lc = [t.tolist() for t in trie.tables()]
+    edges = [{ct[e]: cn[e] for e in range(cb[n], cb[n + 1])} for n in range(len(lc))]
+
+    def fn(batch_id, input_ids):
+        n = 0
+        for t in input_ids.tolist():
+            if lc[n] >= 0 or t not in edges[n]:
+                return [int(pad)]
+            n = edges[n][t]
+        return [int(pad)] if lc[n] >= 0 else list(edges[n].keys())
+    return fn

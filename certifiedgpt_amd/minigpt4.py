@@ -21,11 +21,11 @@ mask is all ones (identical to what the reference's left-padding produces for eq
 
 What the LLaMA path is specified to compute (stop rule, sampling law, int8 laws, the grouped-query twin, padding) is stated in
 llm_laws.py; the ctypes binding of the native engine (`_HipDecoder`, `_LinearRoute`) is llm_engine.py.  Their names stay importable
-from this module, and the classifier resolves `_HipDecoder`, `_LinearRoute` and `vote` through this module's globals.
+from this module, and the classifier resolves `_HipDecoder`, `_LinearRoute`, `vote` and `vote_labels` through this module's globals.
 """
 import torch
 
-from .classifier import vote
+from .classifier import vote, vote_labels
 from .llm_engine import _HipDecoder, _LinearRoute, _rope_theta, hip_decode_unsupported    # noqa: F401  (resolved through this module's globals)
 from .llm_laws import (GQA_RATIOS, LAYER_LINEARS, MAX_STOP_LEN, MAX_STOP_SEQS, PHILOX_WORD_SAMPLE, SAMPLE_FIELDS,    # noqa: F401
                        SAMPLE_HF_DEFAULTS, _ActInt8Linear, _as_rows, _philox4x32_10, act_int8_twin, apply_stop_sequences,
@@ -33,6 +33,8 @@ from .llm_laws import (GQA_RATIOS, LAYER_LINEARS, MAX_STOP_LEN, MAX_STOP_SEQS, P
                        greedy_decode_parity, int8_state_dict, left_pad_embeds, llm_int8_linear, pack_row_candidates,
                        quantize_act_rows_int8, quantize_rows_int8, sample_token_law, sample_uniform, shared_prefix_len,
                        stop_finish_columns, stop_sequences_criteria)
+from .llm_laws import (TRIE_MAX_DEPTH, TRIE_MAX_NODES, AnswerTrie, allowed_tokens_fn, build_answer_trie,    # noqa: F401
+                       constrained_decode_law, constrained_select_law, trie_walk)
 
 IMAGE_PLACEHOLDER = "<ImageHere>"
 
@@ -142,8 +144,11 @@ class MiniGPT4Classifier:
        :param end_sym: text appended to every candidate answer of `multi_select` ("\n": the reference's default; its VQA configs: "###")
        :param label_smoothing: of the answer loss (0.1: modeling_llama.py:105)
        :param score: "hf" (default) | "hip" -- who computes the answer losses of `multi_select`; see __init__
-       :param classify: "generate" (default) | "multi_select" -- what the base classifier of `Smooth` does with a batch; see __init__
-       :param candidates: the answers `classify="multi_select"` ranks (default: `label_map.answers`, in class-id order)
+       :param classify: "generate" (default) | "multi_select" | "constrained" -- what the base classifier of `Smooth` does with a
+               batch; see __init__
+       :param constrain: "hf" (default) | "hip" (with decode="hip") -- who runs the decode of classify="constrained"; see __init__
+       :param candidates: the answers `classify="multi_select"` ranks and `classify="constrained"` decodes among (default:
+               `label_map.answers`, in class-id order)
 
     `prompt` is a plain attribute: assigning a new prompt between two images (`clf.prompt = ...`) is the supported way to ask a
     per-image question (VQA: one question per image).  Under decode="graph" / "hip" every new prompt LENGTH captures a graph of its
@@ -156,7 +161,7 @@ class MiniGPT4Classifier:
                  generate_kwargs=None, decode="hf", prefill_linear="torch", prefill="model", ragged="hf", prompt_bucket=None,
                  weights="fp16", end_sym="\n", label_smoothing=0.1, score="hf", classify="generate", candidates=None,
                  early_stop=False, grouped_kv=False, activations="fp16", int8_threshold=6.0, outlier_cap=64, stop_words_ids=None,
-                 stop_text=None, sample="hf", shared_prefix=False):
+                 stop_text=None, sample="hf", shared_prefix=False, constrain="hf"):
         self.encoder = encoder
         self.llama_model = llama_model
         self.llama_tokenizer = llama_tokenizer
@@ -276,6 +281,22 @@ class MiniGPT4Classifier:
         #   answers, in class-id order; at least 2, at most num_classes - 1) instead of generating: logits [B, num_classes] hold -loss in
         #   column i for candidate i and -inf in column `other_id`, so every row votes for a known class.  classify = "generate"
         #   (default): as before.
+        # classify = "constrained": the greedy decode restricted to `candidates`: at every step the arg-max runs over
+        #   the tokens that continue some candidate -- a trie over the tokens of `answer + end_sym` (`_answer_tokens`, the format
+        #   `multi_select` scores), HF's `prefix_allowed_tokens_fn`; `constrained_select_law` is the law -- and a row stops when it has
+        #   spelled a whole candidate: `depth` = the longest candidate's tokens are generated, whatever the number of candidates, every
+        #   row votes for a known class (never `other_id`), and the class id is the trie leaf's.  The prompt is `generate`'s.  The trie
+        #   is built once, here (`build_answer_trie`: at most 2**20 nodes and 32 tokens per candidate; no candidate may be a prefix of
+        #   another); generation arguments that ask for anything but the plain arg-max are a ValueError here, never another law, and
+        #   stop_words_ids / stop_text belong to `generate()`: the constrained call ignores them.
+        #   constrain = "hf" (default): `llama_model.generate(..., prefix_allowed_tokens_fn=allowed_tokens_fn(trie))`; works on the
+        #   CPU; counted in decode_stats["hf_constrained"].  constrain = "hip" (with decode = "hip"; anything else is a ValueError): the
+        #   native loop with the trie select in the arg-max's place (csrc/llm_trie.hip), after either prefill, from the captured graph;
+        #   composes with prefill = "hip", ragged = "hip", prompt_bucket, shared_prefix, weights / activations = "int8", grouped_kv and
+        #   early_stop (only the select differs); `sample_counts` / `sample_counts_pair` then vote from the device labels
+        #   (cgpt_vote_labels) and read nothing back per batch.  Counted in decode_stats["hip_constrained"]; a call the engine cannot
+        #   take (off the device, more rows than max_batch, per-row texts without ragged = "hip") takes the "hf" path and is counted in
+        #   decode_stats["hf_constrained_fallbacks"].
         assert decode in ("hf", "graph", "hip") and prefill_linear in ("torch", "cgpt")
         if prefill not in ("model", "hip"):
             raise ValueError(f'prefill={prefill!r}: expected "model" or "hip"')
@@ -339,21 +360,30 @@ class MiniGPT4Classifier:
         if score == "hip" and (decode != "hip" or prefill != "hip"):
             raise ValueError(f'score="hip" needs decode="hip" and prefill="hip" (got decode={decode!r}, prefill={prefill!r}): '
                              "the candidates are scored on the cache the native prefill fills")
-        if classify not in ("generate", "multi_select"):
-            raise ValueError(f'classify={classify!r}: expected "generate" or "multi_select"')
+        if classify not in ("generate", "multi_select", "constrained"):
+            raise ValueError(f'classify={classify!r}: expected "generate", "multi_select" or "constrained"')
+        if constrain not in ("hf", "hip"):
+            raise ValueError(f'constrain={constrain!r}: expected "hf" or "hip"')
+        if constrain == "hip" and classify != "constrained":
+            raise ValueError(f'constrain="hip" needs classify="constrained" (got classify={classify!r})')
+        if constrain == "hip" and decode != "hip":
+            raise ValueError(f'constrain="hip" needs decode="hip" (got decode={decode!r}): the trie select takes the place of the native '
+                             "engine's token select")
         if not 0.0 <= float(label_smoothing) < 1.0:
             raise ValueError(f"label_smoothing={label_smoothing!r}: expected a value in [0, 1)")
-        if candidates is not None and classify != "multi_select":
-            raise ValueError('candidates need classify="multi_select" (classify="generate" maps free text through label_map)')
-        if classify == "multi_select":
+        if candidates is not None and classify == "generate":
+            raise ValueError('candidates need classify="multi_select" or "constrained" (classify="generate" maps free text through '
+                             "label_map)")
+        if classify != "generate":
             candidates = list(label_map.answers if candidates is None else candidates)
             if not 2 <= len(candidates) <= self.num_classes - 1:
-                raise ValueError(f'classify="multi_select" needs at least 2 and at most num_classes - 1 = {self.num_classes - 1} '
+                raise ValueError(f'classify="{classify}" needs at least 2 and at most num_classes - 1 = {self.num_classes - 1} '
                                  f"candidates (got {len(candidates)}): class id num_classes - 1 stays \"other\"")
         self.end_sym = end_sym
         self.label_smoothing = float(label_smoothing)
         self.score = score
         self.classify = classify
+        self.constrain = constrain
         self.candidates = candidates
         self.decode = decode
         self.prefill = prefill
@@ -376,9 +406,23 @@ class MiniGPT4Classifier:
         self.activations, self.int8_threshold, self.outlier_cap = activations, float(int8_threshold), int(outlier_cap)
         if activations == "int8":
             engine_kw.update(activations="int8", int8_threshold=self.int8_threshold, outlier_cap=self.outlier_cap)
+        self.trie = None
+        if classify == "constrained":                       # every refusal comes now, before the engine is created
+            if not self._greedy_defaults(native_sampler=False):
+                raise ValueError(f'classify="constrained" is an arg-max over the candidates: generation arguments {self.generate_kwargs!r} '
+                                 "(or the checkpoint's generation_config) ask for sampling, a penalty or another decoding mode")
+            seqs = [tuple(self._answer_tokens(a).tolist()) for a in candidates]
+            eos_ids, _ = self._eos_and_pad_ids()
+            for a, seq in zip(candidates, seqs):
+                if any(t in eos_ids for t in seq[:-1]):
+                    raise ValueError(f"candidate {a!r} holds an end-of-sequence id before its last token (tokens {list(seq)}): HF's "
+                                     "generate would end the row there")
+            self.trie = build_answer_trie(seqs, int(llama_model.config.vocab_size), names=candidates)
         self._hip = _HipDecoder(llama_model, self.max_batch, weights=weights, early_stop=early_stop, **engine_kw) if decode == "hip" else None
         if self._hip is not None and stops:                 # none is the handle's state at create: nothing is called for it
             self._hip.set_stop_sequences(stops)
+        if constrain == "hip":
+            self._hip.set_trie(self.trie)
         self.routed_linears = (_LinearRoute.install(llama_model)
                                if (decode in ("graph", "hip") and prefill_linear == "cgpt" and prefill == "model") else 0)
         import collections
@@ -397,6 +441,9 @@ class MiniGPT4Classifier:
                              "hip_sampled": 0,                    # decodes of the native sampler (sample = "hip"): one per call
                              "hip_prefix_prefills": 0,            # shared_prefix: one-row prefills of a prefix (LRU misses)
                              "hip_prefix_hits": 0,                # shared_prefix: calls that found their prefix in the LRU
+                             "hip_constrained": 0,                # native constrained decodes (constrain = "hip"): one per call
+                             "hf_constrained": 0,                 # constrained decodes through HF `generate`: one per call
+                             "hf_constrained_fallbacks": 0,       # constrain = "hip" calls that took the "hf" path (see __init__)
                              # bytes the native engine holds for weights, scales and scratch (None without one)
                              "weight_bytes": self._hip.weight_bytes if self._hip is not None else None}
 
@@ -459,10 +506,11 @@ class MiniGPT4Classifier:
         return torch.cat(mixed, dim=1)
 
     # ---- minigpt_base.py:374-448 with encode_img's output given
-    @torch.no_grad()
-    def generate_from_embeds(self, img_embeds, texts, draws=None):
-        """img_embeds [B, queries, hidden] (any float dtype) + one prompt per row (or ONE str shared by all rows) -> list[str].
-        draws (sample = "hip" only): (first draw id, seed) -- row r draws stream first + r; None: the running counter (`reset_draws`)."""
+    def _prompt_inputs(self, img_embeds, texts, allow_prefix=True):
+        """The decoder's input for img_embeds [B, queries, hidden] + one prompt per row (or ONE str shared by all rows), as `generate`
+        and the constrained decode take it: (embs, attention mask, starts or None, prefix or None, shared, native_pad).
+        allow_prefix=False: the caller will not take the native engine, so `embs` must be the WHOLE prompts whatever shared_prefix says
+        (HF `generate` knows no prefix cache)."""
         dtype = self.embed_tokens(torch.zeros(1, 1, dtype=torch.long, device=img_embeds.device)).dtype
         img_embeds = img_embeds.to(dtype)
         B = img_embeds.shape[0]
@@ -472,7 +520,8 @@ class MiniGPT4Classifier:
         starts = None
         # shared_prefix: on the calls the native engine takes, the rows' common first segment is held once (`prefix`, a `_Prefix`)
         # and `embs` are the suffixes: image tokens + second segment
-        use_prefix = self.shared_prefix and img_embeds.is_cuda and bool(self._greedy_defaults()) and (shared or bool(native_pad))
+        use_prefix = (allow_prefix and self.shared_prefix and img_embeds.is_cuda and bool(self._greedy_defaults())
+                      and (shared or bool(native_pad)))
         prefix = None
         if shared:
             # shared prompt: segments embedded once and broadcast; equal lengths -> no padding, all-ones mask
@@ -506,6 +555,14 @@ class MiniGPT4Classifier:
                                                       prefix=prefix.P if prefix else 0)                        # minigpt_base.py:407-416
             if not native_pad:
                 starts = None
+        return embs, attn_mask, starts, prefix, shared, native_pad
+
+    @torch.no_grad()
+    def generate_from_embeds(self, img_embeds, texts, draws=None):
+        """img_embeds [B, queries, hidden] (any float dtype) + one prompt per row (or ONE str shared by all rows) -> list[str].
+        draws (sample = "hip" only): (first draw id, seed) -- row r draws stream first + r; None: the running counter (`reset_draws`)."""
+        embs, attn_mask, starts, prefix, shared, native_pad = self._prompt_inputs(img_embeds, texts)
+        B = embs.shape[0]
         if self.decode in ("graph", "hip") and (shared or native_pad) and embs.is_cuda and self._greedy_defaults():
             if self._sample_settings() is not None:                     # written before the replay: the kernels read them when they run
                 self._write_draws(B, draws, embs.device)
@@ -521,6 +578,44 @@ class MiniGPT4Classifier:
             outputs = self.llama_model.generate(inputs_embeds=embs, attention_mask=attn_mask, max_new_tokens=self.max_new_tokens,
                                                 **self.hf_generate_kwargs())
         return self._decode_outputs(outputs)
+
+    @torch.no_grad()
+    def constrained_from_embeds(self, img_embeds, texts, return_logits=False):
+        """classify = "constrained": img_embeds [B, queries, hidden] + one prompt per row (or ONE str) -> (labels [B] int32, tokens
+        [B, depth] int64) on the embeds' device: labels[b] = the index in `candidates` of the answer row b spelled, tokens its
+        tokens followed by pad ids.  Nothing is read back.  return_logits (the "hf" path only): also HF's raw per-step logits
+        [B, steps, V]."""
+        assert self.trie is not None, 'constrained_from_embeds needs classify="constrained"'
+        # decided before the inputs are built: only the native engine may be handed a prompt whose shared prefix sits in a cache
+        shared = isinstance(texts, str) or len(set(texts)) == 1
+        native = (self.constrain == "hip" and not return_logits and img_embeds.is_cuda and img_embeds.shape[0] <= self.max_batch
+                  and (shared or self.ragged == "hip"))
+        embs, attn_mask, starts, prefix, _, _ = self._prompt_inputs(img_embeds, texts, allow_prefix=native)
+        if native:
+            tokens, labels = self._generate_graph(embs, starts, prefix, constrained=True)
+            self.decode_stats["hip_constrained"] += 1
+            return labels, tokens
+        if self.constrain == "hip" and not return_logits:
+            self.decode_stats["hf_constrained_fallbacks"] += 1
+        self.decode_stats["hf_constrained"] += 1
+        _, pad = self._eos_and_pad_ids()
+        kw = self.hf_generate_kwargs()
+        kw.pop("stopping_criteria", None)                              # stop sequences belong to generate(): the trie ends the rows
+        kw.pop("min_new_tokens", None)                                 # and no EOS column is masked: the law reads the raw logits
+        out = self.llama_model.generate(inputs_embeds=embs, attention_mask=attn_mask, max_new_tokens=self.trie.depth,
+                                        prefix_allowed_tokens_fn=allowed_tokens_fn(self.trie, pad), return_dict_in_generate=True,
+                                        output_logits=bool(return_logits), **kw)
+        seq = out.sequences[:, -self.trie.depth:] if out.sequences.shape[1] > self.trie.depth else out.sequences
+        tokens = torch.full((embs.shape[0], self.trie.depth), int(pad), dtype=torch.long, device=embs.device)
+        tokens[:, :seq.shape[1]] = seq                                 # HF ends the call once every row has finished on an EOS
+        walked = trie_walk(tokens, self.trie)
+        if min(walked) < 0:                                            # e.g. a candidate token equal to the pad id HF appends
+            b = walked.index(-1)
+            raise RuntimeError(f'classify="constrained": row {b} of HF generate spells no candidate (tokens {tokens[b].tolist()})')
+        labels = torch.tensor(walked, dtype=torch.int32, device=embs.device)
+        if return_logits:
+            return labels, tokens, torch.stack([l.float() for l in out.logits], dim=1)
+        return labels, tokens
 
     def _decode_outputs(self, outputs):
         """minigpt_base.py:440-447."""
@@ -552,14 +647,16 @@ class MiniGPT4Classifier:
                        "watermarking_config": (None,), "prompt_lookup_num_tokens": (None,), "stop_strings": (None,),
                        "diversity_penalty": (None, 0, 0.0), "max_time": (None,), "dola_layers": (None,)}
 
-    def _greedy_defaults(self):
+    def _greedy_defaults(self, native_sampler=None):
         """May this call take the fixed-length greedy loop?  Only when every argument of the call AND every field of the model's own
         generation_config (which `generate` applies wherever the call is silent) is one the loop reproduces; otherwise the HF path
-        runs, so the same classifier never decodes differently by `decode=`."""
+        runs, so the same classifier never decodes differently by `decode=`.
+        native_sampler (None: sample == "hip"): whether the sampling fields count as reproduced at any value."""
+        sampler = self.sample == "hip" if native_sampler is None else bool(native_sampler)
         for key, val in self.generate_kwargs.items():
             if key not in self._GREEDY_NEUTRAL:
                 return False
-            if self.sample == "hip" and key in SAMPLE_FIELDS:         # the native sampler takes these at any value it accepts
+            if sampler and key in SAMPLE_FIELDS:         # the native sampler takes these at any value it accepts
                 continue
             want = self._GREEDY_NEUTRAL[key]
             if want is not None and val != want:
@@ -567,7 +664,7 @@ class MiniGPT4Classifier:
         gen = getattr(self.llama_model, "generation_config", None)
         if gen is not None:
             for key, neutral in self._CONFIG_NEUTRAL.items():
-                if key in self.generate_kwargs or (self.sample == "hip" and key in SAMPLE_FIELDS):
+                if key in self.generate_kwargs or (sampler and key in SAMPLE_FIELDS):
                     continue                                           # the call's argument wins over the checkpoint's field
                 val = getattr(gen, key, None)
                 if isinstance(val, (list, tuple, dict)) and len(val) == 0:
@@ -613,8 +710,11 @@ class MiniGPT4Classifier:
         self._draw_bufs[1].fill_(seed - (1 << 64) if seed >= 1 << 63 else seed)     # the 64 bits, as int64
         return self._draw_bufs
 
-    def _select(self, logits, L, min_new, eos_ids, pad, k_bufs, v_bufs, return_logits, starts=None):
-        """The native loop after the prefill: the sampler under sample = "hip" when the settings ask for it, the arg-max otherwise."""
+    def _select(self, logits, L, min_new, eos_ids, pad, k_bufs, v_bufs, return_logits, starts=None, constrained=False):
+        """The native loop after the prefill: the sampler under sample = "hip" when the settings ask for it, the arg-max otherwise;
+        constrained: the trie select (tokens and labels)."""
+        if constrained:
+            return self._hip.constrained(logits, L, pad, k_bufs, v_bufs, return_logits=return_logits, starts=starts)
         settings = self._sample_settings()
         if settings is None:
             return self._hip.greedy(logits, L, self.max_new_tokens, min_new, eos_ids, pad, k_bufs, v_bufs, return_logits=return_logits,
@@ -669,7 +769,7 @@ class MiniGPT4Classifier:
         shape = (B, self._hip.kv_heads, length, 128)
         return ([embs.new_empty(shape) for _ in range(self._hip.layers)], [embs.new_empty(shape) for _ in range(self._hip.layers)])
 
-    def greedy_tokens(self, embs, return_logits=False, starts=None, prefix=None):
+    def greedy_tokens(self, embs, return_logits=False, starts=None, prefix=None, constrained=False):
         """What `generate(inputs_embeds=embs, attention_mask=ones, max_new_tokens=n, do_sample=False, min_length=1, ...)` returns for
         prompts without padding, as a straight loop of the model's own forward calls: [B, n] token ids, pad_token_id after a row's
         EOS.  (HF additionally stops, and truncates, at the step where every row has finished; the extra columns here are pad ids,
@@ -678,7 +778,9 @@ class MiniGPT4Classifier:
         result is what each row gives without its padding.
         prefix (a `_Prefix`, prefill = "hip" only): `embs` are the positions AFTER P positions
         every row shares; their one-row caches are copied into every row, the prefill continues at position P, and the result is
-        what the whole prompts give."""
+        what the whole prompts give.
+        constrained (constrain = "hip" only): the trie select in the arg-max's place, `trie.depth` tokens instead of max_new_tokens
+        -> (tokens [B, depth], labels [B] int32[, step logits])."""
         from transformers import DynamicCache
         from transformers.cache_utils import DynamicLayer
 
@@ -707,6 +809,10 @@ class MiniGPT4Classifier:
         llm = self.llama_model
         eos_ids, pad = self._eos_and_pad_ids()
         B, L, _ = embs.shape
+        assert not constrained or (self._hip is not None and self._hip.trie is not None), 'a constrained loop needs constrain="hip"'
+        num_new = self.trie.depth if constrained else self.max_new_tokens
+        if constrained:                                                # the trie ends the rows: no EOS id, no EOS mask
+            eos_ids = []
         assert starts is None or self.prefill == "hip", 'left-padded rows need prefill="hip"'
         assert prefix is None or self.prefill == "hip", 'a shared prefix needs prefill="hip"'
         if self.prefill == "hip":                                      # the whole decode in this library: no HF forward, no DynamicCache
@@ -714,17 +820,18 @@ class MiniGPT4Classifier:
             if prefix is not None:                                     # the prompt is the P shared positions + these L
                 P, pk, pv = prefix.P, prefix.k, prefix.v
                 L += P
-            k_bufs, v_bufs = self._kv_buffers(embs, B, L + self.max_new_tokens)      # what PreallocLayer allocates on the other path
+            k_bufs, v_bufs = self._kv_buffers(embs, B, L + num_new)                  # what PreallocLayer allocates on the other path
             if prefix is not None:
                 self._hip.kv_broadcast(pk, pv, P, k_bufs, v_bufs, starts=starts)
                 logits = self._hip.prefill_from(embs.contiguous(), P, k_bufs, v_bufs, starts=starts)
             else:
                 logits = self._hip.prefill(embs.contiguous(), k_bufs, v_bufs, starts=starts)
             self.decode_stats["hip_prefills"] += 1
-            self.decode_stats["hip_steps"] += self.max_new_tokens - 1
-            return self._select(logits, L, self.min_new_tokens() if eos_ids else 0, eos_ids, pad, k_bufs, v_bufs, return_logits, starts)
+            self.decode_stats["hip_steps"] += num_new - 1
+            return self._select(logits, L, self.min_new_tokens() if eos_ids else 0, eos_ids, pad, k_bufs, v_bufs, return_logits, starts,
+                                constrained=constrained)
         cache = DynamicCache(config=llm.config)
-        cache.layers = [PreallocLayer(L + self.max_new_tokens) for _ in cache.layers] or cache.layers
+        cache.layers = [PreallocLayer(L + num_new) for _ in cache.layers] or cache.layers
         pos = torch.arange(L, device=embs.device).unsqueeze(0)
         out = llm(inputs_embeds=embs, position_ids=pos, past_key_values=cache, use_cache=True, logits_to_keep=1)
         logits = out.logits[:, -1, :].float()
@@ -737,9 +844,9 @@ class MiniGPT4Classifier:
                 self._eos_mask = (key, m.to(embs.device))
         if self._hip is not None:                                      # decode = "hip": the loop below, in this library's kernels
             assert B <= self.max_batch, f"{B} rows > max_batch {self.max_batch} (the native decoder's workspace)"
-            self.decode_stats["hip_steps"] += self.max_new_tokens - 1
+            self.decode_stats["hip_steps"] += num_new - 1
             return self._select(logits.contiguous(), L, min_new, eos_ids, pad, [l.buf_k for l in cache.layers],
-                                [l.buf_v for l in cache.layers], return_logits)
+                                [l.buf_v for l in cache.layers], return_logits, constrained=constrained)
         unfinished = torch.ones(B, dtype=torch.long, device=embs.device)
         tokens, step_logits = [], []
         for i in range(self.max_new_tokens):
@@ -767,7 +874,7 @@ class MiniGPT4Classifier:
             return torch.stack(tokens, dim=1), torch.stack(step_logits, dim=1)
         return torch.stack(tokens, dim=1)
 
-    def _graph_key(self, embs, ragged=False, prefix=0):
+    def _graph_key(self, embs, ragged=False, prefix=0, constrained=False):
         key = (embs.shape[0], embs.shape[1], embs.dtype, embs.device.index, self.max_new_tokens, bool(self.routed_linears), self.decode,
                self.prefill)
         key = key + ("ragged",) if ragged else key                    # a graph of the _ragged entries is never an unpadded one's
@@ -775,6 +882,8 @@ class MiniGPT4Classifier:
         key = key + ("grouped_kv",) if self.grouped_kv else key
         key = key + ("early_stop",) if self.early_stop else key       # nor is one captured with early stop on one captured without
         key = key + ("stop", self.stop_words_ids) if self.stop_words_ids else key      # nor under one set of stop sequences another's
+        if constrained:                                               # nor the trie select under one trie another's, or the arg-max's
+            return key + ("constrained", self.trie.depth, id(self.trie))
         settings = self._sample_settings()
         return key + ("sample", settings) if settings is not None else key             # nor the sampler under one law another's
 
@@ -786,7 +895,7 @@ class MiniGPT4Classifier:
             raise RuntimeError('last_live_steps: no native engine (decode="hip") on this classifier')
         return self._hip.live_steps()
 
-    def _generate_graph(self, embs, starts=None, prefix=None):
+    def _generate_graph(self, embs, starts=None, prefix=None, constrained=False):
         """One captured hipGraph per (batch, prompt length, dtype, device, max_new_tokens, routed prefill, engine, prefill engine), kept in an LRU of
         `max_graphs` entries: a graph pins its private pool -- the pre-allocated K / V of every layer plus activations, ~6.7 GB of K / V
         alone at 200 rows x 32 layers x 64 positions -- and ragged last batches or new prompt lengths add entries; the least recently
@@ -795,8 +904,9 @@ class MiniGPT4Classifier:
         the embeds -- the kernels read it when they run, so one graph per (batch, PADDED length) serves every mix of prompt lengths.
         prefix (shared_prefix, see greedy_tokens): the graph reads the prefix caches from static tensors of its own, which are
         refreshed before a replay only when they hold another prefix than the wanted one (the ids are compared on the host): with one
-        template for a whole dataset nothing is copied."""
-        key = self._graph_key(embs, ragged=starts is not None, prefix=prefix.P if prefix else 0)
+        template for a whole dataset nothing is copied.
+        constrained (see greedy_tokens): the static output is the pair (tokens, labels)."""
+        key = self._graph_key(embs, ragged=starts is not None, prefix=prefix.P if prefix else 0, constrained=constrained)
         entry = self._graphs.get(key)
         if entry is not None:
             self._graphs.move_to_end(key)
@@ -810,6 +920,8 @@ class MiniGPT4Classifier:
             static_starts = None if starts is None else starts.clone()
             static_prefix = None if prefix is None else prefix.clone()
             extra = {} if prefix is None else {"prefix": static_prefix}
+            if constrained:
+                extra["constrained"] = True
             side = torch.cuda.Stream(device=embs.device)
             side.wait_stream(torch.cuda.current_stream())
             import contextlib
@@ -848,10 +960,10 @@ class MiniGPT4Classifier:
         graph.replay()
         self.decode_stats["graph_replays"] += 1
         if self._hip is not None:
-            self.decode_stats["hip_steps"] += self.max_new_tokens - 1
+            self.decode_stats["hip_steps"] += (self.trie.depth if constrained else self.max_new_tokens) - 1
         if self.prefill == "hip":
             self.decode_stats["hip_prefills"] += 1
-        return static_out.clone()
+        return tuple(t.clone() for t in static_out) if constrained else static_out.clone()
 
     @torch.no_grad()
     def generate(self, images, texts, **_ignored):
@@ -1031,17 +1143,49 @@ class MiniGPT4Classifier:
     def _classify_embeds(self, emb, device, draws=None):
         """One classifier batch from encode_img's output -> (logits [B, num_classes] on `device`, the rows' answer texts).
         classify="generate": one-hot of the generated answer's class.  classify="multi_select": -loss of candidate i in column i,
-        -inf in column `other_id` (and in unused columns), so the top class is always a candidate."""
+        -inf in column `other_id` (and in unused columns), so the top class is always a candidate.  classify="constrained": one-hot
+        of the candidate the row spelled."""
         if self.classify == "generate":
             # the keyword travels only where it says something (sample = "hip"): subclasses that replace generate_from_embeds keep working
             kw = {"draws": draws} if draws is not None and self.sample == "hip" else {}
             answers = self.generate_from_embeds(emb, self.prompt, **kw)
             return self.label_map.one_hot_logits(answers, device), answers
+        if self.classify == "constrained":
+            labels, _ = self.constrained_from_embeds(emb, self.prompt)
+            if self.constrain == "hip" and self.activations == "int8":  # the labels are read next: the same sync
+                self.last_act_stats()
+            return torch.nn.functional.one_hot(labels.long(), self.num_classes).float().to(device), self._label_texts(labels)
         losses = self.answer_losses_from_embeds(emb, self.prompt, self.candidates)
         logits = torch.full((losses.shape[0], self.num_classes), float("-inf"), dtype=torch.float32, device=losses.device)
         logits[:, :losses.shape[1]] = -losses
         answers = [self.candidates[i] for i in losses.argmin(dim=1).tolist()]
         return logits.to(device), answers
+
+    def _label_texts(self, labels):
+        """The candidates' texts of device labels (ONE host read)."""
+        return [self.candidates[i] for i in labels.tolist()]
+
+    def _constrained_counts(self, x, ranges, batch_size, sigma, seed, law):
+        """constrain = "hip": the draws of `ranges` = [(first index, count, counts row), ...] -- contiguous index ranges -- in common
+        classifier batches.  Per batch: encode_img_noisy -> graph replay -> vote_labels on the device labels; nothing is read back
+        until the last batch is enqueued, then ONE host read of the kept labels fills `last_answers`."""
+        bs = max(1, min(int(batch_size), self.max_batch))
+        first, total, done, kept = ranges[0][0], sum(n for _, n, _ in ranges), 0, []
+        while done < total:
+            nb = min(bs, total - done)
+            emb = self._encode_noisy(x, first + done, nb, sigma, seed, law)
+            labels, _ = self.constrained_from_embeds(emb, self.prompt)
+            lo, at = 0, 0                                              # rows of this batch, range by range
+            for _, n, counts in ranges:
+                hi = max(lo, min(nb, at + n - done))
+                if hi > lo:
+                    vote_labels(labels[lo:hi], counts)
+                lo, at = hi, at + n
+            kept.append(labels)
+            done += nb
+        if self.activations == "int8":                                  # the labels are read next: the same sync
+            self.last_act_stats()
+        self.last_answers = self._label_texts(torch.cat(kept)) if kept else []
 
     def __call__(self, images):
         out = []
@@ -1061,6 +1205,9 @@ class MiniGPT4Classifier:
         if first_b != first_a + num_a:                                 # not one contiguous index range: two passes
             self.sample_counts(x, first_a, num_a, batch_size, sigma, seed, counts[0], law=law)
             self.sample_counts(x, first_b, num_b, batch_size, sigma, seed, counts[1], law=law)
+            return counts
+        if self.classify == "constrained" and self.constrain == "hip":
+            self._constrained_counts(x, [(first_a, num_a, counts[0]), (first_b, num_b, counts[1])], batch_size, sigma, seed, law)
             return counts
         bs = max(1, min(int(batch_size), self.max_batch))
         total, done, answers = num_a + num_b, 0, []
@@ -1087,6 +1234,9 @@ class MiniGPT4Classifier:
     def sample_counts(self, x, first_sample, num, batch_size, sigma, seed, counts=None, law="gaussian"):
         if counts is None:
             counts = torch.zeros(self.num_classes, dtype=torch.int64, device=x.device)
+        if self.classify == "constrained" and self.constrain == "hip":
+            self._constrained_counts(x, [(first_sample, num, counts)], batch_size, sigma, seed, law)
+            return counts
         bs = max(1, min(int(batch_size), self.max_batch))
         done = 0
         while done < num:

@@ -189,6 +189,10 @@ cgpt_status cgpt_rgf_step(const float* x_adv_dev, const float* x_clean_dev, int6
                           const float* coeffs_host, float lr, float eps, uint64_t noise_seed, float* out_dev, void* stream);
 /* smoothing.py:97-98,101-105: counts_dev[argmax(logits[b,:])] += 1 for b < num (first max index on ties). */
 cgpt_status cgpt_vote(const float* logits_dev, int64_t num, int32_t num_classes, int64_t* counts_dev, void* stream);
+/* counts_dev[labels_dev[i]] += 1 for i < num: the vote of rows whose class is already known on the device (int32 labels, the
+ * labels_out_dev of cgpt_llm_constrained), into the int64 histogram cgpt_vote fills, with 64-bit atomics.  A label outside
+ * 0 .. num_classes-1 is not counted.  Enqueues only. */
+cgpt_status cgpt_vote_labels(const int32_t* labels_dev, int64_t num, int32_t num_classes, int64_t* counts_dev, void* stream);
 
 /* ---- the one collective of the path, for callers that are not Python (Python callers use torch.distributed, whose "nccl"
  *      backend IS RCCL on ROCm): in-place sum over all ranks of the int64 vote histograms a cgpt_sample_counts* call produced
@@ -707,6 +711,52 @@ cgpt_status cgpt_llm_sample_logits(const float* logits_dev, int64_t ld, int32_t 
                                    const int64_t* draw_ids_dev, const uint64_t* seed_dev, const float* uniforms_in_dev,
                                    int64_t* tokens_out_dev, float* uniforms_out_dev, int32_t* kept_count_out_dev,
                                    float* kept_mass_out_dev, void* stream);
+
+/* ---- Trie-constrained answer decoding: the greedy entries with the arg-max restricted to a vocabulary of candidate answers ----
+ * Replaces: HF `generate(..., prefix_allowed_tokens_fn=...)`, greedy, over the token sequences of C candidate answers: at every select
+ * the arg-max runs over the tokens that continue some candidate, a row finishes when it has spelled a whole candidate, and its class
+ * id is then known on the device (`constrained_select_law` in llm_laws.py is the law).
+ * The candidates are a CSR trie of int32 tables: node 0 is the root; the edges of node n are child_begin[n] .. child_begin[n + 1];
+ * edge e carries token child_tok[e] and leads to node child_node[e]; leaf_class[n] is the class id (>= 0) of a leaf and -1 on an
+ * inner node.  Nodes are numbered breadth-first (child_node[e] == e + 1, so a child's index is greater than its parent's) and the
+ * edges of one node ascend STRICTLY by token id: "the first maximum over the edges" is "the lowest token id among the maxima".
+ * cgpt_llm_trie_check: host only, no handle, no GPU.  CGPT_OK and *depth_out (may be NULL) = the longest candidate, or
+ * CGPT_ERR_INVALID with a message naming the first offending node for: a null table, nodes outside 3 .. 2^20, edges != nodes - 1,
+ * child_begin not monotone from 0 to child_begin[nodes] == edges, a token outside 0 .. vocab-1, edge tokens not strictly ascending, a
+ * child index not above its parent's or out of range or not breadth-first, a node with two parents or none, a leaf with a class < 0,
+ * an inner node with a class other than -1 (a candidate that is a prefix of another), fewer than 2 leaves, depth > 32.
+ * cgpt_llm_set_trie: validates the host tables with that check (vocab = the handle's) and copies them to the device.  Handle state,
+ * read when a constrained call ENQUEUES (as cgpt_llm_set_stop_sequences is): a captured call keeps the tables it was captured under,
+ * so replaced tables stay allocated until cgpt_llm_destroy.  SYNCHRONISES and allocates: call it outside any capture.  nodes = 0
+ * clears it (the table pointers are then ignored).  A refused call leaves the handle as it was.
+ * cgpt_llm_constrained / cgpt_llm_constrained_ragged: cgpt_llm_greedy / cgpt_llm_greedy_ragged without min_new and the EOS ids, the
+ * select replaced: num_new selects with num_new - 1 token steps between them, num_new == the trie's depth, so every row reaches a
+ * leaf.  tokens_out_dev [B, num_new] int64: the row's candidate, then pad_id.  labels_out_dev [B] int32: leaf_class of the leaf each
+ * row reached (every entry is written).  step_logits_out_dev (or NULL) [B, num_new, vocab] fp32: row i = the RAW logits select i
+ * read.  Logits are finite by contract.  Early stop (a row is finished at its leaf), grouped K/V, int8 weights and activations and
+ * left padding are the token step's and hold unchanged; cgpt_llm_live_steps reports these calls too.  The greedy and sampling entries
+ * launch exactly what they launched before these existed.  CGPT_ERR_INVALID before any launch, besides the greedy entries' rules:
+ * no trie set on the handle, num_new != the trie's depth, a null labels_out_dev.
+ * cgpt_llm_trie_select_logits: one select alone, without a handle, on the current device: logits_dev [B, V] fp32 (rows ld apart),
+ * the four tables as DEVICE pointers (trusted: pass tables cgpt_llm_trie_check accepted), node_dev / unfinished_dev [B] int32 read and
+ * written as the engine's own are (a row holding unfinished 0, or standing on a leaf, gets pad_id and nothing else is written for it;
+ * a node outside 0 .. nodes-1 reads as the root), tokens_out_dev [B] int64, labels_out_dev [B] int32 written for the rows that reach
+ * a leaf in this select. */
+cgpt_status cgpt_llm_trie_check(const int32_t* child_begin, const int32_t* child_tok, const int32_t* child_node,
+                                const int32_t* leaf_class, int32_t nodes, int32_t edges, int32_t vocab, int32_t* depth_out);
+cgpt_status cgpt_llm_set_trie(cgpt_llm_handle h, const int32_t* child_begin, const int32_t* child_tok, const int32_t* child_node,
+                              const int32_t* leaf_class, int32_t nodes, int32_t edges);
+cgpt_status cgpt_llm_constrained(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len, int32_t num_new,
+                                 int64_t pad_id, void* const* k_ptrs_host, void* const* v_ptrs_host, int64_t kv_len_stride,
+                                 int64_t* tokens_out_dev, float* step_logits_out_dev, int32_t* labels_out_dev, void* stream);
+cgpt_status cgpt_llm_constrained_ragged(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t prompt_len,
+                                        const int32_t* starts_dev, int32_t num_new, int64_t pad_id, void* const* k_ptrs_host,
+                                        void* const* v_ptrs_host, int64_t kv_len_stride, int64_t* tokens_out_dev,
+                                        float* step_logits_out_dev, int32_t* labels_out_dev, void* stream);
+cgpt_status cgpt_llm_trie_select_logits(const float* logits_dev, int64_t ld, int32_t B, int32_t V, const int32_t* child_begin_dev,
+                                        const int32_t* child_tok_dev, const int32_t* child_node_dev, const int32_t* leaf_class_dev,
+                                        int32_t nodes, int64_t pad_id, int32_t* node_dev, int32_t* unfinished_dev,
+                                        int64_t* tokens_out_dev, int32_t* labels_out_dev, void* stream);
 
 #ifdef __cplusplus
 }
