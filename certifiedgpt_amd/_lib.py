@@ -153,6 +153,10 @@ SIGNATURES = {
     "cgpt_llm_constrained": (_I32, [_P, _P, _I32, _I32, _I32, _I64, _P, _P, _I64, _P, _P, _P, _P]),
     "cgpt_llm_constrained_ragged": (_I32, [_P, _P, _I32, _I32, _P, _I32, _I64, _P, _P, _I64, _P, _P, _P, _P]),
     "cgpt_llm_trie_select_logits": (_I32, [_P, _I64, _I32, _I32, _P, _P, _P, _P, _I32, _I64, _P, _P, _P, _P, _P]),
+    "cgpt_llm_beam_reserve": (_I32, [_P, _I32, _I32, _I32]),
+    "cgpt_llm_beam_step": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _P, _I64, _P, _P, _I64, _P, _P, _I64, _P, _P]),
+    "cgpt_llm_beam_select_logits": (_I32, [_P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _I64, _F] + [_P] * 18 + [_P]),
+    "cgpt_llm_beam": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _I64, _F, _P, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

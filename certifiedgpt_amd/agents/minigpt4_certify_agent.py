@@ -36,6 +36,8 @@ Config (a plain dict or any mapping; the reference's YAMLs define no smoothing k
             #          also: classify: "constrained" (the greedy decode restricted to `answers` through a token trie: as many tokens as the
             #          longest answer + end_sym has, whatever the number of answers; every noisy copy votes for one of them),
             #          constrain: "hf" | "hip" (who runs it; "hip" needs decode "hip" and votes from device labels, no per-batch read)
+            #          also: beams: "hf" | "hip" with num_beams: 2..8 and length_penalty (beam search on the native engine: one prompt
+            #          cache per image, an ancestry table instead of reorder_cache; needs decode and prefill "hip")
             mode: vit_head | encode_img, weights: <path to a torch state_dict saved with torch.save> | null, dims: {...},
             partial_weights: false}   # true: load what the checkpoint has on top of the synthetic initialisation
     data:  {num_images: 10, seed: 1234}      # synthetic CLIP-normalised images unless `dataset` is passed to the agent
@@ -224,7 +226,9 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
                   same answers; needs decode and prefill "hip");
                   sample: "hf" | "hip" (who decodes a sampled call; "hip" needs decode "hip") and the generation fields do_sample,
                   temperature, top_k, top_p, repetition_penalty (handed to the classifier's generate_kwargs where present;
-                  `Chat.answer`: do_sample True, top_p 0.9, repetition_penalty 1.05, temperature 1.0)"""
+                  `Chat.answer`: do_sample True, top_p 0.9, repetition_penalty 1.05, temperature 1.0);
+                  beams: "hf" | "hip" (who decodes a call with num_beams > 1; "hip" needs decode and prefill "hip") and the generation
+                  fields num_beams (2..8 on the native engine) and length_penalty, handed over likewise"""
     from ..minigpt4 import MiniGPT4Classifier
     from .label_adapter import AnswerLabelMap
     if llama_model is None:
@@ -249,7 +253,8 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
                          f"{num_classes} leaves room for {num_classes - 1} (the last class id is \"other\"): raise num_classes "
                          "or shorten the vocabulary -- truncating it would move real answers into the non-certifiable bucket")
     label_map = AnswerLabelMap(num_classes, answers, frozen=True)
-    fields = {k: gen_cfg[k] for k in ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty") if k in gen_cfg}
+    fields = {k: gen_cfg[k] for k in ("do_sample", "temperature", "top_k", "top_p", "repetition_penalty", "num_beams", "length_penalty")
+              if k in gen_cfg}
     return MiniGPT4Classifier(encoder, llama_model, tokenizer, prompt, label_map,
                               max_new_tokens=int(gen_cfg.get("max_new_tokens", 20)), max_batch=encoder.max_batch,
                               decode=gen_cfg.get("decode", "hf"), prefill_linear=gen_cfg.get("prefill_linear", "torch"),
@@ -261,7 +266,7 @@ def build_generating_classifier(encoder, gen_cfg, num_classes, tokenizer=None, l
                               int8_threshold=gen_cfg.get("int8_threshold", 6.0), outlier_cap=gen_cfg.get("outlier_cap", 64),
                               stop_words_ids=gen_cfg.get("stop_words_ids"), stop_text=gen_cfg.get("stop_text"),
                               sample=gen_cfg.get("sample", "hf"), shared_prefix=gen_cfg.get("shared_prefix", False),
-                              constrain=gen_cfg.get("constrain", "hf"),
+                              constrain=gen_cfg.get("constrain", "hf"), beams=gen_cfg.get("beams", "hf"),
                               generate_kwargs=fields or None)
 
 

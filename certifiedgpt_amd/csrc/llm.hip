@@ -34,6 +34,7 @@
 #include "../../include/cgpt.h"
 #include "common_host.h"
 #include "llm.h"
+#include "llm_beam.h"
 #include "llm_select.h"
 
 using namespace cgpt;
@@ -556,6 +557,11 @@ struct cgpt_llm {
     const int *t_begin = nullptr, *t_tok = nullptr, *t_node = nullptr, *t_leaf = nullptr;
     int t_nodes = 0, t_depth = 0;
     int* trie_node = nullptr;              // [max_batch]: the trie node every row of the running constrained call stands on
+    // beam search (cgpt_llm_beam_reserve): the two state sets the selects of a beam call alternate between (select i reads set i & 1
+    // and writes the other), for bm_rows beam rows and bm_elems = rows x num_new token / ancestry entries.  Replaced sets stay in `allocs`.
+    int64_t bm_rows = 0, bm_elems = 0;
+    BeamState bm[2]{};
+    int32_t* bm_parents = nullptr;
     std::set<std::string> loaded;
     size_t expected = 0;
     std::vector<void*> allocs;
@@ -632,9 +638,16 @@ cgpt_status gemm(cgpt_llm* m, int epi, const half_t* A, int K, const Mat& W, int
 // One token step on rows 0..B-1: tokens -> logits (fp32, row stride ld_logits).
 // starts (device, or null): per-row left padding, clamped into 0 .. smax, see llm_attn_kernel.
 // GUARD: every launch is the guarded instantiation on m->live (a greedy call with early stop on); otherwise the plain kernels.
+// beam != null (a beam step, plain handles without GUARD only): the B rows are images x k beam rows, kp / vp / len_stride are the BEAM
+// caches, pos = L + t, and the attention is llm_attn_beam_kernel on the prompt caches and the ancestry table `beam` names.
+struct BeamStep {
+    void* const* pk; void* const* pv; int64_t prompt_stride;
+    const int32_t* anc; int64_t ld_anc;
+    int k, L, t;
+};
 template <bool GUARD>
 cgpt_status run_step(cgpt_llm* m, const long long* tokens, int B, int pos, const int32_t* starts, int smax, void* const* kp, void* const* vp,
-                     int64_t len_stride, float* logits, int64_t ld_logits, hipStream_t st) {
+                     int64_t len_stride, float* logits, int64_t ld_logits, hipStream_t st, const BeamStep* beam = nullptr) {
     const LlmCfg& c = m->cfg;
     const int H = c.hidden, NQ = qkv_width(c);
     const int* live = GUARD ? m->live : nullptr;
@@ -646,7 +659,11 @@ cgpt_status run_step(cgpt_llm* m, const long long* tokens, int B, int pos, const
         hipLaunchKernelGGL(llm_rmsnorm_kernel<GUARD>, dim3(B), dim3(256), 0, st, m->h, L.ln1, H, c.rms_eps, m->xn, live);
         LAUNCHED();
         CGCHK(gemm(m, DEC_F16, m->xn, H, L.wqkv, NQ, m->qkv, NQ, nullptr, B, st, live));
-        if (c.grouped_kv) {
+        if (beam) {
+            BeamAttnArgs a{m->qkv, H, c.heads, beam->k, (const half_t*)beam->pk[l], (const half_t*)beam->pv[l], beam->prompt_stride,
+                           (half_t*)kp[l], (half_t*)vp[l], len_stride, beam->anc, beam->ld_anc, m->rope, beam->L, beam->t, B, m->attn};
+            HIPCHK(launch_llm_beam_attn(a, st));
+        } else if (c.grouped_kv) {
             half_t *Kl = (half_t*)kp[l], *Vl = (half_t*)vp[l];
             switch (c.heads / c.kv_heads) {
                 case 1: gqa_attn_launch<1, GUARD>(m->qkv, H, c.kv_heads, B, Kl, Vl, len_stride, m->rope, pos, m->attn, starts, smax, live, st); break;
@@ -1250,6 +1267,141 @@ cgpt_status cgpt_llm_constrained_ragged(cgpt_llm_handle h, const float* first_lo
     return llm_greedy_entry("cgpt_llm_constrained_ragged", h, first_logits_dev, B, prompt_len, starts_dev, num_new, 0, nullptr, 0, pad_id,
                             k_ptrs_host, v_ptrs_host, kv_len_stride, tokens_out_dev, step_logits_out_dev, stream, nullptr, nullptr, nullptr,
                             true, labels_out_dev);
+}
+
+// ---- beam search (llm_beam.hip; include/cgpt.h: "Beam search")
+cgpt_status cgpt_llm_beam_reserve(cgpt_llm_handle h, int32_t max_images, int32_t k, int32_t num_new) {
+    const std::string who = "cgpt_llm_beam_reserve";
+    if (!h) return cgpt_fail(CGPT_ERR_INVALID, who + ": null handle");
+    if (k < BEAM_MIN || k > BEAM_MAX)
+        return cgpt_fail(CGPT_ERR_INVALID, who + ": num_beams " + std::to_string(k) + " outside " + std::to_string(BEAM_MIN) + ".." +
+                                               std::to_string(BEAM_MAX));
+    if (max_images < 1 || (int64_t)max_images * k > h->cfg.max_batch)
+        return cgpt_fail(CGPT_ERR_INVALID, who + ": " + std::to_string(max_images) + " images x " + std::to_string(k) +
+                                               " beams outside 1..max_batch = " + std::to_string(h->cfg.max_batch) + " rows");
+    if (num_new < 1 || num_new > h->cfg.max_len) return cgpt_fail(CGPT_ERR_INVALID, who + ": num_new outside 1..max_len");
+    const int64_t rows = (int64_t)max_images * k, elems = rows * num_new;
+    if (rows <= h->bm_rows && elems <= h->bm_elems) return CGPT_OK;    // grows only; a second call with the same sizes does nothing
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const size_t R = (size_t)std::max(rows, h->bm_rows), E = (size_t)std::max(elems, h->bm_elems);
+    BeamState fresh[2]{};                                              // complete before it takes the old sets' place
+    for (BeamState& s : fresh) {
+        CGCHK(dev_zalloc(h, R * sizeof(float), (void**)&s.running));
+        CGCHK(dev_zalloc(h, E * sizeof(long long), (void**)&s.tokens));
+        CGCHK(dev_zalloc(h, E * sizeof(int32_t), (void**)&s.anc));
+        CGCHK(dev_zalloc(h, R * sizeof(float), (void**)&s.pool_score));
+        CGCHK(dev_zalloc(h, R * sizeof(int32_t), (void**)&s.pool_fin));
+        CGCHK(dev_zalloc(h, R * sizeof(int32_t), (void**)&s.pool_len));
+        CGCHK(dev_zalloc(h, E * sizeof(long long), (void**)&s.pool_seq));
+        CGCHK(dev_zalloc(h, R * sizeof(int32_t), (void**)&s.open));
+    }
+    int32_t* parents = nullptr;
+    CGCHK(dev_zalloc(h, R * sizeof(int32_t), (void**)&parents));
+    HIPCHK(hipDeviceSynchronize());
+    h->bm[0] = fresh[0]; h->bm[1] = fresh[1]; h->bm_parents = parents;
+    h->bm_rows = (int64_t)R; h->bm_elems = (int64_t)E;
+    return CGPT_OK;
+}
+
+// The checks a beam step and the beam loop share: the handle, the rows, both cache sets.  last_t: the last generated position appended.
+static cgpt_status beam_check(const std::string& who, cgpt_llm_handle h, int32_t B, int32_t k, int32_t L, int32_t last_t, bool steps,
+                              void* const* pk, void* const* pv, int64_t prompt_stride, void* const* bk, void* const* bv, int64_t beam_stride) {
+    if (h->cfg.grouped_kv) return cgpt_fail(CGPT_ERR_INVALID, who + ": a grouped_kv handle is not supported (beam search runs on plain handles)");
+    if (k < BEAM_MIN || k > BEAM_MAX)
+        return cgpt_fail(CGPT_ERR_INVALID, who + ": num_beams " + std::to_string(k) + " outside " + std::to_string(BEAM_MIN) + ".." +
+                                               std::to_string(BEAM_MAX));
+    if (B < 1 || (int64_t)B * k > h->cfg.max_batch)
+        return cgpt_fail(CGPT_ERR_INVALID, who + ": B * num_beams = " + std::to_string(B) + " * " + std::to_string(k) + " outside 1..max_batch = " +
+                                               std::to_string(h->cfg.max_batch));
+    if (L < 1 || last_t < 0 || (int64_t)L + last_t >= h->cfg.max_len)
+        return cgpt_fail(CGPT_ERR_INVALID, who + ": prompt_len >= 1, t >= 0 and prompt_len + t < max_len are required");
+    if (!pk || !pv) return cgpt_fail(CGPT_ERR_INVALID, who + ": null prompt K/V pointer table");
+    if (L > prompt_stride) return cgpt_fail(CGPT_ERR_INVALID, who + ": prompt_len exceeds prompt_stride");
+    for (int l = 0; l < h->cfg.layers; ++l)
+        if (!pk[l] || !pv[l]) return cgpt_fail(CGPT_ERR_INVALID, who + ": null prompt K/V buffer");
+    if (steps) {
+        if (!bk || !bv) return cgpt_fail(CGPT_ERR_INVALID, who + ": null beam K/V pointer table");
+        if (last_t >= beam_stride) return cgpt_fail(CGPT_ERR_INVALID, who + ": generated position outside the beam cache (beam_stride)");
+        for (int l = 0; l < h->cfg.layers; ++l)
+            if (!bk[l] || !bv[l]) return cgpt_fail(CGPT_ERR_INVALID, who + ": null beam K/V buffer");
+    }
+    return CGPT_OK;
+}
+
+cgpt_status cgpt_llm_beam_step(cgpt_llm_handle h, const int64_t* tokens_dev, int32_t B, int32_t k, int32_t prompt_len, int32_t t,
+                               const int32_t* anc_dev, int64_t anc_ld, void* const* prompt_k_ptrs_host, void* const* prompt_v_ptrs_host,
+                               int64_t prompt_stride, void* const* beam_k_ptrs_host, void* const* beam_v_ptrs_host, int64_t beam_stride,
+                               float* logits_dev, void* stream) {
+    const std::string who = "cgpt_llm_beam_step";
+    if (!h || !tokens_dev || !logits_dev || !anc_dev) return cgpt_fail(CGPT_ERR_INVALID, who + ": null argument");
+    if (anc_ld < t) return cgpt_fail(CGPT_ERR_INVALID, who + ": anc_ld < t");
+    CGCHK(beam_check(who, h, B, k, prompt_len, t, true, prompt_k_ptrs_host, prompt_v_ptrs_host, prompt_stride, beam_k_ptrs_host,
+                     beam_v_ptrs_host, beam_stride));
+    CGCHK(ready(h, who.c_str()));
+    HIPCHK(hipSetDevice(h->cfg.device));
+    const BeamStep bs{prompt_k_ptrs_host, prompt_v_ptrs_host, prompt_stride, anc_dev, anc_ld, k, prompt_len, t};
+    return run_step<false>(h, (const long long*)tokens_dev, B * k, prompt_len + t, nullptr, 0, beam_k_ptrs_host, beam_v_ptrs_host, beam_stride,
+                           logits_dev, h->cfg.vocab, (hipStream_t)stream, &bs);
+}
+
+cgpt_status cgpt_llm_beam(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t k, int32_t prompt_len, int32_t num_new,
+                          int32_t min_new, const int64_t* eos_ids_host, int32_t num_eos, int64_t pad_id, float length_penalty,
+                          void* const* prompt_k_ptrs_host, void* const* prompt_v_ptrs_host, int64_t prompt_stride,
+                          void* const* beam_k_ptrs_host, void* const* beam_v_ptrs_host, int64_t beam_stride, int64_t* tokens_out_dev,
+                          float* scores_out_dev, float* step_logits_out_dev, float* trace_out_dev, void* stream) {
+    const std::string who = "cgpt_llm_beam";
+    if (!h || !first_logits_dev || !tokens_out_dev) return cgpt_fail(CGPT_ERR_INVALID, who + ": null argument");
+    if (num_new < 1 || min_new < 0 || num_eos < 0 || num_eos > MAX_EOS || (num_eos > 0 && !eos_ids_host))
+        return cgpt_fail(CGPT_ERR_INVALID, who + ": bad lengths (num_new >= 1, min_new >= 0; at most 8 EOS ids)");
+    if (!(length_penalty == length_penalty) || fabsf(length_penalty) == INFINITY)
+        return cgpt_fail(CGPT_ERR_INVALID, who + ": length_penalty is not finite");
+    CGCHK(beam_check(who, h, B, k, prompt_len, num_new > 1 ? num_new - 2 : 0, num_new > 1, prompt_k_ptrs_host, prompt_v_ptrs_host,
+                     prompt_stride, beam_k_ptrs_host, beam_v_ptrs_host, beam_stride));
+    const int V = h->cfg.vocab, K = std::max(2, 1 + num_eos) * k;
+    if (V < K + num_eos || V > BEAM_MAX_VOCAB)           // K unmasked columns in beam 0's row: the -1e9 beams never enter select 0's top K
+        return cgpt_fail(CGPT_ERR_INVALID, who + ": the vocabulary must hold K + num_eos columns, K = max(2, 1 + num_eos) * num_beams = " +
+                                               std::to_string(K) + ", and at most " + std::to_string(BEAM_MAX_VOCAB));
+    if (h->early_stop) return cgpt_fail(CGPT_ERR_STATE, who + ": early stop is set on the handle (beam search runs every step)");
+    if (h->stop.n > 0) return cgpt_fail(CGPT_ERR_STATE, who + ": stop sequences are set on the handle (beam search finishes on EOS ids only)");
+    const int rows = B * k;
+    if (rows > h->bm_rows || (int64_t)rows * num_new > h->bm_elems)
+        return cgpt_fail(CGPT_ERR_STATE, who + ": the beam state is not reserved for " + std::to_string(B) + " images x " + std::to_string(k) +
+                                             " beams x " + std::to_string(num_new) + " tokens (cgpt_llm_beam_reserve)");
+    CGCHK(ready(h, who.c_str()));
+    HIPCHK(hipSetDevice(h->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    BeamSelectArgs a{};
+    a.vocab = V; a.k = k; a.keep = K; a.n = num_new; a.pad = pad_id;
+    a.eos.n = num_eos;
+    for (int e = 0; e < num_eos; ++e) a.eos.id[e] = eos_ids_host[e];
+    a.next_tok = h->tok;
+    a.parents = h->bm_parents;
+    const int64_t ld_out = (int64_t)num_new * V;
+    h->last_on = 0;
+    h->off_steps = num_new - 1;
+    for (int i = 0; i < num_new; ++i) {
+        if (i == 0 && step_logits_out_dev) HIPCHK(launch_llm_beam_spread(first_logits_dev, V, step_logits_out_dev, ld_out, V, rows, k, st));
+        if (step_logits_out_dev) { a.src = step_logits_out_dev + (int64_t)i * V; a.lds = ld_out; a.shared = 0; }
+        else if (i == 0) { a.src = first_logits_dev; a.lds = V; a.shared = 1; }
+        else { a.src = h->logits; a.lds = V; a.shared = 0; }
+        a.step = i;
+        a.first = i == 0 ? 1 : 0;
+        a.mask_eos = (i < min_new && num_eos > 0) ? 1 : 0;
+        a.divisor = (float)pow((double)(i + 1), (double)length_penalty);
+        a.in = h->bm[i & 1];
+        a.out = h->bm[(i + 1) & 1];
+        const bool last = i + 1 == num_new;
+        a.tokens_out = last ? (long long*)tokens_out_dev : nullptr;
+        a.scores_out = last ? scores_out_dev : nullptr;
+        a.trace = trace_out_dev ? trace_out_dev + (int64_t)i * B * (5 * k + 1) : nullptr;
+        HIPCHK(launch_llm_beam_select(a, B, st));
+        if (last) break;
+        float* next = step_logits_out_dev ? step_logits_out_dev + (int64_t)(i + 1) * V : h->logits;
+        const BeamStep bs{prompt_k_ptrs_host, prompt_v_ptrs_host, prompt_stride, a.out.anc, num_new, k, prompt_len, i};
+        CGCHK(run_step<false>(h, h->tok, rows, prompt_len + i, nullptr, 0, beam_k_ptrs_host, beam_v_ptrs_host, beam_stride, next,
+                              step_logits_out_dev ? ld_out : (int64_t)V, st, &bs));
+    }
+    return CGPT_OK;
 }
 
 cgpt_status cgpt_llm_set_trie(cgpt_llm_handle h, const int32_t* child_begin, const int32_t* child_tok, const int32_t* child_node,

@@ -410,6 +410,62 @@ class _HipDecoder:
                            starts, extra=(C.c_void_p(labels.data_ptr()),))
         return (out[0], labels, out[1]) if return_logits else (out, labels)
 
+    def _beam_tables(self, B, k, prompt_k, prompt_v, beam_k, beam_v, prompt_len, beam_len):
+        """The four host pointer tables of a beam entry: prompt caches of B image rows, beam caches of B * k beam rows."""
+        assert not self.grouped_kv, "beam search runs on plain handles"
+        pk, pv, pstride = self._cache_tables(prompt_k, prompt_v, B, int(prompt_len))
+        bk, bv, bstride = self._cache_tables(beam_k, beam_v, B * k, max(1, int(beam_len)))
+        return pk, pv, pstride, bk, bv, bstride
+
+    def beam_step(self, tokens, k, prompt_len, t, anc, prompt_k, prompt_v, beam_k, beam_v):
+        """One teacher-forced beam step (cgpt_llm_beam_step): tokens [B * k] int64 at generated position t of beam rows whose image
+        prompts (prompt_len positions) sit in prompt_k / prompt_v [B, heads, ., 128] and whose generated positions sit in beam_k /
+        beam_v [B * k, heads, ., 128] under the ancestry table anc [B * k, >= t] int32 -> logits [B * k, vocab] fp32; row t of every
+        beam row's own cache appended in place."""
+        C = self._C
+        rows = int(tokens.shape[0])
+        B = rows // int(k)
+        assert rows == B * k and tokens.dtype == torch.int64 and tokens.device == self.device and tokens.is_contiguous()
+        assert (anc.dtype == torch.int32 and anc.device == self.device and anc.is_contiguous() and anc.dim() == 2
+                and anc.shape[0] == rows and anc.shape[1] >= t), (tuple(anc.shape), anc.dtype)
+        pk, pv, pstride, bk, bv, bstride = self._beam_tables(B, k, prompt_k, prompt_v, beam_k, beam_v, prompt_len, t + 1)
+        logits = torch.empty((rows, self.vocab), dtype=torch.float32, device=self.device)
+        self._lib_mod.check(self.L.cgpt_llm_beam_step(self.handle, C.c_void_p(tokens.data_ptr()), B, int(k), int(prompt_len), int(t),
+                                                      C.c_void_p(anc.data_ptr()), int(anc.shape[1]), pk, pv, pstride, bk, bv, bstride,
+                                                      C.c_void_p(logits.data_ptr()), self._stream()))
+        return logits
+
+    def beam_reserve(self, k, num_new):
+        """cgpt_llm_beam_reserve for as many images as the handle's rows hold at k beams; outside any capture, grows only."""
+        self._lib_mod.check(self.L.cgpt_llm_beam_reserve(self.handle, max(1, self.max_batch // int(k)), int(k), int(num_new)))
+
+    def beam(self, first_logits, k, prompt_len, num_new, min_new, eos_ids, pad_id, length_penalty, prompt_k, prompt_v, beam_k, beam_v,
+             return_logits=False):
+        """The beam search after the prefill (cgpt_llm_beam; `beam_decode_law`): first_logits [B, vocab] fp32 = the prefill's logits
+        of B images, prompt_k / prompt_v the caches it filled, beam_k / beam_v [B * k, heads, >= num_new - 1, 128] the beams' own ->
+        (tokens [B, num_new] int64: the best finished hypothesis, then pad ids; scores [B] fp32: its `sequences_scores`) and, with
+        return_logits, the raw logits every select read [B * k, num_new, vocab] and the state after every select [num_new, B, 5 k + 1]
+        (running, parents, tokens, pool scores, pool flags, open).  The state is reserved here (outside a capture only)."""
+        C = self._C
+        B, V = first_logits.shape
+        assert (first_logits.dtype == torch.float32 and first_logits.device == self.device and first_logits.is_contiguous()
+                and V == self.vocab and 1 <= B * k <= self.max_batch), (tuple(first_logits.shape), k, self.max_batch)
+        assert num_new >= 1 and len(eos_ids) <= 8
+        pk, pv, pstride, bk, bv, bstride = self._beam_tables(B, k, prompt_k, prompt_v, beam_k, beam_v, prompt_len, num_new - 1)
+        if not torch.cuda.is_current_stream_capturing():
+            self.beam_reserve(k, num_new)
+        tokens = torch.empty((B, num_new), dtype=torch.int64, device=self.device)
+        scores = torch.empty((B,), dtype=torch.float32, device=self.device)
+        steps = torch.empty((B * k, num_new, V), dtype=torch.float32, device=self.device) if return_logits else None
+        trace = torch.empty((num_new, B, 5 * k + 1), dtype=torch.float32, device=self.device) if return_logits else None
+        self._greedy_ran = True
+        self._lib_mod.check(self.L.cgpt_llm_beam(
+            self.handle, C.c_void_p(first_logits.data_ptr()), B, int(k), int(prompt_len), int(num_new), int(min_new),
+            (C.c_int64 * max(1, len(eos_ids)))(*[int(e) for e in eos_ids]), len(eos_ids), int(pad_id), float(length_penalty), pk, pv, pstride,
+            bk, bv, bstride, C.c_void_p(tokens.data_ptr()), C.c_void_p(scores.data_ptr()),
+            C.c_void_p(steps.data_ptr()) if return_logits else None, C.c_void_p(trace.data_ptr()) if return_logits else None, self._stream()))
+        return (tokens, scores, steps, trace) if return_logits else (tokens, scores)
+
     def set_early_stop(self, on):
         """cgpt_llm_set_early_stop: read by the next `greedy` when it enqueues; a captured call keeps what it was captured under."""
         self._lib_mod.check(self.L.cgpt_llm_set_early_stop(self.handle, int(bool(on))))

@@ -8,6 +8,7 @@
     the multi-head twin of a grouped-query decoder                               expand_kv_state_dict
     left padding and per-row candidate packing                                   left_pad_embeds, pack_row_candidates
     the trie-constrained select over a vocabulary of candidate answers           build_answer_trie, constrained_select_law, ...
+    beam search, HF 5.x `_beam_search` restated                                  beam_step_law, beam_decode_law, check_beam_settings
 
 Nothing here touches the library or a device API: torch and the standard library only (`transformers` lazily, where a law is handed
 to HF).  Dependencies point one way: llm_laws <- llm_engine <- minigpt4.
@@ -608,3 +609,165 @@ def allowed_tokens_fn(trie, pad=0):
             n = edges[n][t]
         return [int(pad)] if lc[n] >= 0 else list(edges[n].keys())
     return fn
+
+
+# ---- beam search (beams="hip"; csrc/llm_beam.hip; include/cgpt.h: "Beam search"), stated once
+BEAM_MIN, BEAM_MAX = 2, 8                                               # num_beams the native engine takes
+BEAM_NEG = -1.0e9                                                       # HF's "never chosen" score
+BEAM_FIELDS = ("num_beams", "length_penalty")
+# the fields that shape a beam search, with GenerationConfig's defaults: what `generate` resolves where call and checkpoint are silent
+BEAM_HF_DEFAULTS = {"num_beams": 1, "length_penalty": 1.0, "early_stopping": False, "num_return_sequences": 1, "num_beam_groups": 1}
+
+
+def check_beam_settings(num_beams, length_penalty=1.0, early_stopping=False, num_return_sequences=1, num_beam_groups=1,
+                        do_sample=False, repetition_penalty=1.0):
+    """(num_beams, length_penalty) as the native beam search takes them; ValueError naming the field for num_beams outside 2..8, a
+    length_penalty that is not finite, early_stopping set (True or "never"), num_return_sequences != 1, num_beam_groups != 1,
+    do_sample set or a repetition_penalty other than 1 (beam sampling and penalised beams are HF's)."""
+    if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not BEAM_MIN <= num_beams <= BEAM_MAX:
+        raise ValueError(f"num_beams={num_beams!r}: expected an int in {BEAM_MIN}..{BEAM_MAX}")
+    lp = 1.0 if length_penalty is None else length_penalty
+    if isinstance(lp, bool) or not isinstance(lp, (int, float)) or lp != lp or abs(lp) == float("inf"):
+        raise ValueError(f"length_penalty={length_penalty!r}: expected a finite number")
+    if early_stopping not in (False, None):
+        raise ValueError(f"early_stopping={early_stopping!r}: only early_stopping=False is supported")
+    if num_return_sequences not in (1, None):
+        raise ValueError(f"num_return_sequences={num_return_sequences!r}: only 1 is supported")
+    if num_beam_groups not in (1, None):
+        raise ValueError(f"num_beam_groups={num_beam_groups!r}: only 1 is supported (no group / diverse beams)")
+    if do_sample not in (False, None, 0):
+        raise ValueError(f"do_sample={do_sample!r}: beam sampling is not supported")
+    if repetition_penalty not in (1, 1.0, None):
+        raise ValueError(f"repetition_penalty={repetition_penalty!r}: a penalty cannot be combined with beams")
+    return int(num_beams), float(lp)
+
+
+def beam_keep(num_beams, num_eos):
+    """K: the candidates HF keeps per image and step, max(2, 1 + number of EOS ids) * num_beams."""
+    return max(2, 1 + int(num_eos)) * int(num_beams)
+
+
+def beam_length_divisor(i, length_penalty):
+    """What a hypothesis of i + 1 generated tokens is divided by: (i + 1) ** length_penalty in float64, rounded ONCE to fp32 -- the
+    value HF's fp32 tensor division sees and the one the select kernel is handed."""
+    return float(torch.tensor(float(i + 1) ** float(length_penalty), dtype=torch.float64).to(torch.float32))
+
+
+def _ulp32(x):
+    """Spacing of fp32 at magnitude |x| (float64 tensor in, float64 tensor out); the smallest normal spacing below that range."""
+    a = x.abs().clamp_min(2.0 ** -126)
+    return torch.exp2(torch.floor(torch.log2(a)) - 23)
+
+
+def _near(a, b, ulps):
+    """Is the pair (a, b) of float64 scores separated by more than nothing and by at most `ulps` fp32 ulp of the larger magnitude?"""
+    if not (torch.isfinite(a) and torch.isfinite(b)) or a == b:
+        return False
+    return bool((a - b).abs() <= ulps * _ulp32(torch.maximum(a.abs(), b.abs())))
+
+
+def beam_init_state(B, k, n, pad):
+    """The state of B images before select 0: running scores (0, -1e9, ...), per-beam tokens, the finished pool (scores -1e9, flags
+    false, sequences of pad ids, lengths 0) and `open`; all CPU tensors."""
+    running = torch.full((B, k), BEAM_NEG, dtype=torch.float64)
+    running[:, 0] = 0.0
+    return {"running": running, "tokens": torch.full((B, k, n), int(pad), dtype=torch.int64),
+            "pool_score": torch.full((B, k), BEAM_NEG, dtype=torch.float64), "pool_fin": torch.zeros((B, k), dtype=torch.bool),
+            "pool_seq": torch.full((B, k, n), int(pad), dtype=torch.int64), "pool_len": torch.zeros((B, k), dtype=torch.int64),
+            "open": torch.ones(B, dtype=torch.bool)}
+
+
+def beam_step_law(state, logits, i, n, min_new, eos_ids, pad, length_penalty=1.0, ulps=(2.0, 3.0)):
+    """One beam-search select, HF 5.x `_beam_search` with do_sample=False, early_stopping=False, num_return_sequences=1 and no prompt
+    ids, on the fp32 logits [B, k, V] of the k beams of B images at step i of n, evaluated in float64:
+      1. lp = l - logsumexp(l) per beam row; the EOS columns then read -inf while i < min_new (the processor runs after the
+         log-softmax, so the normaliser includes the EOS mass);   2. c = running + lp;
+      3. the top K = max(2, 1 + E) k of the flat [k V] array by value descending, then by lowest flat index j V + v;
+      4. fin_r = (token is an EOS id) or (i == n - 1);
+      5. the next running beams are the first k ranks in the order (fin ascending, rank ascending): score, parent's tokens + token;
+      6. while `open`, every rank r < k with fin_r enters the pool with score s_r / d, d = `beam_length_divisor(i, length_penalty)`; the
+         pool keeps the best k of old slots + entrants, old slots first on ties, then by rank;
+      7. open &= running'[0] / d > worst, worst = the smallest pool score when all k slots are finished, else -1e9.
+    `state` (`beam_init_state`, or a state this function returned; fp32 scores are read as float64) is not modified.  Returns the new
+    state with, besides its fields, parents [B, k] (the beam each new beam continues), next_tokens [B, k], and near [B] bool: some pair of
+    scores the select COMPARES (neighbours among the first K + 1 sorted candidates: `ulps[0]` fp32 ulp; an entrant against a pool
+    score or another entrant, and step 7: `ulps[1]`) differs by less than what fp32 arithmetic can resolve -- such an image may
+    legitimately come out differently from an fp32 evaluation."""
+    l = torch.as_tensor(logits).detach().cpu().to(torch.float64)
+    B, k, V = l.shape
+    eos = [int(e) for e in eos_ids]
+    K = beam_keep(k, len(eos))
+    # K + E columns: with the EOS columns masked, beam 0 alone still fills select 0's top K, so the -1e9 beams never enter it
+    assert V >= K + len(eos), f"vocabulary {V} < K + E = {K + len(eos)}"
+    lp = l - torch.logsumexp(l, dim=-1, keepdim=True)
+    if i < int(min_new):
+        for e in eos:
+            if 0 <= e < V:
+                lp[:, :, e] = float("-inf")
+    run = state["running"].detach().cpu().to(torch.float64)
+    c = (run[:, :, None] + lp).reshape(B, k * V)
+    d = torch.tensor(beam_length_divisor(i, length_penalty), dtype=torch.float64)
+    last = i == n - 1
+    out = {key: val.detach().cpu().clone() for key, val in state.items() if key in
+           ("running", "tokens", "pool_score", "pool_fin", "pool_seq", "pool_len", "open")}
+    out["running"] = out["running"].to(torch.float64)
+    out["pool_score"] = out["pool_score"].to(torch.float64)
+    out["parents"] = torch.zeros((B, k), dtype=torch.int64)
+    out["next_tokens"] = torch.zeros((B, k), dtype=torch.int64)
+    out["near"] = torch.zeros(B, dtype=torch.bool)
+    for b in range(B):
+        vals, idx = torch.sort(c[b], descending=True, stable=True)         # equal values keep ascending flat index
+        take = min(K + 1, k * V)
+        near = any(_near(vals[r], vals[r + 1], ulps[0]) for r in range(take - 1))
+        s, par, tok = vals[:K], (idx[:K] // V).tolist(), (idx[:K] % V).tolist()
+        fin = [bool(t in eos or last) for t in tok]
+        order = [r for r in range(K) if not fin[r]] + [r for r in range(K) if fin[r]]
+        old_tokens = state["tokens"][b]
+        for q, r in enumerate(order[:k]):
+            out["running"][b, q] = s[r]
+            out["tokens"][b, q] = old_tokens[par[r]]
+            out["tokens"][b, q, i] = tok[r]
+            out["parents"][b, q] = par[r]
+            out["next_tokens"][b, q] = tok[r]
+        if bool(state["open"][b]):
+            old_s = state["pool_score"][b].to(torch.float64)
+            merged = [(old_s[j], ("old", j)) for j in range(k)] + [(s[r] / d, ("new", r)) for r in range(k) if fin[r]]
+            for a in range(k, len(merged)):
+                near = near or any(_near(merged[a][0], merged[o][0], ulps[1]) for o in range(len(merged)) if o != a)
+            picked = sorted(range(len(merged)), key=lambda m: (-float(merged[m][0]), m))[:k]     # stable: old first, then by rank
+            for q, m in enumerate(picked):
+                score, (kind, j) = merged[m]
+                out["pool_score"][b, q] = score
+                if kind == "old":
+                    out["pool_fin"][b, q] = state["pool_fin"][b, j]
+                    out["pool_seq"][b, q] = state["pool_seq"][b, j]
+                    out["pool_len"][b, q] = state["pool_len"][b, j]
+                else:
+                    out["pool_fin"][b, q] = True
+                    out["pool_seq"][b, q] = old_tokens[par[j]]
+                    out["pool_seq"][b, q, i] = tok[j]
+                    out["pool_seq"][b, q, i + 1:] = int(pad)
+                    out["pool_len"][b, q] = i + 1
+        worst = out["pool_score"][b].min() if bool(out["pool_fin"][b].all()) else torch.tensor(BEAM_NEG, dtype=torch.float64)
+        best = out["running"][b, 0] / d
+        near = near or (bool(state["open"][b]) and _near(best, worst, ulps[1]))
+        out["open"][b] = bool(state["open"][b]) and bool(best > worst)
+        out["near"][b] = near
+    return out
+
+
+def beam_decode_law(logits_fn, B, k, n, min_new, eos_ids, pad, length_penalty=1.0, ulps=(2.0, 3.0)):
+    """The whole beam search of B images: `logits_fn(tokens [B, k, i] int64) -> logits [B, k, V]` gives the next-token logits of
+    every beam after its i generated tokens (i = 0: after the prompt alone; every beam of an image then gets the same row, and only
+    beam 0 counts).  n selects of `beam_step_law` -> (tokens [B, n] int64: pool slot 0's sequence, EOS included, then pad ids;
+    scores [B] float64: its score, HF's `sequences_scores`; near [B] bool: some select of the image compared a near-tied pair; the
+    list of the n states).  An image that is no longer `open` keeps its pool, which is why a loop of fixed length gives what HF's loop
+    gives, whose exit is global to the batch."""
+    state = beam_init_state(B, k, n, pad)
+    near = torch.zeros(B, dtype=torch.bool)
+    trace = []
+    for i in range(n):
+        state = beam_step_law(state, logits_fn(state["tokens"][:, :, :i]), i, n, min_new, eos_ids, pad, length_penalty, ulps)
+        near |= state["near"]
+        trace.append(state)
+    return state["pool_seq"][:, 0].clone(), state["pool_score"][:, 0].clone(), near, trace

@@ -35,6 +35,8 @@ from .llm_laws import (GQA_RATIOS, LAYER_LINEARS, MAX_STOP_LEN, MAX_STOP_SEQS, P
                        stop_finish_columns, stop_sequences_criteria)
 from .llm_laws import (TRIE_MAX_DEPTH, TRIE_MAX_NODES, AnswerTrie, allowed_tokens_fn, build_answer_trie,    # noqa: F401
                        constrained_decode_law, constrained_select_law, trie_walk)
+from .llm_laws import (BEAM_FIELDS, BEAM_HF_DEFAULTS, BEAM_MAX, BEAM_MIN, BEAM_NEG, beam_decode_law, beam_init_state, beam_keep,    # noqa: F401
+                       beam_length_divisor, beam_step_law, check_beam_settings)
 
 IMAGE_PLACEHOLDER = "<ImageHere>"
 
@@ -147,6 +149,7 @@ class MiniGPT4Classifier:
        :param classify: "generate" (default) | "multi_select" | "constrained" -- what the base classifier of `Smooth` does with a
                batch; see __init__
        :param constrain: "hf" (default) | "hip" (with decode="hip") -- who runs the decode of classify="constrained"; see __init__
+       :param beams: "hf" (default) | "hip" (with decode="hip" and prefill="hip") -- who decodes a call with num_beams > 1; see __init__
        :param candidates: the answers `classify="multi_select"` ranks and `classify="constrained"` decodes among (default:
                `label_map.answers`, in class-id order)
 
@@ -161,7 +164,7 @@ class MiniGPT4Classifier:
                  generate_kwargs=None, decode="hf", prefill_linear="torch", prefill="model", ragged="hf", prompt_bucket=None,
                  weights="fp16", end_sym="\n", label_smoothing=0.1, score="hf", classify="generate", candidates=None,
                  early_stop=False, grouped_kv=False, activations="fp16", int8_threshold=6.0, outlier_cap=64, stop_words_ids=None,
-                 stop_text=None, sample="hf", shared_prefix=False, constrain="hf"):
+                 stop_text=None, sample="hf", shared_prefix=False, constrain="hf", beams="hf"):
         self.encoder = encoder
         self.llama_model = llama_model
         self.llama_tokenizer = llama_tokenizer
@@ -297,6 +300,18 @@ class MiniGPT4Classifier:
         #   (cgpt_vote_labels) and read nothing back per batch.  Counted in decode_stats["hip_constrained"]; a call the engine cannot
         #   take (off the device, more rows than max_batch, per-row texts without ragged = "hip") takes the "hf" path and is counted in
         #   decode_stats["hf_constrained_fallbacks"].
+        # beams = "hip" (with decode = "hip" AND prefill = "hip" only; anything else is a ValueError): a `generate` / `__call__` /
+        #   `sample_counts` call under classify = "generate" whose generation arguments differ from the greedy ones ONLY in num_beams
+        #   (2..8) and length_penalty -- the first slider of MiniGPT-4's demo -- stays on the native engine (csrc/
+        #   llm_beam.hip; `beam_step_law` / `beam_decode_law` are the law, HF 5.x `_beam_search` restated).  The prompt is prefilled
+        #   once per IMAGE, not once per beam; the beams' generated positions live in a cache of their own and HF's reorder_cache is an
+        #   ancestry table the step attention reads, so no K/V byte moves.  The loop runs in chunks of max_batch // num_beams images,
+        #   all in the one captured graph per (batch, prompt length); counted in decode_stats["hip_beam"]; `last_beam_scores()` gives
+        #   the winners' sequences_scores.  Works with weights / activations = "int8" and shared_prefix (the prefill is untouched).
+        #   Out of scope, each a ValueError here: grouped_kv, ragged = "hip" / prompt_bucket, early_stop, stop_words_ids, and
+        #   sample = "hip" with do_sample or a penalty in the generation arguments; early_stopping, num_return_sequences > 1 and beam
+        #   groups are not among the arguments the native path reproduces and take HF `generate`.  classify = "multi_select" /
+        #   "constrained" do not generate and ignore the switch.  beams = "hf" (default): num_beams > 1 takes HF `generate`, as before.
         assert decode in ("hf", "graph", "hip") and prefill_linear in ("torch", "cgpt")
         if prefill not in ("model", "hip"):
             raise ValueError(f'prefill={prefill!r}: expected "model" or "hip"')
@@ -397,10 +412,28 @@ class MiniGPT4Classifier:
         self.grouped_kv = grouped_kv
         self.shared_prefix = shared_prefix
         self.sample = sample
+        self.beams = beams
+        self._beam_scores = None                            # `last_beam_scores`
         self._draw_next, self._draw_seed = 0, 0             # `reset_draws`: the ids and the seed of calls that name no sample index
         self._draw_bufs = None                              # (ids [max_batch] int64, seed [1] int64) on the device, made at first use
         if sample == "hip":
             self._sample_settings()                         # a ValueError for a setting the sampler refuses comes now
+        if beams not in ("hf", "hip"):
+            raise ValueError(f'beams={beams!r}: expected "hf" or "hip"')
+        if beams == "hip":                                  # every failing combination is named in ONE message
+            bad = [what for what, fails in (
+                (f'decode="hip" (got decode={decode!r})', decode != "hip"),
+                (f'prefill="hip" (got prefill={prefill!r})', prefill != "hip"),
+                ("grouped_kv=False (grouped-query handles are out of scope)", bool(grouped_kv)),
+                ('ragged="hf" (left-padded prompts are out of scope)', ragged == "hip"),
+                ("prompt_bucket=None (bucketed prompts are out of scope)", prompt_bucket is not None),
+                ("early_stop=False (a beam search runs every step)", bool(early_stop)),
+                ("stop_words_ids=None (beams finish on EOS ids only)", bool(stops)),
+            ) if fails]
+            if sample == "hip" and self._sample_settings() is not None:
+                bad.append('no do_sample=True / repetition_penalty under sample="hip" (beam sampling and penalised beams are out of scope)')
+            if bad:
+                raise ValueError('beams="hip" needs ' + "; ".join(bad))
         # the keyword reaches the engine only when it is set (as `law` reaches an encoder)
         engine_kw = {"grouped_kv": True} if grouped_kv else {}
         self.activations, self.int8_threshold, self.outlier_cap = activations, float(int8_threshold), int(outlier_cap)
@@ -444,6 +477,7 @@ class MiniGPT4Classifier:
                              "hip_constrained": 0,                # native constrained decodes (constrain = "hip"): one per call
                              "hf_constrained": 0,                 # constrained decodes through HF `generate`: one per call
                              "hf_constrained_fallbacks": 0,       # constrain = "hip" calls that took the "hf" path (see __init__)
+                             "hip_beam": 0,                       # native beam searches (beams = "hip"): one per call
                              # bytes the native engine holds for weights, scales and scratch (None without one)
                              "weight_bytes": self._hip.weight_bytes if self._hip is not None else None}
 
@@ -568,7 +602,11 @@ class MiniGPT4Classifier:
                 self._write_draws(B, draws, embs.device)
                 self.decode_stats["hip_sampled"] += 1
             # without a prefix the call is the two-argument one it always was (callers wrap this method with that signature)
+            beam = self._beam_settings() is not None                   # the graph then returns (tokens, sequences_scores)
             outputs = self._generate_graph(embs, starts, prefix) if prefix else self._generate_graph(embs, starts)
+            if beam:
+                outputs, self._beam_scores = outputs
+                self.decode_stats["hip_beam"] += 1
             if self.activations == "int8":                              # the tokens are read next: the same sync
                 self.last_act_stats()
         else:
@@ -651,12 +689,19 @@ class MiniGPT4Classifier:
         """May this call take the fixed-length greedy loop?  Only when every argument of the call AND every field of the model's own
         generation_config (which `generate` applies wherever the call is silent) is one the loop reproduces; otherwise the HF path
         runs, so the same classifier never decodes differently by `decode=`.
-        native_sampler (None: sample == "hip"): whether the sampling fields count as reproduced at any value."""
+        native_sampler (None: sample == "hip"): whether the sampling fields count as reproduced at any value.
+        beams == "hip": num_beams in 2..8 with a finite length_penalty counts as reproduced too, unless the call also samples or
+        penalises, or the call or the checkpoint sets early_stopping, num_return_sequences or num_beam_groups (`_beam_settings`)."""
         sampler = self.sample == "hip" if native_sampler is None else bool(native_sampler)
+        beam = native_sampler is None and getattr(self, "beams", "hf") == "hip" and self._beam_settings() is not None
+        if beam and self._sample_settings() is not None:
+            return False
         for key, val in self.generate_kwargs.items():
             if key not in self._GREEDY_NEUTRAL:
                 return False
             if sampler and key in SAMPLE_FIELDS:         # the native sampler takes these at any value it accepts
+                continue
+            if beam and key in BEAM_FIELDS:              # the native beam search takes these at the values `_beam_settings` accepted
                 continue
             want = self._GREEDY_NEUTRAL[key]
             if want is not None and val != want:
@@ -672,6 +717,53 @@ class MiniGPT4Classifier:
                 if val not in neutral:
                     return False
         return True
+
+    def _beam_settings(self):
+        """beams = "hip": (num_beams, length_penalty) as `generate` would resolve them -- the call's argument, else the checkpoint's
+        generation_config, else GenerationConfig's default, and so for early_stopping, num_return_sequences and num_beam_groups --
+        when they ask for 2..8 beams with a finite length penalty and nothing else, else None (one beam: the greedy entries; anything
+        `check_beam_settings` refuses, wherever it was set: HF `generate`).  None under beams = "hf"."""
+        if getattr(self, "beams", "hf") != "hip":
+            return None
+        gen = getattr(self.llama_model, "generation_config", None)
+        vals = {}
+        for key, default in BEAM_HF_DEFAULTS.items():
+            val = self.generate_kwargs.get(key)
+            val = getattr(gen, key, None) if val is None else val
+            vals[key] = default if val is None else val
+        try:
+            return check_beam_settings(**vals)
+        except ValueError:
+            return None
+
+    def last_beam_scores(self):
+        """beams = "hip": the `sequences_scores` of the last native beam search, [B] fp32 on the device (the winners' summed log
+        probabilities over length ** length_penalty).  RuntimeError when none has run."""
+        if self._beam_scores is None:
+            raise RuntimeError('last_beam_scores: no native beam search (beams="hip", num_beams > 1) has run on this classifier')
+        return self._beam_scores
+
+    def _beam_chunks(self, logits, L, beam, min_new, eos_ids, pad, k_bufs, v_bufs, return_logits):
+        """The native beam search on the prompt caches a prefill of B images left, in chunks of max_batch // num_beams images (the
+        engine's workspace holds max_batch rows): each chunk reads ITS rows of the prompt caches through offset table pointers; the
+        beam caches are allocated once, for the largest chunk, and reused in stream order."""
+        k, lp = beam
+        B, n = logits.shape[0], self.max_new_tokens
+        per = self.max_batch // k
+        if per < 1:
+            raise ValueError(f"num_beams={k} > max_batch={self.max_batch}: the native engine's workspace holds max_batch beam rows")
+        shape = (min(per, B) * k, self._hip.kv_heads, max(1, n - 1), 128)
+        bk = [logits.new_empty(shape, dtype=torch.float16) for _ in range(self._hip.layers)]
+        bv = [logits.new_empty(shape, dtype=torch.float16) for _ in range(self._hip.layers)]
+        outs = []
+        for c0 in range(0, B, per):
+            c1 = min(B, c0 + per)
+            rows = (c1 - c0) * k
+            outs.append(self._hip.beam(logits[c0:c1], k, L, n, min_new, eos_ids, pad, lp, [t[c0:c1] for t in k_bufs],
+                                       [t[c0:c1] for t in v_bufs], [t[:rows] for t in bk], [t[:rows] for t in bv],
+                                       return_logits=return_logits))
+        cat_dims = (0, 0, 0, 1)                                         # tokens, scores, step logits by row; the trace by image
+        return tuple(torch.cat([o[j] for o in outs], dim=cat_dims[j]) for j in range(len(outs[0])))
 
     def _sample_settings(self):
         """sample = "hip": (do_sample, temperature, top_k, top_p, repetition_penalty) as `generate` would resolve them -- the call's
@@ -820,7 +912,9 @@ class MiniGPT4Classifier:
             if prefix is not None:                                     # the prompt is the P shared positions + these L
                 P, pk, pv = prefix.P, prefix.k, prefix.v
                 L += P
-            k_bufs, v_bufs = self._kv_buffers(embs, B, L + num_new)                  # what PreallocLayer allocates on the other path
+            beam = None if constrained else self._beam_settings()
+            # what PreallocLayer allocates on the other path; under beams the generated positions live in the beam caches
+            k_bufs, v_bufs = self._kv_buffers(embs, B, L if beam is not None else L + num_new)
             if prefix is not None:
                 self._hip.kv_broadcast(pk, pv, P, k_bufs, v_bufs, starts=starts)
                 logits = self._hip.prefill_from(embs.contiguous(), P, k_bufs, v_bufs, starts=starts)
@@ -828,6 +922,8 @@ class MiniGPT4Classifier:
                 logits = self._hip.prefill(embs.contiguous(), k_bufs, v_bufs, starts=starts)
             self.decode_stats["hip_prefills"] += 1
             self.decode_stats["hip_steps"] += num_new - 1
+            if beam is not None:                                       # (tokens, scores[, step logits, trace]): see `_beam_chunks`
+                return self._beam_chunks(logits, L, beam, self.min_new_tokens() if eos_ids else 0, eos_ids, pad, k_bufs, v_bufs, return_logits)
             return self._select(logits, L, self.min_new_tokens() if eos_ids else 0, eos_ids, pad, k_bufs, v_bufs, return_logits, starts,
                                 constrained=constrained)
         cache = DynamicCache(config=llm.config)
@@ -884,6 +980,8 @@ class MiniGPT4Classifier:
         key = key + ("stop", self.stop_words_ids) if self.stop_words_ids else key      # nor under one set of stop sequences another's
         if constrained:                                               # nor the trie select under one trie another's, or the arg-max's
             return key + ("constrained", self.trie.depth, id(self.trie))
+        if self._beam_settings() is not None:                         # nor a beam search under one setting another's, or the arg-max's
+            return key + ("beams",) + self._beam_settings()
         settings = self._sample_settings()
         return key + ("sample", settings) if settings is not None else key             # nor the sampler under one law another's
 
@@ -963,7 +1061,7 @@ class MiniGPT4Classifier:
             self.decode_stats["hip_steps"] += (self.trie.depth if constrained else self.max_new_tokens) - 1
         if self.prefill == "hip":
             self.decode_stats["hip_prefills"] += 1
-        return tuple(t.clone() for t in static_out) if constrained else static_out.clone()
+        return tuple(t.clone() for t in static_out) if isinstance(static_out, tuple) else static_out.clone()
 
     @torch.no_grad()
     def generate(self, images, texts, **_ignored):

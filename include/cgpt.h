@@ -758,6 +758,62 @@ cgpt_status cgpt_llm_trie_select_logits(const float* logits_dev, int64_t ld, int
                                         int32_t nodes, int64_t pad_id, int32_t* node_dev, int32_t* unfinished_dev,
                                         int64_t* tokens_out_dev, int32_t* labels_out_dev, void* stream);
 
+/* ---- Beam search: the decode loop with HF's beam search in the place of the arg-max ----
+ * Replaces: HF `generate(num_beams=k, length_penalty=..., do_sample=False, early_stopping=False, num_return_sequences=1)` on
+ * `inputs_embeds` (transformers 5.x `_beam_search`), the first slider of MiniGPT-4's demo (`beam_step_law` /
+ * `beam_decode_law` in llm_laws.py are the law).  An image has k beams (2..8), E EOS ids and n = num_new; every select keeps
+ * K = max(2, 1 + E) * k candidates; vocab >= K + E is required (with the EOS columns masked, beam 0 alone fills select 0's top K, so
+ * the -1e9 beams never enter it).  Per image: running[k] scores (0, -1e9, ...), the beams' tokens, a pool
+ * of k finished hypotheses (score -1e9, flag 0) and `open` = 1.  Select i on the k beams' fp32 logits:
+ *   1. lp = l - logsumexp(l) per row (float64 normaliser, ONE fp32 rounding); EOS columns then read -inf while i < min_new;
+ *   2. c = running + lp (fp32);   3. the top K of the flat [k * vocab] array, by value descending, then lowest flat index;
+ *   4. fin = the token is an EOS id, or i == n - 1;   5. the next beams: the first k ranks in (fin ascending, rank ascending);
+ *   6. while open: every rank < k with fin enters the pool with c / fp32((i + 1) ** length_penalty) and its tokens; the pool keeps
+ *      the best k, old slots first on ties, then by rank;
+ *   7. open &= running'[0] / fp32((i + 1) ** length_penalty) > (all k slots finished ? the smallest pool score : -1e9).
+ * The result of an image is pool slot 0's tokens, EOS included, then pad_id, and its score (HF's sequences_scores).
+ * Rows: beam row r = b * k + j of image b.  Two cache sets per layer: the PROMPT cache [B, heads, prompt_stride, 128], rows
+ * 0 .. prompt_len-1 as a prefill of the B images left them (read, never written), and a BEAM cache [B * k, heads, beam_stride, 128]
+ * of generated positions only: generated step t of row r rotates at prompt_len + t, writes beam row r's cache row t (the only row
+ * written) and attends over the image's prompt rows, then cache row s of beam row anc[r][s] for s < t, then its own new key.  No K/V
+ * byte moves between beams.  A row's logits and its appended cache row are bit for bit what cgpt_llm_step gives on the physically
+ * gathered cache.  int8 weights and activations are the token step's and hold unchanged.
+ * cgpt_llm_beam_reserve: the beam state of max_images x k beam rows and num_new tokens (two sets a select alternates between).  Outside
+ * any capture; idempotent, grows only (replaced buffers stay allocated until cgpt_llm_destroy), like cgpt_llm_prefill_reserve.
+ * cgpt_llm_beam_step: ONE teacher-forced beam step (the twin of cgpt_llm_step): tokens_dev [B * k], anc_dev [B * k, anc_ld] int32
+ * (columns 0 .. t-1 read; a value outside 0 .. B*k-1 is clamped into it), logits_dev [B * k, vocab] fp32.
+ * cgpt_llm_beam_select_logits: ONE select alone, without a handle, on the current device, on the caller's logits [B * k, V] (rows ld
+ * apart) and the caller's state before (running [B k] fp32, tokens [B k, num_new] int64, anc [B k, num_new] int32, pool score [B k]
+ * fp32 / finished [B k] int32 / length [B k] int32 / tokens [B k, num_new] int64, open [B] int32); writes the state after into the
+ * second set (never in place), the next tokens [B k] int64 and the parents [B k] int32 (0 .. k-1 within the image).
+ * cgpt_llm_beam: the whole loop after the prefill: num_new selects with num_new - 1 beam steps between them.  first_logits_dev
+ * [B, vocab] = the prefill's logits, one row per image, read by select 0 for every beam (only beam 0 counts there).  tokens_out_dev
+ * [B, num_new] int64, scores_out_dev [B] fp32 (or NULL).  step_logits_out_dev (or NULL) [B * k, num_new, vocab] fp32: row (r, i) =
+ * the raw logits select i read for beam row r.  trace_out_dev (or NULL) [num_new, B, 5 k + 1] fp32: the state after select i of image
+ * b: running[k], parents[k], tokens[k], pool scores[k], pool finished flags[k], open.
+ * Enqueue only: no host sync, allocation or copy after the reserve call; capturable.  CGPT_ERR_INVALID before any launch for: a null
+ * pointer, num_beams outside 2..8, B * num_beams outside 1..max_batch (the message names both), a grouped_kv handle, vocab < K + E or
+ * > 131072, more than 8 EOS ids, a length_penalty that is not finite, positions outside either cache or max_len.  CGPT_ERR_STATE for:
+ * early stop or stop sequences set on the handle, weights not loaded, a beam state not reserved for the call. */
+cgpt_status cgpt_llm_beam_reserve(cgpt_llm_handle h, int32_t max_images, int32_t num_beams, int32_t num_new);
+cgpt_status cgpt_llm_beam_step(cgpt_llm_handle h, const int64_t* tokens_dev, int32_t B, int32_t num_beams, int32_t prompt_len, int32_t t,
+                               const int32_t* anc_dev, int64_t anc_ld, void* const* prompt_k_ptrs_host, void* const* prompt_v_ptrs_host,
+                               int64_t prompt_stride, void* const* beam_k_ptrs_host, void* const* beam_v_ptrs_host, int64_t beam_stride,
+                               float* logits_dev, void* stream);
+cgpt_status cgpt_llm_beam_select_logits(const float* logits_dev, int64_t ld, int32_t B, int32_t num_beams, int32_t V, int32_t step,
+                                        int32_t num_new, int32_t min_new, const int64_t* eos_ids_host, int32_t num_eos, int64_t pad_id,
+                                        float length_penalty, const float* running_in_dev, const int64_t* tokens_in_dev,
+                                        const int32_t* anc_in_dev, const float* pool_score_in_dev, const int32_t* pool_fin_in_dev,
+                                        const int32_t* pool_len_in_dev, const int64_t* pool_seq_in_dev, const int32_t* open_in_dev,
+                                        float* running_out_dev, int64_t* tokens_out_dev, int32_t* anc_out_dev, float* pool_score_out_dev,
+                                        int32_t* pool_fin_out_dev, int32_t* pool_len_out_dev, int64_t* pool_seq_out_dev,
+                                        int32_t* open_out_dev, int64_t* next_tokens_dev, int32_t* parents_dev, void* stream);
+cgpt_status cgpt_llm_beam(cgpt_llm_handle h, const float* first_logits_dev, int32_t B, int32_t num_beams, int32_t prompt_len,
+                          int32_t num_new, int32_t min_new, const int64_t* eos_ids_host, int32_t num_eos, int64_t pad_id,
+                          float length_penalty, void* const* prompt_k_ptrs_host, void* const* prompt_v_ptrs_host, int64_t prompt_stride,
+                          void* const* beam_k_ptrs_host, void* const* beam_v_ptrs_host, int64_t beam_stride, int64_t* tokens_out_dev,
+                          float* scores_out_dev, float* step_logits_out_dev, float* trace_out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
