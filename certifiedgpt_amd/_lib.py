@@ -120,6 +120,7 @@ SIGNATURES = {
     "cgpt_linear_f16": (_I32, [_P, _I64, _P, _I64, _P, _P, _I64, _P, _I64, _I64, _I64, _I64, _I32, _P]),
     "cgpt_attention_f16": (_I32, [_P, _I64, _P, _P, _I64, _P, _I64, _I32, _I32, _I32, _I32, _I32, _F, _P]),
     "cgpt_layernorm": (_I32, [_P, _I64, _P, _P, _F, _P, _I64, _P, _I64, _I64, _I32, _P]),
+    "cgpt_layernorm_resid": (_I32, [_P, _I64, _P, _I64, _P, _I64, _I32, _P, _P, _F, _P, _I64, _P, _I64, _I64, _I32, _P]),
     "cgpt_llm_create": (_I32, [C.POINTER(LlmConfig), C.POINTER(_P)]),
     "cgpt_llm_destroy": (_I32, [_P]),
     "cgpt_llm_load_weight_f16": (_I32, [_P, C.c_char_p, _P, _I64, _P]),

@@ -163,6 +163,120 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8))) voi
     layernorm4_body<11>(CGPT_LN4_PASS);
 }
 
+// The 16-byte path again, scheduled for the memory system (ln_kernel = 1, the default; layernorm4_body above is ln_kernel = 0).
+// Same row -> lane mapping and the same floating-point operations in the same order as layernorm4_body, so the bits are the
+// same; what differs is when memory is touched:
+//  * the form (delta / delta2 / store x / y16 / y32) is a template parameter: no branch in any loop, so hipcc can hoist loads;
+//  * the global loads of a row (x, delta, delta2: NCH x (16 + 8 + 8) B per lane) all stand before the first use and are waited
+//    for with counted vmcnt (hipcc holds the last 6 of LN1's 22 and 8 of LN2's 33 back until the first return, for registers);
+//    the fp32 stream store leaves after the statistics, behind the row's last load;
+//  * gamma and beta are staged once per workgroup in LDS (ds_read_b128 counts on lgkmcnt, so pass 3 never waits for its own
+//    stores, which a global load there would: vmcnt counts loads and stores together), and a workgroup walks row groups in a
+//    grid-stride loop so that the staging is paid once per ~6 groups.
+// SPLIT = 0: loads issued chunk by chunk (x, delta, delta2 of chunk c together); SPLIT = 1: two halves of the row, each as
+// x.. delta.. delta2.., the second half's loads issued before the first half's arithmetic.  WAVES = waves per SIMD asked for.
+template <int NCH, bool HAS_D, bool HAS_D2, bool STORE_X, bool Y16, bool Y32, int SPLIT>
+__device__ __forceinline__ void layernorm4_rows_body(float* __restrict__ x, int64_t ldx, const half_t* __restrict__ delta, int64_t ldd,
+                                                     const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                     half_t* __restrict__ y16, int64_t ldy16, float* __restrict__ y32, int64_t ldy32,
+                                                     int64_t rows, const half_t* __restrict__ delta2, int64_t ldd2) {
+    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+    typedef float f32x4nt __attribute__((ext_vector_type(4)));
+    constexpr int D = NCH * 128, HALF = (NCH + 1) / 2;
+    __shared__ float4 gb[2 * NCH * 32];                    // gamma, then beta
+    for (int i = threadIdx.x; i < NCH * 32; i += 256) {
+        gb[i] = reinterpret_cast<const float4*>(gamma)[i];
+        gb[NCH * 32 + i] = reinterpret_cast<const float4*>(beta)[i];
+    }
+    __syncthreads();
+    const int l32 = threadIdx.x & 31;
+    const int64_t groups = (rows + 7) >> 3;
+    for (int64_t g = blockIdx.x; g < groups; g += gridDim.x) {            // uniform per workgroup: every wave stays in the shuffles
+        const int64_t row = g * 8 + (threadIdx.x >> 5);
+        const bool live = row < rows;
+        const int64_t rr = live ? row : rows - 1;                       // a dead half-wave reads the last row and stores nothing
+        float* xr = x + rr * ldx + l32 * 4;
+        const half_t* dr = HAS_D ? delta + rr * ldd + l32 * 4 : nullptr;
+        const half_t* er = HAS_D2 ? delta2 + rr * ldd2 + l32 * 4 : nullptr;
+        f32x4nt xv[NCH];
+        f16x4 dv[NCH], ev[NCH];
+        if constexpr (SPLIT == 0) {
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+                xv[c] = __builtin_nontemporal_load(reinterpret_cast<const f32x4nt*>(xr + c * 128));
+                if constexpr (HAS_D) dv[c] = __builtin_nontemporal_load(reinterpret_cast<const f16x4*>(dr + c * 128));
+                if constexpr (HAS_D2) ev[c] = __builtin_nontemporal_load(reinterpret_cast<const f16x4*>(er + c * 128));
+            }
+        } else {
+            constexpr int H = HALF;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int c0 = h ? H : 0, c1 = h ? NCH : H;
+#pragma unroll
+                for (int c = c0; c < c1; ++c) xv[c] = __builtin_nontemporal_load(reinterpret_cast<const f32x4nt*>(xr + c * 128));
+                if constexpr (HAS_D) {
+#pragma unroll
+                    for (int c = c0; c < c1; ++c) dv[c] = __builtin_nontemporal_load(reinterpret_cast<const f16x4*>(dr + c * 128));
+                }
+                if constexpr (HAS_D2) {
+#pragma unroll
+                    for (int c = c0; c < c1; ++c) ev[c] = __builtin_nontemporal_load(reinterpret_cast<const f16x4*>(er + c * 128));
+                }
+            }
+        }
+        float4 v[NCH];
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            v[c] = make_float4(xv[c][0], xv[c][1], xv[c][2], xv[c][3]);
+            if constexpr (HAS_D) { v[c].x += (float)dv[c][0]; v[c].y += (float)dv[c][1]; v[c].z += (float)dv[c][2]; v[c].w += (float)dv[c][3]; }
+            if constexpr (HAS_D2) { v[c].x += (float)ev[c][0]; v[c].y += (float)ev[c][1]; v[c].z += (float)ev[c][2]; v[c].w += (float)ev[c][3]; }
+            s += (v[c].x + v[c].y) + (v[c].z + v[c].w);
+        }
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        const float mean = s / (float)D;
+        float q = 0.f;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            const float a = v[c].x - mean, b = v[c].y - mean, cc = v[c].z - mean, d = v[c].w - mean;
+            q += (a * a + b * b) + (cc * cc + d * d);
+        }
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) q += __shfl_xor(q, o);
+        const float rstd = rsqrtf(q / (float)D + eps);
+        if (live) {
+            if constexpr (STORE_X) {
+#pragma unroll
+                for (int c = 0; c < NCH; ++c)
+                    __builtin_nontemporal_store(f32x4nt{v[c].x, v[c].y, v[c].z, v[c].w}, reinterpret_cast<f32x4nt*>(xr + c * 128));
+            }
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+                const int col = c * 128 + l32 * 4;
+                const float4 gm = gb[c * 32 + l32];
+                const float4 bt = gb[NCH * 32 + c * 32 + l32];
+                float o0 = (v[c].x - mean) * rstd * gm.x + bt.x, o1 = (v[c].y - mean) * rstd * gm.y + bt.y;
+                float o2 = (v[c].z - mean) * rstd * gm.z + bt.z, o3 = (v[c].w - mean) * rstd * gm.w + bt.w;
+                // keep the fp32 result as its own value: with the output type known at compile time hipcc otherwise fuses the fma and
+                // the fp16 convert into v_fma_mix*_f16 (ONE rounding); layernorm4_body rounds to fp32 first, then to fp16
+                asm volatile("" : "+v"(o0), "+v"(o1), "+v"(o2), "+v"(o3));
+                if constexpr (Y16) *reinterpret_cast<f16x4*>(y16 + row * ldy16 + col) = f16x4{(half_t)o0, (half_t)o1, (half_t)o2, (half_t)o3};
+                if constexpr (Y32) *reinterpret_cast<float4*>(y32 + row * ldy32 + col) = make_float4(o0, o1, o2, o3);
+            }
+        }
+    }
+}
+
+#define CGPT_LNR_ARGS float* __restrict__ x, int64_t ldx, const half_t* __restrict__ delta, int64_t ldd, const float* __restrict__ gamma, \
+                      const float* __restrict__ beta, float eps, half_t* __restrict__ y16, int64_t ldy16, float* __restrict__ y32, \
+                      int64_t ldy32, int64_t rows, const half_t* __restrict__ delta2, int64_t ldd2
+template <int NCH, bool HAS_D, bool HAS_D2, bool STORE_X, bool Y16, bool Y32, int SPLIT, int WAVES>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) void layernorm4_rows_kernel(CGPT_LNR_ARGS) {
+    layernorm4_rows_body<NCH, HAS_D, HAS_D2, STORE_X, Y16, Y32, SPLIT>(x, ldx, delta, ldd, gamma, beta, eps, y16, ldy16, y32, ldy32, rows,
+                                                                      delta2, ldd2);
+}
+
 // x[row, :] += delta[row, :]  (the last block's pending residual update, when no LayerNorm follows on those rows)
 __global__ __launch_bounds__(256) void add_delta_kernel(float* __restrict__ x, int64_t ldx, const half_t* __restrict__ delta,
                                                         int64_t ldd, int64_t rows, int D, int skip_mod) {
@@ -472,6 +586,77 @@ hipError_t launch_add_delta(float* x, int64_t ldx, const half_t* delta, int64_t 
     return hipGetLastError();
 }
 
+int g_ln_kernel = 1;
+
+namespace {
+
+struct LnArgs {
+    float* x; int64_t ldx; const half_t* delta; int64_t ldd; const float* gamma; const float* beta; float eps;
+    half_t* y16; int64_t ldy16; float* y32; int64_t ldy32; int64_t rows; const half_t* delta2; int64_t ldd2; hipStream_t stream;
+};
+
+inline hipError_t ln_device_cus(int& cus) {
+    constexpr int kMaxDevicesLn = 64;
+    static int table[kMaxDevicesLn] = {0};
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+    if (dev < 0 || dev >= kMaxDevicesLn) return hipErrorInvalidDevice;
+    if (table[dev] == 0) {
+        int n = 0;
+        if (hipError_t e = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); e != hipSuccess) return e;
+        table[dev] = n > 0 ? n : 256;
+    }
+    cus = table[dev];
+    return hipSuccess;
+}
+
+// One resident workgroup (4 waves, one per SIMD) per wave slot: WAVES workgroups per CU walk the row groups.
+template <int NCH, bool HAS_D, bool HAS_D2, bool STORE_X, bool Y16, bool Y32, int SPLIT, int WAVES>
+hipError_t launch_ln_rows(const LnArgs& a) {
+    int cus = 0;
+    if (hipError_t e = ln_device_cus(cus); e != hipSuccess) return e;
+    const int64_t groups = (a.rows + 7) / 8, resident = (int64_t)cus * WAVES;
+    hipLaunchKernelGGL((layernorm4_rows_kernel<NCH, HAS_D, HAS_D2, STORE_X, Y16, Y32, SPLIT, WAVES>),
+                       dim3((unsigned)(groups < resident ? groups : resident)), dim3(256), 0, a.stream, a.x, a.ldx, a.delta, a.ldd, a.gamma,
+                       a.beta, a.eps, a.y16, a.ldy16, a.y32, a.ldy32, a.rows, a.delta2, a.ldd2);
+    return hipGetLastError();
+}
+
+// The forms the library launches at the ViT-G width (model.hip forward()); `variant` = ln_kernel (1 = the kept schedule per form,
+// measured in profiles/r07/layernorm_rewrite.txt; lab builds: 10 + 3 * SPLIT + (WAVES - 4)).  false: no fast kernel for this form.
+template <bool HAS_D, bool HAS_D2, bool STORE_X, int SPLIT, int WAVES>
+bool launch_ln_vitg_form(const LnArgs& a, int variant, hipError_t& e) {
+    if (variant == 1) { e = launch_ln_rows<11, HAS_D, HAS_D2, STORE_X, true, false, SPLIT, WAVES>(a); return true; }
+#ifdef CGPT_LAB
+#define CGPT_LNV(V, S, W) if (variant == V) { e = launch_ln_rows<11, HAS_D, HAS_D2, STORE_X, true, false, S, W>(a); return true; }
+    CGPT_LNV(10, 0, 4) CGPT_LNV(11, 0, 5) CGPT_LNV(12, 0, 6) CGPT_LNV(13, 1, 4) CGPT_LNV(14, 1, 5) CGPT_LNV(15, 1, 6)
+#undef CGPT_LNV
+#endif
+    return false;
+}
+
+// SPLIT, WAVES kept per form (profiles/r07/layernorm_rewrite.txt): the most waves that hold the row's loads without scratch --
+// 74 VGPRs / 6 waves without an update, 94 / 5 with one, 117 / 4 with two or with the stream store.  One wave more spills and loses the gain.
+#define CGPT_LN_KEPT_PLAIN 0, 6
+#define CGPT_LN_KEPT_LN1 0, 5
+#define CGPT_LN_KEPT_LN2 0, 4
+// Every other form and every other width keeps layernorm4_body (the Q-Former's post-LNs, 8 160 rows of 768, were slower in the rows
+// kernel: 13.9 against 12.0 us -- at one row group per workgroup the LDS staging is not paid back).
+bool launch_ln_fast(const LnArgs& a, int nch, bool store, int variant, hipError_t& e) {
+    const bool d = a.delta != nullptr, d2 = a.delta2 != nullptr;
+    if (nch == 11 && a.y16 && !a.y32) {
+        if (!d && !d2) return launch_ln_vitg_form<false, false, false, CGPT_LN_KEPT_PLAIN>(a, variant, e);     // block 0 LN1
+        if (d && !d2 && !store) return launch_ln_vitg_form<true, false, false, CGPT_LN_KEPT_LN1>(a, variant, e);   // LN1
+        if (d && d2 && store) return launch_ln_vitg_form<true, true, true, CGPT_LN_KEPT_LN2>(a, variant, e);       // LN2
+        if (!d && d2 && store) return launch_ln_vitg_form<false, true, true, CGPT_LN_KEPT_LN2>(a, variant, e);     // block 0 LN2
+        if (d && !d2 && store) return launch_ln_vitg_form<true, false, true, CGPT_LN_KEPT_LN2>(a, variant, e);     // ln_vision
+        return false;
+    }
+    return false;
+}
+
+}  // namespace
+
 hipError_t launch_layernorm(float* x, int64_t ldx, const half_t* delta, int64_t ldd, const float* gamma,
                             const float* beta, float eps, half_t* y16, int64_t ldy16, float* y32, int64_t ldy32,
                             int64_t rows, int D, hipStream_t stream, const half_t* delta2, int64_t ldd2, int keep_x) {
@@ -479,6 +664,11 @@ hipError_t launch_layernorm(float* x, int64_t ldx, const half_t* delta, int64_t 
     if (D <= 0 || (D & 1) || D > 32 * 128 || (ldx & 1) || (ldy16 & 1) || (ldy32 & 1) || (ldd & 1) || (ldd2 & 1)) return hipErrorInvalidValue;
     // 16-byte path: D a multiple of 128 (1408 = 11 x 128, 768 = 6 x 128, 4096) and 16-byte aligned rows
     if ((D % 128) == 0 && D / 128 <= 32 && (ldx % 4) == 0 && (ldd % 4) == 0 && (ldd2 % 4) == 0 && (ldy16 % 4) == 0 && (ldy32 % 4) == 0) {
+        if (g_ln_kernel != 0) {
+            const LnArgs a{x, ldx, delta, ldd, gamma, beta, eps, y16, ldy16, y32, ldy32, rows, delta2, ldd2, stream};
+            hipError_t e = hipSuccess;
+            if (launch_ln_fast(a, D / 128, (delta || delta2) && !keep_x, g_ln_kernel, e)) return e;
+        }
         dim3 grid4((unsigned)((rows + 7) / 8)), block4(256);
 #define CGPT_LN4(NCH) hipLaunchKernelGGL(layernorm4_kernel<NCH>, grid4, block4, 0, stream, x, ldx, delta, ldd, gamma, beta, eps, \
                                          y16, ldy16, y32, ldy32, rows, D, delta2, ldd2, keep_x)

@@ -67,6 +67,9 @@ hipError_t launch_layernorm(float* x, int64_t ldx, const half_t* delta, int64_t 
                             const float* beta, float eps, half_t* y16, int64_t ldy16, float* y32, int64_t ldy32,
                             int64_t rows, int D, hipStream_t stream, const half_t* delta2 = nullptr, int64_t ldd2 = 0,
                             int keep_x = 0);   // delta2: second pending update; keep_x: do not write x + updates back
+// 16-byte path (D % 128 == 0): 1 (default) = loads-first kernel with gamma/beta in LDS for the forms the model launches,
+// 0 = layernorm4_body for every form.  Same bits either way (speed only); lab builds: 10..15 = the schedules tried.
+extern int g_ln_kernel;
 // x += delta without a LayerNorm (after the last block).  skip_mod > 0: rows r with r % skip_mod == 0 are left alone.
 hipError_t launch_add_delta(float* x, int64_t ldx, const half_t* delta, int64_t ldd, int64_t rows, int D,
                             hipStream_t stream, int skip_mod = 0);

@@ -841,6 +841,16 @@ cgpt_status cgpt_set_option(const char* key, int32_t value) {
         g_gemm_kernel = value;
         return CGPT_OK;
     }
+    if (k == "ln_kernel") {
+#ifdef CGPT_LAB
+        const bool ok = value == 0 || value == 1 || (value >= 10 && value <= 15);
+#else
+        const bool ok = value == 0 || value == 1;
+#endif
+        if (!ok) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_set_option: ln_kernel must be 0 or 1");
+        g_ln_kernel = value;
+        return CGPT_OK;
+    }
     if (k == "gemm_ablate") {
 #ifndef CGPT_LAB
         if (value & ~(512 | 16384))
@@ -974,6 +984,19 @@ cgpt_status cgpt_layernorm(const float* x_dev, int64_t ldx, const float* gamma_d
                                     (hipStream_t)stream);
     if (e != hipSuccess) return cgpt_fail(e == hipErrorInvalidValue ? CGPT_ERR_INVALID : CGPT_ERR_HIP,
                                           std::string("cgpt_layernorm: ") + hipGetErrorString(e));
+    return CGPT_OK;
+}
+
+cgpt_status cgpt_layernorm_resid(float* x_dev, int64_t ldx, const void* delta_dev, int64_t ldd, const void* delta2_dev, int64_t ldd2,
+                                 int32_t keep_x, const float* gamma_dev, const float* beta_dev, float eps, void* y16_dev, int64_t ldy16,
+                                 float* y32_dev, int64_t ldy32, int64_t rows, int32_t D, void* stream) {
+    if (!x_dev || !gamma_dev || !beta_dev || (!y16_dev && !y32_dev)) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_layernorm_resid: null argument");
+    if (rows < 0 || ldx < D || (delta_dev && ldd < D) || (delta2_dev && ldd2 < D) || (y16_dev && ldy16 < D) || (y32_dev && ldy32 < D))
+        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_layernorm_resid: rows < 0 or a leading dimension below D");
+    hipError_t e = launch_layernorm(x_dev, ldx, (const half_t*)delta_dev, ldd, gamma_dev, beta_dev, eps, (half_t*)y16_dev, ldy16, y32_dev, ldy32,
+                                    rows, D, (hipStream_t)stream, (const half_t*)delta2_dev, ldd2, keep_x != 0);
+    if (e != hipSuccess) return cgpt_fail(e == hipErrorInvalidValue ? CGPT_ERR_INVALID : CGPT_ERR_HIP,
+                                          std::string("cgpt_layernorm_resid: ") + hipGetErrorString(e));
     return CGPT_OK;
 }
 

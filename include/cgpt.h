@@ -270,6 +270,10 @@ cgpt_status cgpt_profile_batches(cgpt_handle h, int32_t* samples_out, int64_t ca
  *   "gemm_kernel": 0 = automatic choice (default); 1 = 128x128 register-staged tile, 3 = 256x128 direct-to-LDS tile,
  *                  4 = 256x256 phase-alternating tile, 14 = 256x256 two-phase quadrant tile with a 1.5-K-tile LDS-DMA run-ahead (the
  *                  automatic choice for M >= 1024 when the shape has more than 128 tiles of 256x256).
+ *   "ln_kernel":   MEASUREMENT aid; 1 (default) = the LayerNorm forms the ViT launches (D = 1408, fp16 out, any of the deferred residual adds)
+ *                  run the kernel that issues a row's loads before its first use and reads gamma / beta from LDS; 0 = the earlier
+ *                  chunk-at-a-time kernel for every form.  Same bits (tests/test_gpu_layernorm_forms.py); tools/layernorm_bench.py
+ *                  times both in one process.
  *   "gemm_ablate": TEST-ONLY bit mask; each bit turns ONE optimisation of the 256x256 kernels off without changing a result, so that
  *                  the test suite can check that the bits do not depend on it: 512 = LDS-transposed fp16 epilogue, 16384 = 192-column
  *                  last tiles for N = 256k+128.  Any other bit is rejected with CGPT_ERR_INVALID.  Process-global and unsynchronised: set it only while no launch is in flight.
@@ -313,6 +317,15 @@ cgpt_status cgpt_attention_f16(const void* Q_dev, int64_t ldq, const void* K_dev
 cgpt_status cgpt_layernorm(const float* x_dev, int64_t ldx, const float* gamma_dev, const float* beta_dev, float eps,
                            void* y_dev, int64_t ldy, float* y32_dev, int64_t ldy32, int64_t rows, int32_t D,
                            void* stream);
+/* The same LayerNorm with the ViT blocks' deferred residual adds (eva_vit.py:180-181), as the forward launches it:
+ * v = (x + delta) + delta2 in fp32 (delta_dev / delta2_dev: fp16 [rows, ldd] / [rows, ldd2], either may be NULL), y = LayerNorm(v);
+ * unless keep_x != 0, v is written back to x when at least one update is given.  y16_dev (fp16) and y32_dev (fp32): at least one.
+ * CGPT_ERR_INVALID: null x / gamma / beta, both outputs null, rows < 0, D <= 0, odd or above 4096, an odd leading dimension, or a
+ * leading dimension of a given operand below D.  Rows of x / delta / delta2 must be 4-byte aligned (even strides); the 16-byte
+ * kernels run when D % 128 == 0 and every stride is a multiple of 4. */
+cgpt_status cgpt_layernorm_resid(float* x_dev, int64_t ldx, const void* delta_dev, int64_t ldd, const void* delta2_dev, int64_t ldd2,
+                                 int32_t keep_x, const float* gamma_dev, const float* beta_dev, float eps, void* y16_dev, int64_t ldy16,
+                                 float* y32_dev, int64_t ldy32, int64_t rows, int32_t D, void* stream);
 
 /* ---- LLaMA decode steps and prefill (replaces: the forwards inside `self.llama_model.generate(...)`,
  *      minigpt_base.py:418-431 -- greedy, one new token per row, K/V cache) ----
