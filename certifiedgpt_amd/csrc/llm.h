@@ -1,4 +1,4 @@
-// llm.h -- launchers of the LLaMA decode-step kernels (llm_gemm.hip, llm.hip).  All enqueue on `stream`, no host sync.
+// llm.h -- launchers of the LLaMA decode-step kernels (llm_gemm.hip, llm_step.hip, ...).  All enqueue on `stream`, no host sync.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -65,6 +65,32 @@ size_t i8_gemm_slab_bytes(int N, int K);
 hipError_t i8_gemm_prepare();                               // dynamic-LDS limit on the CURRENT device, outside any capture
 // DEC_F16, DEC_F16_RESID or DEC_SWIGLU; N % 64 == 0, K % 128 == 0; any M >= 1 (256-row tiles on the grid's second dimension).
 hipError_t launch_i8_gemm(int epilogue, const I8GemmParams& p, hipStream_t stream, const int* live = nullptr);
+
+// ------------------------------------------------------------------------------------- token step (llm_step.hip)
+// One launcher per kernel (the arg-max select's is llm_select.h's).  `rows` <= 256 fp16 rows, `hidden` (a multiple of 8) elements apart.
+// live as for launch_decode_gemm.  h[r, :] = table[tokens[r], :] (a token outside the table reads row 0);  y[r, :] = LlamaRMSNorm(x[r, :]) * w
+hipError_t launch_llm_embed(const long long* tokens, const half_t* table, int vocab, int hidden, half_t* h, int rows, hipStream_t stream, const int* live = nullptr);
+hipError_t launch_llm_rmsnorm(const half_t* x, const half_t* w, int hidden, float eps, half_t* y, int rows, hipStream_t stream, const int* live = nullptr);
+// table[pos][0..63 | 64..127] = fp16(cos | sin(pos * inv_freq[i])) for pos < positions; inv_freq holds 64 device floats.
+hipError_t launch_llm_rope_table(const float* inv_freq, half_t* table, int positions, hipStream_t stream);
+// Rotary + K/V append at buffer position `pos` + one-query attention over the row's keys, for every (row, head); out [rows, hidden].
+// G = 0: the plain kernel, qkv rows 3 hidden wide, Kc / Vc [rows, heads, len_stride, 128].  G in {1, 2, 4, 8}: the grouped kernel,
+// kv_heads = heads / G, layouts as for the prefill below.  starts != null (device, [rows]): left padding, clamped into 0 .. min(smax, pos).
+// Dynamic LDS: llm_step_attn_lds_bytes(G, pos + 1); llm_step_prepare(G, max_len) allows it up to max_len (per device, outside a capture).
+struct StepAttnArgs {
+    int G; const half_t* qkv; int hidden, heads; half_t *Kc, *Vc; int64_t len_stride;
+    const half_t* rope; int pos; half_t* out; const int32_t* starts; int smax; const int* live;
+};
+size_t llm_step_attn_lds_bytes(int G, int positions);
+hipError_t llm_step_prepare(int G, int max_len);
+hipError_t launch_llm_step_attention(const StepAttnArgs& a, int rows, hipStream_t stream);
+// The weight law of an int8 handle on w [rows, K] (K % 16 == 0): q and one fp16 scale per row.  Row r goes to row r (interleave < 0)
+// or to row 32 (r / 16) + 16 interleave + r % 16 of q / scales (the gate / up fusion).
+hipError_t launch_llm_quant_rows(const half_t* w, int rows, int K, int interleave, signed char* q, half_t* scales, hipStream_t stream);
+// out[n, k] = fp16(q[n, k]) * scales[n] for all round_up(N, 256) rows of an int8 matrix (pad rows come out as zeros).
+hipError_t launch_llm_dequant(const signed char* q, const half_t* scales, int N, int K, half_t* out, hipStream_t stream);
+// After a select: *live = any(unfinished[0 .. rows)), *live_steps = (first ? 0 : *live_steps) + (*live & more).  rows <= 256.
+hipError_t launch_llm_live(const int* unfinished, int rows, int first, int more, int* live, int* live_steps, hipStream_t stream);
 
 // ------------------------------------------------------------------------------------- prefill (llm_prefill.hip)
 // Token row r = b * L + p of B prompts of L positions.  All fp16, rows `hidden` (or 3 hidden / 2 mlp / mlp) elements apart.

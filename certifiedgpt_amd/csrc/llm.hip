@@ -1,34 +1,22 @@
-// llm.hip -- the LLaMA token step of MiniGPT-4's greedy decode, and its C-ABI (include/cgpt.h, "LLaMA decode steps").
+// llm.hip -- the LLaMA engine behind MiniGPT-4's decode, host side: the handle, the launch sequences (token step, prefill, scoring,
+// greedy loop) and the C-ABI (include/cgpt.h, "LLaMA decode steps").  No kernel lives here: the step's are llm_step.hip's.
 //
 // Reference call replaced: every forward after the prefill inside `self.llama_model.generate(...)`
 // (graphs/models/minigpt4/models/minigpt_base.py:418-431, greedy: do_sample=False, num_beams=1), i.e. HF LlamaForCausalLM
 // on one new token per row with a K/V cache.  The prefill is the caller's (the model's own forward; its K/V are used in place) or
 // cgpt_llm_prefill below: the same layer sequence on B x L token rows, large-shape GEMMs (gemm.hip) and llm_prefill.hip's kernels.
 // cgpt_llm_score (`MiniGPTBase.multi_select`, minigpt_base.py:451-467) runs that sequence once more on the answer tokens of all
-// candidates, on the prompt cache the prefill left and without writing to it (llm_score.hip).
-//
-// One step = embedding lookup, layers x (RMSNorm, fused q/k/v GEMM, rotary + K/V append + one-query attention, o_proj GEMM +
-// residual, RMSNorm, fused gate/up GEMM + SwiGLU, down GEMM + residual), final RMSNorm, lm_head GEMM.  The GEMMs are
-// llm_gemm.hip; the rest is here.  Every kernel rounds where HF's fp16 eager model rounds: what is left between
-// the two is summation order.  Nothing here synchronises, allocates or copies from the host after cgpt_llm_create, so a whole
-// greedy loop can be captured into one graph.
-//
-// int8 handles (cgpt_llm_config.weight_format = CGPT_LLM_W_INT8): the seven layer linears are held as row-wise
-// absmax int8 with one fp16 scale per row (llm_quant_rows_kernel, at load).  The token step reads them through the int8-weight
-// instantiation of the decode GEMM; the prefill expands each matrix into ONE fp16 scratch matrix right before its GEMM
-// (llm_dequant_kernel, same stream).  Both form W' = fp16(q) * s with one fp16 multiply, so every result is bit for bit that of
-// an fp16 handle loaded with W'.
-//
-// Activations-int8 handles (cgpt_llm_config_act.act_format = 1): on top of the int8 weights, every layer linear of
-// the token step, the prefill and the scoring pass is quantise (llm_act_quant_kernel) + int8 GEMM (llm_gemm_i8.hip), in gemm() and
-// big_gemm() below -- the only two call sites.  lm_head stays on the fp16 kernels.  Such a handle has no fp16 scratch.
+// candidates, on the prompt cache the prefill left and without writing to it (llm_score.hip).  No sequence here synchronises,
+// allocates or copies from the host after cgpt_llm_create, so a whole greedy loop can be captured into one graph.
+// int8 handles hold the seven layer linears as row-wise absmax int8 with one fp16 scale per row: gemm() reads
+// them in place, big_gemm() expands one matrix into the fp16 scratch right before its GEMM.  Activations-int8 handles (DESIGN.md
+// 4.4.7) quantise the rows and run the int8 GEMM instead, in those two functions only; lm_head stays fp16 and there is no scratch.
 #include <math.h>
 #include <stddef.h>
 #include <string.h>
 
 #include <set>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/cgpt.h"
@@ -53,469 +41,9 @@ using namespace cgpt;
 
 namespace {
 
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-constexpr int HD = 128;                // head size the attention kernel is written for
+constexpr int HD = 128;                // head size the attention kernels are written for
 constexpr int MAX_ROWS = 256;          // one GEMM row tile
-
-__device__ __forceinline__ float rf16(float v) { return (float)(half_t)v; }
-// fp16(a * b) as a value of its own: without the barrier the compiler contracts fp16(a * b) + c into one v_fma_f16, which skips
-// the product's rounding -- closer to the exact result, but not where HF's eager model rounds (16 % of a rotated key row differed).
-__device__ __forceinline__ float mul_f16(float a, float b) {
-    float r = rf16(a * b);
-    asm volatile("" : "+v"(r));
-    return r;
-}
-
-// Early stop (cgpt_llm_set_early_stop): every kernel of a token step exists twice.  GUARD = true reads *live -- one
-// int, uniform over the grid, written by llm_live_kernel earlier on the same stream -- before any load, LDS write or barrier and
-// returns when it is 0.  GUARD = false never looks at `live` (null) and is the kernel as it was: cgpt_llm_step, the prefill's tail,
-// the scoring pass and a greedy call with early stop off take it.
-
-// h[b, :] = embed[token[b], :].  A token outside the table reads row 0 (never out of bounds).
-template <bool GUARD>
-__global__ __launch_bounds__(256) void llm_embed_kernel(const long long* __restrict__ tokens, const half_t* __restrict__ table,
-                                                        int vocab, int hidden, half_t* __restrict__ h, const int* __restrict__ live) {
-    if constexpr (GUARD)
-        if (*live == 0) return;
-    long long t = tokens[blockIdx.x];
-    if (t < 0 || t >= vocab) t = 0;
-    const h16x8* src = reinterpret_cast<const h16x8*>(table + (int64_t)t * hidden);
-    h16x8* dst = reinterpret_cast<h16x8*>(h + (int64_t)blockIdx.x * hidden);
-    for (int i = threadIdx.x; i < hidden / 8; i += 256) dst[i] = src[i];
-}
-
-// LlamaRMSNorm: y = weight * fp16(x * rsqrt(mean(x^2) + eps)), statistics in fp32, both products rounded to fp16.
-// One workgroup per row; the sum runs in a fixed order (per-thread strided, wave butterfly, 4 wave sums in order).
-template <bool GUARD>
-__global__ __launch_bounds__(256) void llm_rmsnorm_kernel(const half_t* __restrict__ x, const half_t* __restrict__ w, int hidden,
-                                                          float eps, half_t* __restrict__ y, const int* __restrict__ live) {
-    __shared__ float wsum[4];
-    if constexpr (GUARD)
-        if (*live == 0) return;
-    const half_t* xr = x + (int64_t)blockIdx.x * hidden;
-    half_t* yr = y + (int64_t)blockIdx.x * hidden;
-    float ss = 0.0f;
-    for (int i = threadIdx.x; i < hidden / 8; i += 256) {
-        const h16x8 v = reinterpret_cast<const h16x8*>(xr)[i];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) ss += (float)v[e] * (float)v[e];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = ss;
-    __syncthreads();
-    const float total = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-    const float inv = rsqrtf(total / (float)hidden + eps);
-    for (int i = threadIdx.x; i < hidden / 8; i += 256) {
-        const h16x8 v = reinterpret_cast<const h16x8*>(xr)[i];
-        const h16x8 g = reinterpret_cast<const h16x8*>(w)[i];
-        h16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (half_t)((float)g[e] * rf16((float)v[e] * inv));
-        reinterpret_cast<h16x8*>(yr)[i] = o;
-    }
-}
-
-// cos / sin of the default rotary law: table[pos][0..63] = fp16(cos(pos * inv_freq[i])), [64..127] = fp16(sin(...)),
-// the angle in fp32 as HF's LlamaRotaryEmbedding forms it.
-__global__ __launch_bounds__(64) void llm_rope_table_kernel(const float* __restrict__ inv_freq, half_t* __restrict__ table) {
-    const float a = (float)blockIdx.x * inv_freq[threadIdx.x];
-    table[(int64_t)blockIdx.x * HD + threadIdx.x] = (half_t)cosf(a);
-    table[(int64_t)blockIdx.x * HD + 64 + threadIdx.x] = (half_t)sinf(a);
-}
-
-// Rotary + K/V append + attention of one query, one wavefront per (row, head).
-//   q, k, v  = the head's 128 columns of the fused projection row qkv[b, 0 | hidden | 2 hidden + h * 128 ...]
-//   q', k'   = x * cos + rotate_half(x) * sin at position `pos`, each product and the sum rounded to fp16
-//   K[b, h, pos, :] = k',  V[b, h, pos, :] = v        (the only cache rows written)
-//   out[b, h * 128 ...] = fp16(softmax(q' . K[0..pos] / sqrt(128)) . V[0..pos]),  scores, probabilities and the sum in fp32
-// HBM-bound: a head reads (pos + 1) x 2 x 256 B; a wave instruction covers 4 keys x 256 B in 16-byte lanes.
-// RAGGED (left-padded rows, cgpt_llm_step_ragged): the token sits at buffer position `bufpos` of a row whose first real position is
-// s = starts[b] (clamped into 0 .. smax; smax = the prompt's last buffer position, so that prefill and steps clamp alike).  The head's cache pointers move by s and `pos` stands for bufpos - s: rotary row
-// bufpos - s, keys s .. bufpos walked in groups of four from s -- the unpadded row's operations in the unpadded row's order.
-template <bool RAGGED, bool GUARD>
-__global__ __launch_bounds__(64) void llm_attn_kernel(const half_t* __restrict__ qkv, int hidden, int heads, half_t* Kc, half_t* Vc,
-                                                      int64_t len_stride, const half_t* __restrict__ rope, int bufpos,
-                                                      half_t* __restrict__ out, const int* __restrict__ starts, int smax,
-                                                      const int* __restrict__ live) {
-    extern __shared__ float asmem[];                   // [128] rotated query, [128 + 128] halfs: the new key and value, [pos + 1] scores
-    if constexpr (GUARD)
-        if (*live == 0) return;
-    float* qs = asmem;
-    half_t* knew = reinterpret_cast<half_t*>(asmem + HD);
-    half_t* vnew = knew + HD;
-    float* sc = asmem + 2 * HD;
-    const int b = blockIdx.x / heads, h = blockIdx.x % heads, lane = threadIdx.x;
-    const half_t* q = qkv + (int64_t)b * 3 * hidden + h * HD;
-    const half_t* k = q + hidden;
-    const half_t* v = k + hidden;
-    const int s = RAGGED ? min(max(starts[b], 0), min(smax, bufpos)) : 0;
-    const int pos = bufpos - s;
-    half_t* Kh = Kc + ((int64_t)(b * heads + h) * len_stride + s) * HD;
-    half_t* Vh = Vc + ((int64_t)(b * heads + h) * len_stride + s) * HD;
-
-    {   // lane i owns the rotary pair (i, i + 64)
-        const float c = (float)rope[(int64_t)pos * HD + lane], s = (float)rope[(int64_t)pos * HD + 64 + lane];
-        const float q0 = (float)q[lane], q1 = (float)q[lane + 64], k0 = (float)k[lane], k1 = (float)k[lane + 64];
-        qs[lane] = rf16(mul_f16(q0, c) - mul_f16(q1, s));
-        qs[lane + 64] = rf16(mul_f16(q1, c) + mul_f16(q0, s));
-        const half_t r0 = (half_t)(mul_f16(k0, c) - mul_f16(k1, s)), r1 = (half_t)(mul_f16(k1, c) + mul_f16(k0, s));
-        const half_t v0 = v[lane], v1 = v[lane + 64];
-        Kh[(int64_t)pos * HD + lane] = knew[lane] = r0;
-        Kh[(int64_t)pos * HD + lane + 64] = knew[lane + 64] = r1;
-        Vh[(int64_t)pos * HD + lane] = vnew[lane] = v0;
-        Vh[(int64_t)pos * HD + lane + 64] = vnew[lane + 64] = v1;
-    }
-    __syncthreads();                                   // key `pos` is attended from LDS: the cache row just stored is not read back
-
-    const int n = pos + 1;
-    const int kk = lane >> 4, dc = (lane & 15) * 8;    // key within a group of 4, first of the lane's 8 dims
-    float qr[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) qr[e] = qs[dc + e];
-    const float scale = 0.08838834764831845f;          // 1 / sqrt(128)
-    float mx = -INFINITY;
-    for (int t0 = 0; t0 < n; t0 += 4) {
-        const int t = t0 + kk;
-        float d = 0.0f;
-        if (t < n) {
-            const h16x8 kv = *reinterpret_cast<const h16x8*>(t == pos ? knew + dc : Kh + (int64_t)t * HD + dc);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) d += qr[e] * (float)kv[e];
-        }
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) d += __shfl_xor(d, o);
-        d *= scale;
-        if (t < n) {
-            mx = fmaxf(mx, d);
-            if ((lane & 15) == 0) sc[t] = d;
-        }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16));
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    __syncthreads();
-
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    float l = 0.0f;
-    for (int t0 = 0; t0 < n; t0 += 4) {
-        const int t = t0 + kk;
-        if (t < n) {
-            const float p = expf(sc[t] - mx);
-            const h16x8 vv = *reinterpret_cast<const h16x8*>(t == pos ? vnew + dc : Vh + (int64_t)t * HD + dc);
-            l += p;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc[e] += p * (float)vv[e];
-        }
-    }
-    l += __shfl_xor(l, 16);
-    l += __shfl_xor(l, 32);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        acc[e] += __shfl_xor(acc[e], 16);
-        acc[e] += __shfl_xor(acc[e], 32);
-    }
-    if (kk == 0) {
-        h16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (half_t)(acc[e] / l);
-        *reinterpret_cast<h16x8*>(out + (int64_t)b * hidden + h * HD + dc) = o;
-    }
-}
-
-// Grouped-query attention (cgpt_llm_config_gqa.grouped_kv): the token step's attention with ONE read of a K/V head for
-// the G = heads / kv_heads query heads that share it.  One workgroup per (row, K/V head), G wavefronts, wave w = query head
-// kvh * G + w.  The caches are [B, kv_heads, len_stride, 128]; the fused projection row is [hidden | kv_heads * 128 | kv_heads * 128].
-//   every wave rotates its own q; wave 0 rotates and appends the group's one new key / value row, to the cache and to LDS
-//   score pass: the group's cache rows are staged into LDS in chunks of 64 keys (16-byte loads, all waves load), every wave takes
-//       its dot products from the staged chunk; P.V pass: the same walk over V.  Two passes with the scores in LDS, as the plain kernel.
-// A query's arithmetic and key order are exactly llm_attn_kernel's: keys in groups of four from the row's first real key (chunks
-// begin at multiples of 64 keys from it, so the groups of four are the same groups), fp32 dot products with the 16-lane butterfly,
-// the maximum, then expf(sc - mx) and acc += p * v in key order, the same final shuffles and the division.  Staging changes where
-// a byte comes from, never the order of a sum: head h of a grouped handle gives the bits the plain kernel gives on a cache whose
-// head h holds K/V head h / G.  RAGGED and GUARD as in llm_attn_kernel; every barrier sits in block-uniform control flow (n depends on
-// the row alone).  Plain vector stores, no atomics.
-// Dynamic LDS: [64][128] halfs staging, [128 + 128] halfs new key / value, G x [128] floats rotated queries, G x [bufpos + 1] floats
-// scores (gqa_attn_lds_bytes; the limit is set at create, and a (G, max_len) that exceeds the CU's LDS is refused there).
-constexpr int GQA_KC = 64;                          // keys staged per chunk
 constexpr size_t LDS_PER_CU = 160 * 1024;           // gfx950
-
-template <int G, bool RAGGED, bool GUARD>
-__global__ __launch_bounds__(64 * G) void llm_attn_gqa_kernel(const half_t* __restrict__ qkv, int hidden, int kv_heads, half_t* Kc, half_t* Vc,
-                                                              int64_t len_stride, const half_t* __restrict__ rope, int bufpos,
-                                                              half_t* __restrict__ out, const int* __restrict__ starts, int smax,
-                                                              const int* __restrict__ live) {
-    extern __shared__ __attribute__((aligned(16))) float gsmem[];
-    if constexpr (GUARD)
-        if (*live == 0) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    half_t* stage = reinterpret_cast<half_t*>(gsmem);
-    half_t* knew = stage + GQA_KC * HD;
-    half_t* vnew = knew + HD;
-    float* qs = reinterpret_cast<float*>(vnew + HD) + wave * HD;
-    float* sc = reinterpret_cast<float*>(vnew + HD) + G * HD + (int64_t)wave * (bufpos + 1);
-    const int b = blockIdx.x / kv_heads, kvh = blockIdx.x % kv_heads, h = kvh * G + wave;
-    const int kvw = kv_heads * HD;
-    const half_t* q = qkv + (int64_t)b * (hidden + 2 * kvw) + h * HD;
-    const half_t* k = qkv + (int64_t)b * (hidden + 2 * kvw) + hidden + kvh * HD;
-    const half_t* v = k + kvw;
-    const int s = RAGGED ? min(max(starts[b], 0), min(smax, bufpos)) : 0;
-    const int pos = bufpos - s;
-    half_t* Kh = Kc + ((int64_t)(b * kv_heads + kvh) * len_stride + s) * HD;
-    half_t* Vh = Vc + ((int64_t)(b * kv_heads + kvh) * len_stride + s) * HD;
-
-    {   // lane i owns the rotary pair (i, i + 64)
-        const float c = (float)rope[(int64_t)pos * HD + lane], s = (float)rope[(int64_t)pos * HD + 64 + lane];
-        const float q0 = (float)q[lane], q1 = (float)q[lane + 64];
-        qs[lane] = rf16(mul_f16(q0, c) - mul_f16(q1, s));
-        qs[lane + 64] = rf16(mul_f16(q1, c) + mul_f16(q0, s));
-        if (wave == 0) {
-            const float k0 = (float)k[lane], k1 = (float)k[lane + 64];
-            const half_t r0 = (half_t)(mul_f16(k0, c) - mul_f16(k1, s)), r1 = (half_t)(mul_f16(k1, c) + mul_f16(k0, s));
-            const half_t v0 = v[lane], v1 = v[lane + 64];
-            Kh[(int64_t)pos * HD + lane] = knew[lane] = r0;
-            Kh[(int64_t)pos * HD + lane + 64] = knew[lane + 64] = r1;
-            Vh[(int64_t)pos * HD + lane] = vnew[lane] = v0;
-            Vh[(int64_t)pos * HD + lane + 64] = vnew[lane + 64] = v1;
-        }
-    }
-    __syncthreads();                                   // key `pos` is attended from LDS: the cache row just stored is not read back
-
-    const int n = pos + 1;
-    const int kk = lane >> 4, dc = (lane & 15) * 8;    // key within a group of 4, first of the lane's 8 dims
-    float qr[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) qr[e] = qs[dc + e];
-    const float scale = 0.08838834764831845f;          // 1 / sqrt(128)
-    float mx = -INFINITY;
-    for (int c0 = 0; c0 < n; c0 += GQA_KC) {
-        const int nk = min(GQA_KC, n - c0);
-        if (c0 > 0) __syncthreads();                   // the previous chunk has been read by every wave
-        for (int i = tid; i < nk * 16; i += 64 * G) {  // nk keys x 16 pieces of 16 bytes; key `pos` stays in knew
-            const int key = i >> 4, d8 = (i & 15) * 8;
-            if (c0 + key != pos)
-                *reinterpret_cast<h16x8*>(stage + key * HD + d8) = *reinterpret_cast<const h16x8*>(Kh + (int64_t)(c0 + key) * HD + d8);
-        }
-        __syncthreads();
-        for (int t0 = c0; t0 < c0 + nk; t0 += 4) {
-            const int t = t0 + kk;
-            float d = 0.0f;
-            if (t < n) {
-                const h16x8 kv = *reinterpret_cast<const h16x8*>(t == pos ? knew + dc : stage + (t - c0) * HD + dc);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) d += qr[e] * (float)kv[e];
-            }
-#pragma unroll
-            for (int o = 8; o > 0; o >>= 1) d += __shfl_xor(d, o);
-            d *= scale;
-            if (t < n) {
-                mx = fmaxf(mx, d);
-                if ((lane & 15) == 0) sc[t] = d;
-            }
-        }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16));
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    float l = 0.0f;
-    for (int c0 = 0; c0 < n; c0 += GQA_KC) {
-        const int nk = min(GQA_KC, n - c0);
-        __syncthreads();                               // the scores are written / the previous chunk has been read by every wave
-        for (int i = tid; i < nk * 16; i += 64 * G) {
-            const int key = i >> 4, d8 = (i & 15) * 8;
-            if (c0 + key != pos)
-                *reinterpret_cast<h16x8*>(stage + key * HD + d8) = *reinterpret_cast<const h16x8*>(Vh + (int64_t)(c0 + key) * HD + d8);
-        }
-        __syncthreads();
-        for (int t0 = c0; t0 < c0 + nk; t0 += 4) {
-            const int t = t0 + kk;
-            if (t < n) {
-                const float p = expf(sc[t] - mx);
-                const h16x8 vv = *reinterpret_cast<const h16x8*>(t == pos ? vnew + dc : stage + (t - c0) * HD + dc);
-                l += p;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) acc[e] += p * (float)vv[e];
-            }
-        }
-    }
-    l += __shfl_xor(l, 16);
-    l += __shfl_xor(l, 32);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        acc[e] += __shfl_xor(acc[e], 16);
-        acc[e] += __shfl_xor(acc[e], 32);
-    }
-    if (kk == 0) {
-        h16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (half_t)(acc[e] / l);
-        *reinterpret_cast<h16x8*>(out + (int64_t)b * hidden + h * HD + dc) = o;
-    }
-}
-
-size_t gqa_attn_lds_bytes(int G, int positions) {
-    return (size_t)(GQA_KC + 2) * HD * sizeof(half_t) + (size_t)G * (HD + positions) * sizeof(float);
-}
-
-template <int G>
-hipError_t gqa_attn_prepare(int max_len) {
-    const int bytes = (int)gqa_attn_lds_bytes(G, max_len);
-    const void* fns[4] = {reinterpret_cast<const void*>(llm_attn_gqa_kernel<G, false, false>), reinterpret_cast<const void*>(llm_attn_gqa_kernel<G, false, true>),
-                          reinterpret_cast<const void*>(llm_attn_gqa_kernel<G, true, false>), reinterpret_cast<const void*>(llm_attn_gqa_kernel<G, true, true>)};
-    for (const void* f : fns) {
-        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-template <int G, bool GUARD>
-void gqa_attn_launch(const half_t* qkv, int hidden, int kv_heads, int B, half_t* Kc, half_t* Vc, int64_t len_stride, const half_t* rope, int pos,
-                     half_t* out, const int* starts, int smax, const int* live, hipStream_t st) {
-    const size_t lds = gqa_attn_lds_bytes(G, pos + 1);
-    if (starts)
-        hipLaunchKernelGGL((llm_attn_gqa_kernel<G, true, GUARD>), dim3(B * kv_heads), dim3(64 * G), lds, st, qkv, hidden, kv_heads, Kc, Vc, len_stride,
-                           rope, pos, out, starts, smax, live);
-    else
-        hipLaunchKernelGGL((llm_attn_gqa_kernel<G, false, GUARD>), dim3(B * kv_heads), dim3(64 * G), lds, st, qkv, hidden, kv_heads, Kc, Vc, len_stride,
-                           rope, pos, out, nullptr, 0, live);
-}
-
-typedef signed char i8x16 __attribute__((ext_vector_type(16)));
-
-// The weight law of an int8 handle, one workgroup per source row of an HF nn.Linear.weight [rows, K] in fp16:
-//   s = fp16(absmax / 127)           the maximum is exact in any order; the division is fp32, correctly rounded
-//   q = clamp(rint(w / s), -127, 127)   fp32 division, round to nearest even; s == 0 (a zero row, or an underflow): q = 0
-// Row r goes to row r of the destination (interleave < 0) or to row 32 (r / 16) + 16 interleave + r % 16 (gate / up fusion):
-// a row keeps its scale.  16 values per thread and pass: 16-byte stores.
-__global__ __launch_bounds__(256) void llm_quant_rows_kernel(const half_t* __restrict__ w, int K, int interleave,
-                                                             signed char* __restrict__ q, half_t* __restrict__ scales) {
-    __shared__ float wmax[4];
-    const int r = blockIdx.x;
-    const int dr = interleave < 0 ? r : 32 * (r / 16) + 16 * interleave + (r % 16);
-    const h16x8* src = reinterpret_cast<const h16x8*>(w + (int64_t)r * K);
-    float amax = 0.0f;
-    for (int i = threadIdx.x; i < K / 8; i += 256) {
-        const h16x8 v = src[i];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf((float)v[e]));
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
-    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = amax;
-    __syncthreads();
-    amax = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-    const half_t sh = (half_t)__fdiv_rn(amax, 127.0f);
-    const float sf = (float)sh;
-    if (threadIdx.x == 0) scales[dr] = sh;
-    i8x16* dst = reinterpret_cast<i8x16*>(q + (int64_t)dr * K);
-    for (int i = threadIdx.x; i < K / 16; i += 256) {
-        const h16x8 lo = src[2 * i], hi = src[2 * i + 1];
-        i8x16 o;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const float x = (float)(e < 8 ? lo[e] : hi[e - 8]);
-            const float t = fminf(fmaxf(rintf(__fdiv_rn(x, sf)), -127.0f), 127.0f);
-            o[e] = sf == 0.0f ? (signed char)0 : (signed char)(int)t;
-        }
-        dst[i] = o;
-    }
-}
-
-// out[n, k] = fp16(q[n, k]) * s[n] (ONE fp16 multiply; the conversion is exact) for the rows_padded x K int8 matrix of an int8
-// handle: the prefill's expansion into the handle's fp16 scratch.  Pad rows hold q = 0 and s = 0 and come out as zeros.
-// One thread per 16 values: a 16-byte load, two 16-byte stores.
-__global__ __launch_bounds__(256) void llm_dequant_kernel(const signed char* __restrict__ q, const half_t* __restrict__ scales, int K,
-                                                          int64_t chunks, half_t* __restrict__ out) {
-    const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (id >= chunks) return;
-    const int per_row = K / 16;
-    const half_t s = scales[id / per_row];
-    const i8x16 v = reinterpret_cast<const i8x16*>(q)[id];
-    h16x8 lo, hi;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        lo[e] = (half_t)(short)v[e];
-        hi[e] = (half_t)(short)v[e + 8];
-    }
-    lo = lo * s;
-    hi = hi * s;
-    asm volatile("" : "+v"(lo), "+v"(hi));                 // the products stay values of their own
-    reinterpret_cast<h16x8*>(out)[2 * id] = lo;
-    reinterpret_cast<h16x8*>(out)[2 * id + 1] = hi;
-}
-
-// EosIds, StopSeqs and the bookkeeping tail of a select (CGPT_SELECT_TAIL) are llm_select.h's: the sampled select (llm_sample.hip) shares them.
-
-// Greedy bookkeeping of one step, one workgroup per row (greedy_tokens in minigpt4.py): EOS columns read as -inf while
-// `mask_eos` (the first min_new_tokens steps), first-max arg-max, pad once the row has produced an EOS.
-//   dst != null: the (masked) logits are also written there (row stride ldd); dst may be src.
-//   first != 0:  every row starts unfinished (step 0)
-// GUARD (early stop): a select other than the first that reads *live == 0 -- every row has produced an EOS -- is a dead select: no
-// vocabulary scan, no logits copy, `unfinished` left as it is (all zeros); it writes the pad id, which is what the scan would have
-// ended in.  The first select never reads `live` (it holds the previous call's value until llm_live_kernel has run).
-// STOP (stop sequences): a still-unfinished row also finishes when its tokens up to and including this one end in one of the
-// sequences.  The row's earlier tokens are read back from tokens_out (columns col - 1, col - 2, ..., written by the earlier selects
-// of the call on the same stream); a sequence longer than col + 1 is skipped, so nothing left of column 0 -- the previous row's last
-// tokens -- is ever read.  STOP = false is the kernel as it was.
-template <bool GUARD, bool STOP = false>
-__global__ __launch_bounds__(256) void llm_select_kernel(const float* src, int64_t lds, float* dst, int64_t ldd, int vocab,
-                                                         int mask_eos, EosIds eos, long long pad, int first, int* __restrict__ unfinished,
-                                                         long long* __restrict__ tokens_out, int64_t ld_tokens,
-                                                         long long* __restrict__ next_tok, const int* __restrict__ live,
-                                                         StopArg<STOP> stop) {
-    __shared__ float bv[4];
-    __shared__ int bi[4];
-    const int row = blockIdx.x;
-    if constexpr (GUARD) {
-        if (!first && *live == 0) {
-            if (threadIdx.x == 0) {
-                tokens_out[(int64_t)row * ld_tokens] = pad;
-                next_tok[row] = pad;
-            }
-            return;
-        }
-    }
-    const float* s = src + (int64_t)row * lds;
-    float* d = dst ? dst + (int64_t)row * ldd : nullptr;
-    float best = -INFINITY;
-    int idx = 0x7fffffff;
-    for (int j = threadIdx.x; j < vocab; j += 256) {
-        float v = s[j];
-        if (mask_eos)
-            for (int e = 0; e < eos.n; ++e)
-                if (eos.id[e] == j) v = -INFINITY;
-        if (d) d[j] = v;
-        if (idx == 0x7fffffff || v > best) { best = v; idx = j; }          // ascending j: the first maximum stays
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o);
-        const int oi = __shfl_xor(idx, o);
-        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
-    }
-    if ((threadIdx.x & 63) == 0) { bv[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = idx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
-        CGPT_SELECT_TAIL(STOP, row, idx, first, eos, pad, unfinished, tokens_out, ld_tokens, next_tok, stop);
-    }
-}
-
-// The reduction behind early stop, ONE workgroup of 256 threads after a select (rows <= 256): live = any(unfinished[0 .. rows)), and
-// live_steps counts the token steps of the call that run: reset by the first select's launch, + 1 when a step follows this select
-// (`more`) and some row is unfinished.  The next launches of the stream read `live` (the kernel boundary orders the store).
-__global__ __launch_bounds__(256) void llm_live_kernel(const int* __restrict__ unfinished, int rows, int first, int more,
-                                                       int* __restrict__ live, int* __restrict__ live_steps) {
-    const int u = (int)threadIdx.x < rows ? unfinished[threadIdx.x] : 0;
-    const int any = __syncthreads_or(u) ? 1 : 0;
-    if (threadIdx.x == 0) {
-        const int steps = first ? 0 : *live_steps;
-        *live = any;
-        *live_steps = steps + (any & more);
-    }
-}
 
 // The config a handle keeps: the caller's cgpt_llm_config and the switches of cgpt_llm_config_gqa (0 for a plain config).
 struct LlmCfg : cgpt_llm_config {
@@ -540,12 +68,24 @@ struct Layer {
 
 struct cgpt_llm {
     LlmCfg cfg;
+    std::set<std::string> loaded;
+    size_t expected = 0;
+    std::vector<void*> allocs;             // every device buffer of the handle, freed at destroy
+    int64_t weight_bytes = 0;              // matrices, scales and scratch, as allocated (cgpt_llm_weight_bytes)
     std::vector<Layer> layers;
     half_t *embed = nullptr, *norm = nullptr, *lm_head = nullptr, *rope = nullptr;
+    // int8 handles: the prefill's ONE fp16 expansion of the layer matrix its next GEMM reads (stream order makes one enough)
+    half_t* scratch = nullptr;
     half_t *h = nullptr, *xn = nullptr, *qkv = nullptr, *attn = nullptr, *act = nullptr;
     float *slabs = nullptr, *logits = nullptr;
     long long* tok = nullptr;
     int* unfinished = nullptr;
+    // activations-int8 handles: codes, row scales and outlier lists of the rows the next int8 GEMM reads -- 256 rows for the token step,
+    // `p_rows` for the prefill / scoring workspace (one set each: stream order makes one enough) -- and the four statistics counters
+    signed char *a8 = nullptr, *p_a8 = nullptr;
+    float *sa = nullptr, *p_sa = nullptr;
+    uint32_t *lists = nullptr, *p_lists = nullptr;
+    unsigned long long* act_counters = nullptr;
     // early stop (cgpt_llm_set_early_stop): `live` = 1 while some row of the running greedy call is unfinished, `live_steps` = the
     // token steps of that call that ran; both written by llm_live_kernel only.  With early stop off nothing on the device maintains
     // them: the last call's count (num_new - 1, every step runs) is kept in `off_steps`, and `last_on` says which of the two holds.
@@ -562,22 +102,10 @@ struct cgpt_llm {
     int64_t bm_rows = 0, bm_elems = 0;
     BeamState bm[2]{};
     int32_t* bm_parents = nullptr;
-    std::set<std::string> loaded;
-    size_t expected = 0;
-    std::vector<void*> allocs;
     // prefill workspace (cgpt_llm_prefill_reserve): `p_rows` token rows, a multiple of 256.  A workspace that a larger one replaced
     // stays allocated (in `allocs`) until destroy: a graph captured earlier still holds its addresses.
     int64_t p_rows = 0;
     half_t *p_h = nullptr, *p_xn = nullptr, *p_qkv = nullptr, *p_attn = nullptr, *p_proj = nullptr, *p_gu = nullptr, *p_act = nullptr;
-    // int8 handles: the prefill's ONE fp16 expansion of the layer matrix its next GEMM reads (stream order makes one enough)
-    half_t* scratch = nullptr;
-    int64_t weight_bytes = 0;              // matrices, scales and scratch, as allocated (cgpt_llm_weight_bytes)
-    // activations-int8 handles: codes, row scales and outlier lists of the rows the next int8 GEMM reads -- 256 rows for the token step,
-    // `p_rows` for the prefill / scoring workspace (one set each: stream order makes one enough) -- and the four statistics counters
-    signed char *a8 = nullptr, *p_a8 = nullptr;
-    float *sa = nullptr, *p_sa = nullptr;
-    uint32_t *lists = nullptr, *p_lists = nullptr;
-    unsigned long long* act_counters = nullptr;
     // scoring workspace (cgpt_llm_score_reserve) beside the prefill workspace, which holds the tail rows: fp16 logits of `s_rows`
     // tail rows (a multiple of 256; more rows run in chunks) and `s_ce` per-token cross-entropies.  Replaced buffers stay in `allocs`.
     int64_t s_rows = 0, s_ce = 0;
@@ -614,78 +142,81 @@ cgpt_status check_cache(cgpt_llm* m, const char* who, int B, int last_pos, void*
     return CGPT_OK;
 }
 
-#define LAUNCHED() HIPCHK(hipGetLastError())
+// A grower's buffers (prefill / score / beam reserve), built beside the ones in use: add() allocates and zeroes (nothing after a
+// failure); commit() synchronises and hands them to `allocs`, or frees all of them on any failure.  Then the caller swaps them in.
+struct Staging {
+    std::vector<void*> made;
+    hipError_t e = hipSuccess;
+    template <typename T>
+    void add(T** out, size_t bytes) {
+        if (e != hipSuccess || (e = hipMalloc((void**)out, bytes)) != hipSuccess) return;
+        made.push_back(*out);
+        e = hipMemset(*out, 0, bytes);
+    }
+    cgpt_status commit(cgpt_llm* m, const std::string& who) {
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+            for (void* p : made) (void)hipFree(p);
+            return cgpt_fail(CGPT_ERR_HIP, who + ": workspace allocation failed -> " + hipGetErrorString(e));
+        }
+        m->allocs.insert(m->allocs.end(), made.begin(), made.end());
+        return CGPT_OK;
+    }
+};
+
+// The int8 GEMM on what launch_act_quant left in a8 / sa / lists: rows K apart on both sides, the residual laid out as the result.
+I8GemmParams i8_params(const signed char* a8, const float* sa, const uint32_t* lists, int cap, const signed char* Wq, const half_t* Ws,
+                       void* out, int64_t ldo, const half_t* resid, void* slabs, int64_t M, int N, int K) {
+    return I8GemmParams{a8, K, sa, lists, cap, Wq, K, Ws, (half_t*)out, ldo, resid, ldo, (int*)slabs, (int)M, N, K};
+}
 
 cgpt_status gemm(cgpt_llm* m, int epi, const half_t* A, int K, const Mat& W, int N, void* out, int64_t ldo, const half_t* resid,
                  int B, hipStream_t st, const int* live = nullptr) {
-    if (m->cfg.act_format && W.q) {                        // a layer linear of an activations-int8 handle: quantise the rows, int8 GEMM
-        HIPCHK(launch_act_quant(A, B, K, m->cfg.act_threshold, m->cfg.outlier_cap, m->a8, m->sa, m->lists, m->act_counters, st, live));
-        I8GemmParams q{};
-        q.A = m->a8; q.lda = K; q.sa = m->sa; q.lists = m->lists; q.cap = m->cfg.outlier_cap; q.W = W.q; q.ldw = K; q.wscale = W.s;
-        q.out = (half_t*)out; q.ldo = ldo; q.resid = resid; q.ldr = ldo; q.slabs = reinterpret_cast<int*>(m->slabs);
-        q.M = B; q.N = N; q.K = K;
-        HIPCHK(launch_i8_gemm(epi, q, st, live));
+    const LlmCfg& c = m->cfg;
+    if (c.act_format && W.q) {                             // a layer linear of an activations-int8 handle: quantise the rows, int8 GEMM
+        HIPCHK(launch_act_quant(A, B, K, c.act_threshold, c.outlier_cap, m->a8, m->sa, m->lists, m->act_counters, st, live));
+        HIPCHK(launch_i8_gemm(epi, i8_params(m->a8, m->sa, m->lists, c.outlier_cap, W.q, W.s, out, ldo, resid, m->slabs, B, N, K), st, live));
         return CGPT_OK;
     }
-    DecodeGemmParams p{};
-    p.A = A; p.lda = K; p.W = W.q ? reinterpret_cast<const half_t*>(W.q) : W.w; p.ldw = K; p.out = out; p.ldo = ldo; p.resid = resid;
-    p.ldr = ldo; p.slabs = m->slabs;
-    p.M = B; p.N = N; p.K = K;
+    const DecodeGemmParams p{A, K, W.q ? reinterpret_cast<const half_t*>(W.q) : W.w, K, out, ldo, resid, ldo, m->slabs, B, N, K};
     HIPCHK(launch_decode_gemm(epi, p, st, W.q ? W.s : nullptr, live));
     return CGPT_OK;
 }
 
 // One token step on rows 0..B-1: tokens -> logits (fp32, row stride ld_logits).
 // starts (device, or null): per-row left padding, clamped into 0 .. smax, see llm_attn_kernel.
-// GUARD: every launch is the guarded instantiation on m->live (a greedy call with early stop on); otherwise the plain kernels.
-// beam != null (a beam step, plain handles without GUARD only): the B rows are images x k beam rows, kp / vp / len_stride are the BEAM
-// caches, pos = L + t, and the attention is llm_attn_beam_kernel on the prompt caches and the ancestry table `beam` names.
+// live (m->live, or null: the plain kernels): every launch is the guarded instantiation on it (a greedy call with early stop on).
+// beam != null (plain handles without `live` only): the B rows are images x k beam rows, kp / vp / len_stride the BEAM caches,
+// pos = L + t, and the attention is llm_attn_beam_kernel on the prompt caches and the ancestry table `beam` names.
 struct BeamStep {
     void* const* pk; void* const* pv; int64_t prompt_stride;
     const int32_t* anc; int64_t ld_anc;
     int k, L, t;
 };
-template <bool GUARD>
-cgpt_status run_step(cgpt_llm* m, const long long* tokens, int B, int pos, const int32_t* starts, int smax, void* const* kp, void* const* vp,
-                     int64_t len_stride, float* logits, int64_t ld_logits, hipStream_t st, const BeamStep* beam = nullptr) {
+cgpt_status run_step(cgpt_llm* m, const int* live, const long long* tokens, int B, int pos, const int32_t* starts, int smax, void* const* kp,
+                     void* const* vp, int64_t len_stride, float* logits, int64_t ld_logits, hipStream_t st, const BeamStep* beam = nullptr) {
     const LlmCfg& c = m->cfg;
     const int H = c.hidden, NQ = qkv_width(c);
-    const int* live = GUARD ? m->live : nullptr;
-    hipLaunchKernelGGL(llm_embed_kernel<GUARD>, dim3(B), dim3(256), 0, st, tokens, m->embed, c.vocab, H, m->h, live);
-    LAUNCHED();
-    const size_t attn_lds = (size_t)(2 * HD + pos + 1) * sizeof(float);      // scores of the longest row a batch can hold
+    HIPCHK(launch_llm_embed(tokens, m->embed, c.vocab, H, m->h, B, st, live));
     for (int l = 0; l < c.layers; ++l) {
         const Layer& L = m->layers[l];
-        hipLaunchKernelGGL(llm_rmsnorm_kernel<GUARD>, dim3(B), dim3(256), 0, st, m->h, L.ln1, H, c.rms_eps, m->xn, live);
-        LAUNCHED();
+        HIPCHK(launch_llm_rmsnorm(m->h, L.ln1, H, c.rms_eps, m->xn, B, st, live));
         CGCHK(gemm(m, DEC_F16, m->xn, H, L.wqkv, NQ, m->qkv, NQ, nullptr, B, st, live));
         if (beam) {
             BeamAttnArgs a{m->qkv, H, c.heads, beam->k, (const half_t*)beam->pk[l], (const half_t*)beam->pv[l], beam->prompt_stride,
                            (half_t*)kp[l], (half_t*)vp[l], len_stride, beam->anc, beam->ld_anc, m->rope, beam->L, beam->t, B, m->attn};
             HIPCHK(launch_llm_beam_attn(a, st));
-        } else if (c.grouped_kv) {
-            half_t *Kl = (half_t*)kp[l], *Vl = (half_t*)vp[l];
-            switch (c.heads / c.kv_heads) {
-                case 1: gqa_attn_launch<1, GUARD>(m->qkv, H, c.kv_heads, B, Kl, Vl, len_stride, m->rope, pos, m->attn, starts, smax, live, st); break;
-                case 2: gqa_attn_launch<2, GUARD>(m->qkv, H, c.kv_heads, B, Kl, Vl, len_stride, m->rope, pos, m->attn, starts, smax, live, st); break;
-                case 4: gqa_attn_launch<4, GUARD>(m->qkv, H, c.kv_heads, B, Kl, Vl, len_stride, m->rope, pos, m->attn, starts, smax, live, st); break;
-                default: gqa_attn_launch<8, GUARD>(m->qkv, H, c.kv_heads, B, Kl, Vl, len_stride, m->rope, pos, m->attn, starts, smax, live, st); break;
-            }
-        } else if (starts)
-            hipLaunchKernelGGL((llm_attn_kernel<true, GUARD>), dim3(B * c.heads), dim3(64), attn_lds, st, m->qkv, H, c.heads, (half_t*)kp[l],
-                               (half_t*)vp[l], len_stride, m->rope, pos, m->attn, starts, smax, live);
-        else
-            hipLaunchKernelGGL((llm_attn_kernel<false, GUARD>), dim3(B * c.heads), dim3(64), attn_lds, st, m->qkv, H, c.heads, (half_t*)kp[l],
-                               (half_t*)vp[l], len_stride, m->rope, pos, m->attn, nullptr, 0, live);
-        LAUNCHED();
+        } else {
+            const StepAttnArgs a{c.grouped_kv ? c.heads / c.kv_heads : 0, m->qkv, H, c.heads, (half_t*)kp[l], (half_t*)vp[l], len_stride,
+                                 m->rope, pos, m->attn, starts, smax, live};
+            HIPCHK(launch_llm_step_attention(a, B, st));
+        }
         CGCHK(gemm(m, DEC_F16_RESID, m->attn, H, L.wo, H, m->h, H, m->h, B, st, live));
-        hipLaunchKernelGGL(llm_rmsnorm_kernel<GUARD>, dim3(B), dim3(256), 0, st, m->h, L.ln2, H, c.rms_eps, m->xn, live);
-        LAUNCHED();
+        HIPCHK(launch_llm_rmsnorm(m->h, L.ln2, H, c.rms_eps, m->xn, B, st, live));
         CGCHK(gemm(m, DEC_SWIGLU, m->xn, H, L.wgu, 2 * c.mlp, m->act, c.mlp, nullptr, B, st, live));
         CGCHK(gemm(m, DEC_F16_RESID, m->act, c.mlp, L.wdown, H, m->h, H, m->h, B, st, live));
     }
-    hipLaunchKernelGGL(llm_rmsnorm_kernel<GUARD>, dim3(B), dim3(256), 0, st, m->h, m->norm, H, c.rms_eps, m->xn, live);
-    LAUNCHED();
+    HIPCHK(launch_llm_rmsnorm(m->h, m->norm, H, c.rms_eps, m->xn, B, st, live));
     return gemm(m, DEC_F32, m->xn, H, Mat{m->lm_head}, c.vocab, logits, ld_logits, nullptr, B, st, live);
 }
 
@@ -693,20 +224,15 @@ cgpt_status run_step(cgpt_llm* m, const long long* tokens, int B, int pos, const
 // On an int8 handle the matrix is first expanded into the handle's scratch (all up256(N) rows, pad rows zeros), on the same stream:
 // the expansion of the next matrix is ordered behind this GEMM, so one scratch serves every layer.
 cgpt_status big_gemm(cgpt_llm* m, const half_t* A, int K, const Mat& Wm, int N, half_t* out, int64_t M, hipStream_t st) {
+    const LlmCfg& c = m->cfg;
     const half_t* W = Wm.w;
-    if (m->cfg.act_format && Wm.q) {                       // activations-int8 handle: the token step's two launches on M rows (row tiles
-        HIPCHK(launch_act_quant(A, M, K, m->cfg.act_threshold, m->cfg.outlier_cap, m->p_a8, m->p_sa, m->p_lists, m->act_counters, st));
-        I8GemmParams q{};                                  // on the grid's second dimension); no expansion, no scratch
-        q.A = m->p_a8; q.lda = K; q.sa = m->p_sa; q.lists = m->p_lists; q.cap = m->cfg.outlier_cap; q.W = Wm.q; q.ldw = K; q.wscale = Wm.s;
-        q.out = out; q.ldo = N; q.resid = nullptr; q.ldr = 0; q.slabs = reinterpret_cast<int*>(m->slabs);
-        q.M = (int)M; q.N = N; q.K = K;
-        HIPCHK(launch_i8_gemm(DEC_F16, q, st));
+    if (c.act_format && Wm.q) {     // activations-int8 handle: the token step's two launches on M rows (row tiles on the grid's second
+        HIPCHK(launch_act_quant(A, M, K, c.act_threshold, c.outlier_cap, m->p_a8, m->p_sa, m->p_lists, m->act_counters, st));
+        HIPCHK(launch_i8_gemm(DEC_F16, i8_params(m->p_a8, m->p_sa, m->p_lists, c.outlier_cap, Wm.q, Wm.s, out, N, nullptr, m->slabs, M, N, K), st));
         return CGPT_OK;
     }
     if (Wm.q) {
-        const int64_t chunks = (int64_t)((N + 255) / 256 * 256) * (K / 16);
-        hipLaunchKernelGGL(llm_dequant_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, st, Wm.q, Wm.s, K, chunks, m->scratch);
-        HIPCHK(hipGetLastError());
+        HIPCHK(launch_llm_dequant(Wm.q, Wm.s, N, K, m->scratch, st));
         W = m->scratch;
     }
     GemmParams p{};
@@ -716,34 +242,20 @@ cgpt_status big_gemm(cgpt_llm* m, const half_t* A, int K, const Mat& Wm, int N, 
     return CGPT_OK;
 }
 
-// The prefill of B prompts of L positions: embeds [B, L, hidden] -> cache rows 0 .. L-1 of every layer, last-position logits.
-// The residual stream stays fp16 as in HF; a projection's output is added by the NEXT add + RMSNorm pass (`pending`).
-// starts (device, or null): row b is left-padded by start[b] positions.  Only the rotary and attention kernels look at it; pad
-// rows pass through the row-independent kernels and GEMMs like any other row (zero embeds stay zeros).
-// pos0 > 0 (cgpt_llm_prefill_from): the L positions follow pos0 positions whose cache rows exist; only the rotary and attention launches
-// differ (their _from twins).  pos0 = 0 launches what it always launched.
-cgpt_status run_prefill(cgpt_llm* m, const half_t* embeds, int B, int L, const int32_t* starts, void* const* kp, void* const* vp,
-                        int64_t len_stride, float* logits, hipStream_t st, int pos0 = 0) {
+// The layers of the prefill and of the scoring pass on M token rows of the prefill workspace: x (layer 0's input rows) -> m->p_h,
+// with the last layer's down projection left PENDING in m->p_proj: the residual stream stays fp16 as in HF, and a projection's output
+// is added by the NEXT add + RMSNorm pass.  attention(l) enqueues what turns m->p_qkv into m->p_attn and returns the launch's error.
+template <typename Attn>
+cgpt_status run_layers(cgpt_llm* m, const half_t* x, int64_t M, hipStream_t st, Attn attention) {
     const cgpt_llm_config& c = m->cfg;
     const int H = c.hidden, F = c.mlp;
-    const int64_t M = (int64_t)B * L;
-    const half_t* x = embeds;                              // layer 0 reads the caller's rows and writes the stream
     const half_t* pending = nullptr;
     for (int l = 0; l < c.layers; ++l) {
         const Layer& Lw = m->layers[l];
         HIPCHK(launch_prefill_addnorm(x, pending, 1, 0, Lw.ln1, H, c.rms_eps, m->p_h, m->p_xn, M, st));
         x = m->p_h;
         CGCHK(big_gemm(m, m->p_xn, H, Lw.wqkv, qkv_width(c), m->p_qkv, M, st));
-        if (pos0 > 0) {
-            HIPCHK(launch_prefill_rope_from(m->p_qkv, B, pos0, L, H, c.heads, c.kv_heads, (half_t*)kp[l], (half_t*)vp[l], len_stride, m->rope,
-                                            starts, st));
-            HIPCHK(launch_prefill_attention_from(m->p_qkv, B, pos0, L, H, c.heads, c.kv_heads, (const half_t*)kp[l], (const half_t*)vp[l],
-                                                 len_stride, m->p_attn, starts, st));
-        } else {
-            HIPCHK(launch_prefill_rope(m->p_qkv, B, L, H, c.heads, c.kv_heads, (half_t*)kp[l], (half_t*)vp[l], len_stride, m->rope, starts, st));
-            HIPCHK(launch_prefill_attention(m->p_qkv, B, L, H, c.heads, c.kv_heads, (const half_t*)kp[l], (const half_t*)vp[l], len_stride,
-                                              m->p_attn, starts, st));
-        }
+        HIPCHK(attention(l));
         CGCHK(big_gemm(m, m->p_attn, H, Lw.wo, H, m->p_proj, M, st));
         HIPCHK(launch_prefill_addnorm(m->p_h, m->p_proj, 1, 0, Lw.ln2, H, c.rms_eps, m->p_h, m->p_xn, M, st));
         CGCHK(big_gemm(m, m->p_xn, H, Lw.wgu, 2 * F, m->p_gu, M, st));
@@ -751,42 +263,49 @@ cgpt_status run_prefill(cgpt_llm* m, const half_t* embeds, int B, int L, const i
         CGCHK(big_gemm(m, m->p_act, F, Lw.wdown, H, m->p_proj, M, st));
         pending = m->p_proj;
     }
-    // tail, as run_step ends: the last position's row of every prompt (with its pending update) into the step workspace
-    HIPCHK(launch_prefill_addnorm(m->p_h, pending, L, L - 1, m->norm, H, c.rms_eps, m->h, m->xn, B, st));
-    return gemm(m, DEC_F32, m->xn, H, Mat{m->lm_head}, c.vocab, logits, c.vocab, nullptr, B, st);
+    return CGPT_OK;
 }
 
+// The prefill of B prompts of L positions: embeds [B, L, hidden] -> cache rows 0 .. L-1 of every layer, last-position logits.
+// starts (device, or null): row b is left-padded by start[b] positions.  Only the rotary and attention kernels look at it; pad
+// rows pass through the row-independent kernels and GEMMs like any other row (zero embeds stay zeros).  pos0 > 0
+// (cgpt_llm_prefill_from): the L positions follow pos0 positions whose cache rows exist; rotary and attention are the _from twins.
+cgpt_status run_prefill(cgpt_llm* m, const half_t* embeds, int B, int L, const int32_t* starts, void* const* kp, void* const* vp,
+                        int64_t len_stride, float* logits, hipStream_t st, int pos0 = 0) {
+    const cgpt_llm_config& c = m->cfg;
+    const int H = c.hidden;
+    CGCHK(run_layers(m, embeds, (int64_t)B * L, st, [&](int l) {
+        half_t *K = (half_t*)kp[l], *V = (half_t*)vp[l];
+        const hipError_t e = pos0 > 0 ? launch_prefill_rope_from(m->p_qkv, B, pos0, L, H, c.heads, c.kv_heads, K, V, len_stride, m->rope, starts, st)
+                                      : launch_prefill_rope(m->p_qkv, B, L, H, c.heads, c.kv_heads, K, V, len_stride, m->rope, starts, st);
+        if (e != hipSuccess) return e;
+        return pos0 > 0 ? launch_prefill_attention_from(m->p_qkv, B, pos0, L, H, c.heads, c.kv_heads, K, V, len_stride, m->p_attn, starts, st)
+                        : launch_prefill_attention(m->p_qkv, B, L, H, c.heads, c.kv_heads, K, V, len_stride, m->p_attn, starts, st);
+    }));
+    // tail, as run_step ends: the last position's row of every prompt (with its pending update) into the step workspace
+    HIPCHK(launch_prefill_addnorm(m->p_h, m->p_proj, L, L - 1, m->norm, H, c.rms_eps, m->h, m->xn, B, st));
+    return gemm(m, DEC_F32, m->xn, H, Mat{m->lm_head}, c.vocab, logits, c.vocab, nullptr, B, st);
+}
 
 constexpr int64_t SCORE_LOGIT_ROWS = 4096;                 // tail rows whose fp16 logits are held at once (262 MB at 32 000 columns)
 
 // All candidates of `t` on the prompt cache rows 0 .. L-1 of B prompt rows: out[b, c] = summed label-smoothed cross-entropy.
-// run_prefill's layer sequence on the R = B S tail rows with the tail attention in place of rotary + cache write + causal
-// attention; then lm_head and the cross-entropy in chunks of the reserved logits rows.  No cache row is written.
-// starts / row_lens (device, or both null: the plain kernels): per-row left padding and per-row candidates [B, C, tmax], see llm.h.
+// run_prefill's layers on the R = B S tail rows with the tail attention in place of rotary + cache write + causal attention; then
+// lm_head and the cross-entropy in chunks of the reserved logits rows.  No cache row is written.  starts / row_lens: see llm.h.
 cgpt_status run_score(cgpt_llm* m, const float* first_logits, int B, int L, const int32_t* starts, const long long* cand_tokens,
                       const int32_t* row_lens, const ScoreCands& t, float eps, void* const* kp, void* const* vp, int64_t len_stride,
                       float* out, hipStream_t st) {
     const cgpt_llm_config& c = m->cfg;
-    const int H = c.hidden, F = c.mlp, S = t.off[t.n];
+    const int H = c.hidden, S = t.off[t.n];
     const int64_t R = (int64_t)B * S;
     HIPCHK(launch_score_ce_first(first_logits, c.vocab, cand_tokens, t, B, eps, m->s_ce_buf, st, row_lens));
     if (S > 0) {
         HIPCHK(launch_score_embed(cand_tokens, t, B, m->embed, c.vocab, H, m->p_h, st, row_lens != nullptr));
-        const half_t* pending = nullptr;
-        for (int l = 0; l < c.layers; ++l) {
-            const Layer& Lw = m->layers[l];
-            HIPCHK(launch_prefill_addnorm(m->p_h, pending, 1, 0, Lw.ln1, H, c.rms_eps, m->p_h, m->p_xn, R, st));
-            CGCHK(big_gemm(m, m->p_xn, H, Lw.wqkv, qkv_width(c), m->p_qkv, R, st));
-            HIPCHK(launch_score_attention(m->p_qkv, t, B, L, H, c.heads, c.kv_heads, (const half_t*)kp[l], (const half_t*)vp[l], len_stride, m->rope,
-                                          m->p_attn, st, starts));
-            CGCHK(big_gemm(m, m->p_attn, H, Lw.wo, H, m->p_proj, R, st));
-            HIPCHK(launch_prefill_addnorm(m->p_h, m->p_proj, 1, 0, Lw.ln2, H, c.rms_eps, m->p_h, m->p_xn, R, st));
-            CGCHK(big_gemm(m, m->p_xn, H, Lw.wgu, 2 * F, m->p_gu, R, st));
-            HIPCHK(launch_prefill_swiglu(m->p_gu, R, F, m->p_act, st));
-            CGCHK(big_gemm(m, m->p_act, F, Lw.wdown, H, m->p_proj, R, st));
-            pending = m->p_proj;
-        }
-        HIPCHK(launch_prefill_addnorm(m->p_h, pending, 1, 0, m->norm, H, c.rms_eps, m->p_h, m->p_xn, R, st));
+        CGCHK(run_layers(m, m->p_h, R, st, [&](int l) {
+            return launch_score_attention(m->p_qkv, t, B, L, H, c.heads, c.kv_heads, (const half_t*)kp[l], (const half_t*)vp[l], len_stride, m->rope,
+                                          m->p_attn, st, starts);
+        }));
+        HIPCHK(launch_prefill_addnorm(m->p_h, m->p_proj, 1, 0, m->norm, H, c.rms_eps, m->p_h, m->p_xn, R, st));
         for (int64_t r0 = 0; r0 < R; r0 += m->s_rows) {        // chunks begin at multiples of 256 rows: whole GEMM row tiles
             const int64_t n = std::min(m->s_rows, R - r0);
             CGCHK(big_gemm(m, m->p_xn + r0 * H, H, Mat{m->lm_head}, c.vocab, m->s_logits, n, st));
@@ -864,10 +383,11 @@ cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
     if (c.max_batch < 1 || c.max_batch > MAX_ROWS) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: max_batch must be 1..256");
     if (c.max_len < 1 || c.max_len > 8192) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: max_len must be 1..8192");
     if (!(c.rms_eps > 0.0f) || !(c.rope_theta > 0.0f)) return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: rms_eps and rope_theta must be positive");
-    if (c.grouped_kv && gqa_attn_lds_bytes(c.heads / c.kv_heads, c.max_len) > LDS_PER_CU)
-        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: grouped_kv with heads / kv_heads = " + std::to_string(c.heads / c.kv_heads) +
+    const int G = c.grouped_kv ? c.heads / c.kv_heads : 0;        // the step attention's kernel family (StepAttnArgs)
+    if (G && llm_step_attn_lds_bytes(G, c.max_len) > LDS_PER_CU)
+        return cgpt_fail(CGPT_ERR_INVALID, "cgpt_llm_create: grouped_kv with heads / kv_heads = " + std::to_string(G) +
                                                " and max_len = " + std::to_string(c.max_len) + " needs " +
-                                               std::to_string(gqa_attn_lds_bytes(c.heads / c.kv_heads, c.max_len)) +
+                                               std::to_string(llm_step_attn_lds_bytes(G, c.max_len)) +
                                                " bytes of LDS for the token step's scores, a CU has 163840: lower max_len");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -877,14 +397,7 @@ cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
     HIPCHK(decode_gemm_prepare());                        // kernel attributes now: nothing but launches is left for a captured stream
     HIPCHK(score_prepare());
     if (c.act_format) HIPCHK(i8_gemm_prepare());
-    if (c.grouped_kv) {                                   // the grouped step attention's dynamic LDS, for this handle's longest row
-        switch (c.heads / c.kv_heads) {
-            case 1: HIPCHK(gqa_attn_prepare<1>(c.max_len)); break;
-            case 2: HIPCHK(gqa_attn_prepare<2>(c.max_len)); break;
-            case 4: HIPCHK(gqa_attn_prepare<4>(c.max_len)); break;
-            default: HIPCHK(gqa_attn_prepare<8>(c.max_len)); break;
-        }
-    }
+    HIPCHK(llm_step_prepare(G, c.max_len));               // the grouped step attention's dynamic LDS, for this handle's longest row
     cgpt_llm* m = new cgpt_llm();
     m->cfg = c;
     m->layers.resize(c.layers);
@@ -946,8 +459,7 @@ cgpt_status cgpt_llm_create(const cgpt_llm_config* cfg, cgpt_llm_handle* out) {
     for (int i = 0; i < 64; ++i) inv_host[i] = 1.0f / powf(c.rope_theta, (float)(2 * i) / (float)HD);
     if (hipMemcpy(inv_freq, inv_host, sizeof(inv_host), hipMemcpyHostToDevice) != hipSuccess)
         return fail(cgpt_fail(CGPT_ERR_HIP, "cgpt_llm_create: inv_freq upload failed"));
-    hipLaunchKernelGGL(llm_rope_table_kernel, dim3(c.max_len), dim3(64), 0, 0, inv_freq, m->rope);
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+    if (launch_llm_rope_table(inv_freq, m->rope, c.max_len, 0) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
         return fail(cgpt_fail(CGPT_ERR_HIP, "cgpt_llm_create: rotary table kernel failed"));
     *out = m;
     return CGPT_OK;
@@ -1029,11 +541,8 @@ cgpt_status cgpt_llm_linear_i8(const void* A_dev, const void* q_dev, const void*
     HIPCHK(hipMemsetAsync(ws + off[0], 0, 4 * sizeof(unsigned long long), st));
     HIPCHK(launch_act_quant((const half_t*)A_dev, M, (int)K, threshold, outlier_cap, (signed char*)(ws + off[1]), (float*)(ws + off[2]),
                             (uint32_t*)(ws + off[3]), (unsigned long long*)(ws + off[0]), st));
-    I8GemmParams p{};
-    p.A = (const signed char*)(ws + off[1]); p.lda = K; p.sa = (const float*)(ws + off[2]); p.lists = (const uint32_t*)(ws + off[3]);
-    p.cap = outlier_cap; p.W = (const signed char*)q_dev; p.ldw = K; p.wscale = (const half_t*)sw_dev; p.out = (half_t*)out_dev; p.ldo = ncols;
-    p.resid = (const half_t*)resid_dev; p.ldr = ncols; p.slabs = (int*)(ws + off[4]);
-    p.M = (int)M; p.N = (int)N; p.K = (int)K;
+    const I8GemmParams p = i8_params((const signed char*)(ws + off[1]), (const float*)(ws + off[2]), (const uint32_t*)(ws + off[3]), outlier_cap,
+                                     (const signed char*)q_dev, (const half_t*)sw_dev, out_dev, ncols, (const half_t*)resid_dev, ws + off[4], M, (int)N, (int)K);
     HIPCHK(launch_i8_gemm(epilogue, p, st));
     return CGPT_OK;
 }
@@ -1073,9 +582,7 @@ cgpt_status cgpt_llm_load_weight_f16(cgpt_llm_handle h, const char* name, const 
                                                std::to_string(numel));
     HIPCHK(hipSetDevice(c.device));
     if (mat && mat->q) {                                   // int8 handle: quantise the caller's rows straight into the fused matrix
-        hipLaunchKernelGGL(llm_quant_rows_kernel, dim3((unsigned)(want / K)), dim3(256), 0, st, (const half_t*)data_dev, (int)K, interleave,
-                           mat->q + row0 * K, mat->s + row0);
-        LAUNCHED();
+        HIPCHK(launch_llm_quant_rows((const half_t*)data_dev, (int)(want / K), (int)K, interleave, mat->q + row0 * K, mat->s + row0, st));
         h->loaded.insert(n);
         return CGPT_OK;
     }
@@ -1099,7 +606,7 @@ static cgpt_status llm_step_entry(const char* who, cgpt_llm_handle h, const int6
     CGCHK(ready(h, who));
     HIPCHK(hipSetDevice(h->cfg.device));
     CGCHK(check_cache(h, who, B, pos, k_ptrs_host, v_ptrs_host, kv_len_stride));
-    return run_step<false>(h, (const long long*)tokens_dev, B, pos, starts_dev, pos, k_ptrs_host, v_ptrs_host, kv_len_stride, logits_dev,
+    return run_step(h, nullptr, (const long long*)tokens_dev, B, pos, starts_dev, pos, k_ptrs_host, v_ptrs_host, kv_len_stride, logits_dev,
                     h->cfg.vocab, (hipStream_t)stream);
 }
 
@@ -1154,62 +661,33 @@ static cgpt_status llm_greedy_entry(const char* who_c, cgpt_llm_handle h, const 
     h->last_on = early ? 1 : 0;
     h->off_steps = num_new - 1;
     for (int i = 0; i < num_new; ++i) {
-        const float* src;
-        int64_t lds;
-        if (i == 0) { src = first_logits_dev; lds = V; }
-        else if (step_logits_out_dev) { src = step_logits_out_dev + (int64_t)i * V; lds = ld_out; }
-        else { src = h->logits; lds = V; }
+        const bool own = i > 0 && step_logits_out_dev;     // the step before wrote its logits into the caller's buffer
+        const float* src = i == 0 ? first_logits_dev : own ? step_logits_out_dev + (int64_t)i * V : h->logits;
+        const int64_t lds = own ? ld_out : (int64_t)V;
         const int mask = (i < min_new && num_eos > 0) ? 1 : 0;
-        float* dst = nullptr;
-        if (step_logits_out_dev && (i == 0 || mask)) dst = step_logits_out_dev + (int64_t)i * V;
+        float* dst = step_logits_out_dev && (i == 0 || mask) ? step_logits_out_dev + (int64_t)i * V : nullptr;
         stop.col = i;
+        const int first = i == 0 ? 1 : 0;
+        const int* live = early ? h->live : nullptr;
+        const SelectArgs a{src, lds, dst, ld_out, V, mask, eos, (long long)pad_id, first, h->unfinished,
+                           (long long*)tokens_out_dev + i, (int64_t)num_new, h->tok, live};
         if (constrained) {                                 // tables as the handle holds them now: a captured call keeps them
             if (i == 0 && step_logits_out_dev) HIPCHK(launch_llm_copy_rows(first_logits_dev, V, step_logits_out_dev, ld_out, V, B, st));
-            TrieArgs a{src, lds, h->t_begin, h->t_tok, h->t_node, h->t_leaf, h->t_nodes, (long long)pad_id, i == 0 ? 1 : 0, h->trie_node,
-                       h->unfinished, (long long*)tokens_out_dev + i, (int64_t)num_new, h->tok, labels_out_dev, early ? h->live : nullptr};
-            HIPCHK(launch_llm_trie_select(early, a, B, st));
-            if (early)
-                hipLaunchKernelGGL(llm_live_kernel, dim3(1), dim3(256), 0, st, h->unfinished, B, i == 0 ? 1 : 0, i + 1 < num_new ? 1 : 0,
-                                   h->live, h->live_steps);
+            TrieArgs ta{src, lds, h->t_begin, h->t_tok, h->t_node, h->t_leaf, h->t_nodes, a.pad, first, h->trie_node,
+                        h->unfinished, a.tokens_out, a.ld_tokens, h->tok, labels_out_dev, live};
+            HIPCHK(launch_llm_trie_select(early, ta, B, st));
         } else if (sample) {
-            SelectArgs a{src, lds, dst, ld_out, V, mask, eos, (long long)pad_id, i == 0 ? 1 : 0, h->unfinished,
-                         (long long*)tokens_out_dev + i, (int64_t)num_new, h->tok, early ? h->live : nullptr};
             SampleIo io{(const long long*)tokens_out_dev, (int64_t)num_new, i, i, (const long long*)draw_ids_dev,
                         (const unsigned long long*)seed_dev, nullptr, nullptr, nullptr, nullptr};
             HIPCHK(launch_llm_sample(early, stop.n > 0 ? &stop : nullptr, a, law, io, B, st));
-            if (early)
-                hipLaunchKernelGGL(llm_live_kernel, dim3(1), dim3(256), 0, st, h->unfinished, B, i == 0 ? 1 : 0, i + 1 < num_new ? 1 : 0,
-                                   h->live, h->live_steps);
-        } else if (early) {
-            if (stop.n > 0)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(llm_select_kernel<true, true>), dim3(B), dim3(256), 0, st, src, lds, dst, ld_out, V, mask,
-                                   eos, (long long)pad_id, i == 0 ? 1 : 0, h->unfinished, (long long*)tokens_out_dev + i, (int64_t)num_new,
-                                   h->tok, h->live, stop);
-            else
-                hipLaunchKernelGGL(llm_select_kernel<true>, dim3(B), dim3(256), 0, st, src, lds, dst, ld_out, V, mask, eos,
-                                   (long long)pad_id, i == 0 ? 1 : 0, h->unfinished, (long long*)tokens_out_dev + i, (int64_t)num_new,
-                                   h->tok, h->live, NoStop{});
-            LAUNCHED();
-            hipLaunchKernelGGL(llm_live_kernel, dim3(1), dim3(256), 0, st, h->unfinished, B, i == 0 ? 1 : 0, i + 1 < num_new ? 1 : 0,
-                               h->live, h->live_steps);
-        } else if (stop.n > 0) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(llm_select_kernel<false, true>), dim3(B), dim3(256), 0, st, src, lds, dst, ld_out, V, mask,
-                               eos, (long long)pad_id, i == 0 ? 1 : 0, h->unfinished, (long long*)tokens_out_dev + i, (int64_t)num_new,
-                               h->tok, nullptr, stop);
         } else {
-            hipLaunchKernelGGL(llm_select_kernel<false>, dim3(B), dim3(256), 0, st, src, lds, dst, ld_out, V, mask, eos, (long long)pad_id,
-                               i == 0 ? 1 : 0, h->unfinished, (long long*)tokens_out_dev + i, (int64_t)num_new, h->tok, nullptr, NoStop{});
+            HIPCHK(launch_llm_select(early, stop.n > 0 ? &stop : nullptr, a, B, st));
         }
-        LAUNCHED();
+        if (early) HIPCHK(launch_llm_live(h->unfinished, B, first, i + 1 < num_new ? 1 : 0, h->live, h->live_steps, st));
         if (i + 1 == num_new) break;
         float* next = step_logits_out_dev ? step_logits_out_dev + (int64_t)(i + 1) * V : h->logits;
-        const int64_t ld_next = step_logits_out_dev ? ld_out : (int64_t)V;
-        if (early)
-            CGCHK(run_step<true>(h, h->tok, B, prompt_len + i, starts_dev, prompt_len - 1, k_ptrs_host, v_ptrs_host, kv_len_stride, next,
-                                 ld_next, st));
-        else
-            CGCHK(run_step<false>(h, h->tok, B, prompt_len + i, starts_dev, prompt_len - 1, k_ptrs_host, v_ptrs_host, kv_len_stride, next,
-                                  ld_next, st));
+        CGCHK(run_step(h, live, h->tok, B, prompt_len + i, starts_dev, prompt_len - 1, k_ptrs_host, v_ptrs_host, kv_len_stride, next,
+                       step_logits_out_dev ? ld_out : (int64_t)V, st));
     }
     return CGPT_OK;
 }
@@ -1284,20 +762,21 @@ cgpt_status cgpt_llm_beam_reserve(cgpt_llm_handle h, int32_t max_images, int32_t
     if (rows <= h->bm_rows && elems <= h->bm_elems) return CGPT_OK;    // grows only; a second call with the same sizes does nothing
     HIPCHK(hipSetDevice(h->cfg.device));
     const size_t R = (size_t)std::max(rows, h->bm_rows), E = (size_t)std::max(elems, h->bm_elems);
+    Staging stage;
     BeamState fresh[2]{};                                              // complete before it takes the old sets' place
     for (BeamState& s : fresh) {
-        CGCHK(dev_zalloc(h, R * sizeof(float), (void**)&s.running));
-        CGCHK(dev_zalloc(h, E * sizeof(long long), (void**)&s.tokens));
-        CGCHK(dev_zalloc(h, E * sizeof(int32_t), (void**)&s.anc));
-        CGCHK(dev_zalloc(h, R * sizeof(float), (void**)&s.pool_score));
-        CGCHK(dev_zalloc(h, R * sizeof(int32_t), (void**)&s.pool_fin));
-        CGCHK(dev_zalloc(h, R * sizeof(int32_t), (void**)&s.pool_len));
-        CGCHK(dev_zalloc(h, E * sizeof(long long), (void**)&s.pool_seq));
-        CGCHK(dev_zalloc(h, R * sizeof(int32_t), (void**)&s.open));
+        stage.add(&s.running, R * sizeof(float));
+        stage.add(&s.tokens, E * sizeof(long long));
+        stage.add(&s.anc, E * sizeof(int32_t));
+        stage.add(&s.pool_score, R * sizeof(float));
+        stage.add(&s.pool_fin, R * sizeof(int32_t));
+        stage.add(&s.pool_len, R * sizeof(int32_t));
+        stage.add(&s.pool_seq, E * sizeof(long long));
+        stage.add(&s.open, R * sizeof(int32_t));
     }
     int32_t* parents = nullptr;
-    CGCHK(dev_zalloc(h, R * sizeof(int32_t), (void**)&parents));
-    HIPCHK(hipDeviceSynchronize());
+    stage.add(&parents, R * sizeof(int32_t));
+    CGCHK(stage.commit(h, who));
     h->bm[0] = fresh[0]; h->bm[1] = fresh[1]; h->bm_parents = parents;
     h->bm_rows = (int64_t)R; h->bm_elems = (int64_t)E;
     return CGPT_OK;
@@ -1340,7 +819,7 @@ cgpt_status cgpt_llm_beam_step(cgpt_llm_handle h, const int64_t* tokens_dev, int
     CGCHK(ready(h, who.c_str()));
     HIPCHK(hipSetDevice(h->cfg.device));
     const BeamStep bs{prompt_k_ptrs_host, prompt_v_ptrs_host, prompt_stride, anc_dev, anc_ld, k, prompt_len, t};
-    return run_step<false>(h, (const long long*)tokens_dev, B * k, prompt_len + t, nullptr, 0, beam_k_ptrs_host, beam_v_ptrs_host, beam_stride,
+    return run_step(h, nullptr, (const long long*)tokens_dev, B * k, prompt_len + t, nullptr, 0, beam_k_ptrs_host, beam_v_ptrs_host, beam_stride,
                            logits_dev, h->cfg.vocab, (hipStream_t)stream, &bs);
 }
 
@@ -1398,7 +877,7 @@ cgpt_status cgpt_llm_beam(cgpt_llm_handle h, const float* first_logits_dev, int3
         if (last) break;
         float* next = step_logits_out_dev ? step_logits_out_dev + (int64_t)(i + 1) * V : h->logits;
         const BeamStep bs{prompt_k_ptrs_host, prompt_v_ptrs_host, prompt_stride, a.out.anc, num_new, k, prompt_len, i};
-        CGCHK(run_step<false>(h, h->tok, rows, prompt_len + i, nullptr, 0, beam_k_ptrs_host, beam_v_ptrs_host, beam_stride, next,
+        CGCHK(run_step(h, nullptr, h->tok, rows, prompt_len + i, nullptr, 0, beam_k_ptrs_host, beam_v_ptrs_host, beam_stride, next,
                               step_logits_out_dev ? ld_out : (int64_t)V, st, &bs));
     }
     return CGPT_OK;
@@ -1479,38 +958,22 @@ static cgpt_status grow_workspace(cgpt_llm_handle h, int64_t rows, const std::st
     HIPCHK(hipSetDevice(h->cfg.device));
     const size_t H = h->cfg.hidden, F = h->cfg.mlp, hs = sizeof(half_t);
     const size_t cols[7] = {H, H, (size_t)qkv_width(h->cfg), H, H, 2 * F, F};
-    // The larger workspace is built beside the one in use and takes its place only when it is complete: a failure leaves the
-    // handle as it was.  The replaced buffers are NOT freed (they stay in `allocs` until destroy): a graph captured before this
-    // call replays on their addresses.
+    Staging stage;                                         // the larger workspace takes the old one's place only when it is complete
     half_t* fresh[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 7 && e == hipSuccess; ++i) {
-        e = hipMalloc((void**)&fresh[i], (size_t)rows * cols[i] * hs);
-        if (e == hipSuccess) e = hipMemset(fresh[i], 0, (size_t)rows * cols[i] * hs);
-    }
+    for (int i = 0; i < 7; ++i) stage.add(&fresh[i], (size_t)rows * cols[i] * hs);
     // activations-int8 handles: codes, row scales and outlier lists for the same rows
-    void* fresh8[3] = {nullptr, nullptr, nullptr};
-    const size_t bytes8[3] = {(size_t)rows * std::max(H, F), (size_t)rows * sizeof(float),
-                              (size_t)rows * (size_t)(h->cfg.outlier_cap + 1) * sizeof(uint32_t)};
-    for (int i = 0; i < 3 && e == hipSuccess && h->cfg.act_format; ++i) {
-        e = hipMalloc(&fresh8[i], bytes8[i]);
-        if (e == hipSuccess) e = hipMemset(fresh8[i], 0, bytes8[i]);
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        for (half_t* p : fresh) (void)hipFree(p);
-        for (void* p : fresh8) (void)hipFree(p);
-        return cgpt_fail(CGPT_ERR_HIP, who + ": workspace allocation failed -> " + hipGetErrorString(e));
-    }
-    half_t** bufs[7] = {&h->p_h, &h->p_xn, &h->p_qkv, &h->p_attn, &h->p_proj, &h->p_gu, &h->p_act};
-    for (int i = 0; i < 7; ++i) {
-        *bufs[i] = fresh[i];
-        h->allocs.push_back(fresh[i]);
-    }
+    signed char* a8 = nullptr;
+    float* sa = nullptr;
+    uint32_t* lists = nullptr;
     if (h->cfg.act_format) {
-        h->p_a8 = (signed char*)fresh8[0]; h->p_sa = (float*)fresh8[1]; h->p_lists = (uint32_t*)fresh8[2];
-        for (void* p : fresh8) h->allocs.push_back(p);
+        stage.add(&a8, (size_t)rows * std::max(H, F));
+        stage.add(&sa, (size_t)rows * sizeof(float));
+        stage.add(&lists, (size_t)rows * (size_t)(h->cfg.outlier_cap + 1) * sizeof(uint32_t));
     }
+    CGCHK(stage.commit(h, who));
+    half_t** bufs[7] = {&h->p_h, &h->p_xn, &h->p_qkv, &h->p_attn, &h->p_proj, &h->p_gu, &h->p_act};
+    for (int i = 0; i < 7; ++i) *bufs[i] = fresh[i];
+    if (h->cfg.act_format) { h->p_a8 = a8; h->p_sa = sa; h->p_lists = lists; }
     h->p_rows = rows;
     return CGPT_OK;
 }
@@ -1597,26 +1060,14 @@ cgpt_status cgpt_llm_score_reserve(cgpt_llm_handle h, int32_t max_rows, int32_t 
     CGCHK(grow_workspace(h, rows, "cgpt_llm_score_reserve"));      // the tail rows run on the prefill workspace
     HIPCHK(hipSetDevice(h->cfg.device));
     const int64_t lrows = std::min(rows, SCORE_LOGIT_ROWS), nce = (int64_t)max_rows * (max_tail_rows + SCORE_MAX_CANDS);
-    // as the prefill workspace: built beside the buffers in use, which stay allocated until destroy
+    Staging stage;                                         // as the prefill workspace: beside the buffers in use
     half_t* logits = nullptr;
     float* ce = nullptr;
-    hipError_t e = hipSuccess;
-    if (lrows > h->s_rows) {
-        e = hipMalloc((void**)&logits, (size_t)lrows * h->cfg.vocab * sizeof(half_t));
-        if (e == hipSuccess) e = hipMemset(logits, 0, (size_t)lrows * h->cfg.vocab * sizeof(half_t));
-    }
-    if (e == hipSuccess && nce > h->s_ce) {
-        e = hipMalloc((void**)&ce, (size_t)nce * sizeof(float));
-        if (e == hipSuccess) e = hipMemset(ce, 0, (size_t)nce * sizeof(float));
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        (void)hipFree(logits);
-        (void)hipFree(ce);
-        return cgpt_fail(CGPT_ERR_HIP, std::string("cgpt_llm_score_reserve: workspace allocation failed -> ") + hipGetErrorString(e));
-    }
-    if (logits) { h->s_logits = logits; h->s_rows = lrows; h->allocs.push_back(logits); }
-    if (ce) { h->s_ce_buf = ce; h->s_ce = nce; h->allocs.push_back(ce); }
+    if (lrows > h->s_rows) stage.add(&logits, (size_t)lrows * h->cfg.vocab * sizeof(half_t));
+    if (nce > h->s_ce) stage.add(&ce, (size_t)nce * sizeof(float));
+    CGCHK(stage.commit(h, "cgpt_llm_score_reserve"));
+    if (logits) { h->s_logits = logits; h->s_rows = lrows; }
+    if (ce) { h->s_ce_buf = ce; h->s_ce = nce; }
     return CGPT_OK;
 }
 

@@ -4,7 +4,7 @@
 // `_beam_search`, a fixed-shape tensor algorithm -- as MiniGPT-4's demo calls it with its first slider.  The law is stated once in
 // llm_laws.py (`beam_step_law`).  Two kernels:
 //
-// llm_attn_beam_kernel: the token step's rotary + K/V append + one-query attention (llm_attn_kernel in llm.hip) for beam rows.  The k
+// llm_attn_beam_kernel: the token step's rotary + K/V append + one-query attention (llm_attn_kernel in llm_step.hip) for beam rows.  The k
 // beams of an image share its prompt, so the prompt cache holds ONE row per image; what the beams generate lives in a beam cache of
 // generated positions only, and HF's physical `reorder_cache` is an ancestry table: key s < t of beam row r is read from beam row
 // anc[r][s].  No K/V byte moves.  The arithmetic and the key order are llm_attn_kernel's (groups of four keys from key 0, fp32 dot
@@ -47,7 +47,7 @@ constexpr int HD = 128;
 constexpr float NEG = -1.0e9f;
 
 __device__ __forceinline__ float rf16(float v) { return (float)(half_t)v; }
-// fp16(a * b) as a value of its own (see llm.hip: the compiler must not contract it into an fma)
+// fp16(a * b) as a value of its own (see llm_step.hip: the compiler must not contract it into an fma)
 __device__ __forceinline__ float mul_f16(float a, float b) {
     float r = rf16(a * b);
     asm volatile("" : "+v"(r));

@@ -25,7 +25,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int HD = 128;
 
 __device__ __forceinline__ float rf16(float v) { return (float)(half_t)v; }
-// fp16(a * b) as a value of its own (llm.hip: kept from contracting into a fused multiply-add, which would skip the rounding)
+// fp16(a * b) as a value of its own (llm_step.hip: kept from contracting into a fused multiply-add, which would skip the rounding)
 __device__ __forceinline__ float mul_f16(float a, float b) {
     float r = rf16(a * b);
     asm volatile("" : "+v"(r));

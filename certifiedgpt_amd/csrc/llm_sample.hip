@@ -2,7 +2,7 @@
 //
 // Reference call replaced: HF `generate(do_sample=True, temperature, top_k, top_p, repetition_penalty)` as `Chat.answer_prepare`
 // calls it -- RepetitionPenaltyLogitsProcessor, TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper, softmax and
-// torch.multinomial on the device-global generator.  Here one kernel per select, in the slot of llm_select_kernel (llm.hip), draws
+// torch.multinomial on the device-global generator.  Here one kernel per select, in the slot of llm_select_kernel (llm_step.hip), draws
 // from a counter-based stream: the uniform of a row is a function of (seed, draw id, step) alone (philox.h, PHILOX_WORD_SAMPLE).
 //
 // The law (`sample_token_law` in minigpt4.py states it in float64), on one fp32 logits row:

@@ -8,7 +8,7 @@
 // scored on its cache: candidate c contributes T_c - 1 tail rows (its tokens 0 .. T_c - 2 at rotary positions L ..), which attend
 // over the prompt's cache rows and over the rotated keys of their own candidate's earlier tail rows.  Those keys and values live
 // in LDS only: NO cache row is written.
-// Rounding follows the token step (llm.hip: llm_attn_kernel): rotary products and their sum in fp16, scores, probabilities and
+// Rounding follows the token step (llm_step.hip: llm_attn_kernel): rotary products and their sum in fp16, scores, probabilities and
 // sums in fp32.  Plain vector stores, no atomics, fixed summation orders: a (row, candidate) result depends on nothing but that
 // row's prompt cache and that candidate's tokens -- not on the batch, not on the other candidates, not on the launch.
 //
@@ -33,7 +33,7 @@ constexpr int HD = 128;
 constexpr int KC = 64;                                       // prompt keys staged per chunk
 
 __device__ __forceinline__ float rf16(float v) { return (float)(half_t)v; }
-// fp16(a * b) as a value of its own (llm.hip: kept from contracting into a fused multiply-add, which would skip the rounding)
+// fp16(a * b) as a value of its own (llm_step.hip: kept from contracting into a fused multiply-add, which would skip the rounding)
 __device__ __forceinline__ float mul_f16(float a, float b) {
     float r = rf16(a * b);
     asm volatile("" : "+v"(r));

@@ -1,5 +1,5 @@
 // llm_select.h -- what the two token-select kernels share: the by-value id tables, the bookkeeping tail of one select
-// (llm_select_kernel in llm.hip: arg-max; llm_sample_kernel in llm_sample.hip: the sampling law) and the sampler's launcher.
+// (llm_select_kernel in llm_step.hip: arg-max; llm_sample_kernel in llm_sample.hip: the sampling law) and the selects' launchers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -68,8 +68,10 @@ struct SelectArgs {                                            // the arguments 
     int* unfinished; long long* tokens_out; int64_t ld_tokens; long long* next_tok; const int* live;
 };
 // One workgroup per row.  guard: the early-stop instantiation (reads *live); stop != null: the stop-sequence instantiation.
+// launch_llm_select is the arg-max select (llm_step.hip); its kernel takes the struct's fields as positional arguments.
 hipError_t launch_llm_sample(bool guard, const StopSeqs* stop, const SelectArgs& a, const SampleLaw& law, const SampleIo& io, int rows,
                              hipStream_t stream);
+hipError_t launch_llm_select(bool guard, const StopSeqs* stop, const SelectArgs& a, int rows, hipStream_t stream);
 
 // The checks every sampling entry makes before any launch (CGPT_ERR_INVALID naming `who`), and the settings as the kernel takes them.
 cgpt_status check_sample_params(const std::string& who, const cgpt_llm_sample_params& p, int vocab, int num_prev, int num_eos,

@@ -77,7 +77,7 @@ class _LinearRoute:
 
 def hip_decode_unsupported(llama_model, max_batch=None, grouped_kv=False, activations="fp16"):
     """Every property of `llama_model` (and of the classifier batch) that keeps it off the native token step (`decode="hip"`,
-    csrc/llm.hip), as a list of sentences; empty = supported.  The step kernels are written for HF `LlamaForCausalLM` in fp16 on
+    csrc/llm.hip, csrc/llm_step.hip), as a list of sentences; empty = supported.  The step kernels are written for HF `LlamaForCausalLM` in fp16 on
     a HIP device: bias-free linears, RMSNorm, `rotate_half` rotary with the default (unscaled) rope_theta law, as many K/V heads
     as query heads, head size 128, SwiGLU, no sliding window -- Vicuna-7B / 13B.  ALL failing properties are collected, so one
     message names them all.

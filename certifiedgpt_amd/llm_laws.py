@@ -16,7 +16,7 @@ to HF).  Dependencies point one way: llm_laws <- llm_engine <- minigpt4.
 import torch
 
 
-MAX_STOP_SEQS, MAX_STOP_LEN = 8, 8                                    # MAX_STOP, MAX_STOP_LEN of csrc/llm.hip
+MAX_STOP_SEQS, MAX_STOP_LEN = 8, 8                                    # MAX_STOP, MAX_STOP_LEN of csrc/llm_select.h
 
 
 def _as_rows(table):
@@ -296,7 +296,7 @@ def fp16_ulp(x):
     return 2.0 ** (math.floor(math.log2(max(float(x), 6.2e-5))) - 10)
 
 
-# ---- the weight law of weights="int8" (csrc/llm.hip: llm_quant_rows_kernel; include/cgpt.h: CGPT_LLM_W_INT8), in plain torch
+# ---- the weight law of weights="int8" (csrc/llm_step.hip: llm_quant_rows_kernel; include/cgpt.h: CGPT_LLM_W_INT8), in plain torch
 LAYER_LINEARS = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj",
                  "mlp.down_proj")
 

@@ -190,7 +190,7 @@ class MiniGPT4Classifier:
         #   library's GEMM (see _LinearRoute); same arithmetic contract (fp16 operands, fp32 accumulation, fp16 result), other rounding
         #   order than the vendor library: first-token logits within 4 fp16 ulp, same decisive-row rule.
         # decode = "hip": the prefill as under "graph" (routed or not), then every token step in this library's own kernels
-        #   (csrc/llm.hip: RMSNorm, decode-shape GEMMs, rotary + K/V append + one-query attention, token select) on the K/V the
+        #   (csrc/llm_step.hip, csrc/llm_gemm.hip: RMSNorm, decode-shape GEMMs, rotary + K/V append + one-query attention, token select) on the K/V the
         #   prefill wrote, captured into the same kind of graph.  Opt-in; a decoder the kernels do not support is a ValueError here,
         #   never another engine.  Parity: tests/test_gpu_llm_decode.py (teacher-forced logit error against HF's own fp16 error).
         # prefill = "hip" (with decode = "hip" only; anything else is a ValueError, never silently another engine): the prefill too

@@ -1,4 +1,4 @@
-"""decode="hip": the native LLaMA token step (csrc/llm.hip, csrc/llm_gemm.hip) against the installed HF LlamaForCausalLM.
+"""decode="hip": the native LLaMA token step (csrc/llm.hip, csrc/llm_step.hip, csrc/llm_gemm.hip) against the installed HF LlamaForCausalLM.
 
 Accuracy yardstick (teacher-forced): at every step the library, HF's fp16 forward and an fp32 copy of the same weights get HF's
 own token and HF's own cache; with e_hf = |HF fp16 - fp32| and e_lib = |library - fp32| over the logits of the step, the engine

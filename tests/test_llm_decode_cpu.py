@@ -1,4 +1,4 @@
-"""decode="hip" (the native LLaMA token step, csrc/llm.hip) without a GPU: the model check names every unsupported property and
+"""decode="hip" (the native LLaMA token step, csrc/llm.hip and csrc/llm_step.hip) without a GPU: the model check names every unsupported property and
 the constructor never builds another engine in its place; the cgpt_llm_* C-ABI is declared, bound with the declared signature
 and validates its arguments before any device call."""
 import ctypes as C

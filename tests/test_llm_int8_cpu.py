@@ -1,5 +1,5 @@
 """weights="int8" without a GPU: the weight law in plain torch (`quantize_rows_int8` / `dequantize_rows_int8`, the restatement of
-csrc/llm.hip's llm_quant_rows_kernel), the classifier's keyword validation (it runs before any device work) and the config struct's
+csrc/llm_step.hip's llm_quant_rows_kernel), the classifier's keyword validation (it runs before any device work) and the config struct's
 two valid sizes (cgpt_llm_create validates the config before it looks for a device).
 
 The law, per output row n of an fp16 nn.Linear.weight [N, K]:  s_n = fp16(absmax / 127) with the division in fp32;
